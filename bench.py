@@ -36,6 +36,7 @@ if ROOT not in sys.path:
 T_START = time.perf_counter()
 T_BLOCKS = {}             # seconds per block of the line (block_seconds)
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+MAX_HW_QUEUES = 2          # GPU_MAX_HW_QUEUES of the replicas block's child: never above 2 on a shared machine
 SHARDED_TIMEOUT_S = 180    # the sharded leg of N > 1 runs (a few plans of ~20-60 ms plus the communicator) never needs this long
 SCLK_GHZ = 2.4            # MI355X_MICROARCH.md: 256 CU x 2.4 GHz
 N_CUS, SIMDS_PER_CU = 256, 4
@@ -486,13 +487,66 @@ def replicas_block(args, cfg, budget_s, problem_npz=None, rs=None, sync_mode=Non
         cmd += ["--parts", str(args.parts)]
     if args.nodes:
         cmd += ["--nodes", str(args.nodes)]
-    env = dict(os.environ, GPU_MAX_HW_QUEUES=os.environ.get("GPU_MAX_HW_QUEUES", str(args.hw_queues)))
+    hwq = min(int(os.environ.get("GPU_MAX_HW_QUEUES") or args.hw_queues), MAX_HW_QUEUES)
+    env = dict(os.environ, GPU_MAX_HW_QUEUES=str(hwq))
     try:
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=budget_s + 240)
         line = [x for x in p.stdout.splitlines() if x.startswith("{")]
         return json.loads(line[-1])["replicas_on_one_gpu"] if line else {"error": (p.stdout + p.stderr)[-300:]}
     except Exception as e:
         return {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def dump_outputs(res, out_dir, limit_bytes=DUMP_LIMIT_BYTES, seed=20261015):
+    """`--dump-outputs DIR`: what the timed path computed in its last step -- the arrays a caller of PlanNextMap receives
+    (abi.FlatResult: out_kind, out_off, out_nodes, the warnings, and iterations / converged / n_warnings as `summary`) -- as
+    DIR/<name>.npy, each in float32 when every value is exact in it, else float64.  The warnings (at most one per partition
+    and state, in the order they were raised) are written as warn_order[p, m]: the 1-based position of (p, m)'s warning in
+    that order, 0 for none -- the same shape on every run, never empty.  When the whole result would exceed `limit_bytes`,
+    the same arrays are written for a fixed, seeded sample of the partitions (sorted ids in sample_partitions.npy; out_off
+    is then the offsets of the sample's lists).  Returns what was written."""
+    import numpy as np
+    P, M = res.P, res.M
+    n = res.n_warnings
+    total = int(res.out_off[P * M]) if P * M else 0
+    kind = res.out_kind[:P * M].reshape(P, M)
+    off = res.out_off[:P * M + 1]
+    nodes = res.out_nodes[:total]
+    warn_order = np.zeros(P * M, dtype=np.int64)
+    warn_order[res.warn_part[:n].astype(np.int64) * M + res.warn_state[:n]] = np.arange(1, n + 1)
+    warn_order = warn_order.reshape(P, M)
+
+    def as_float(a):                                # (integer arrays: float32 holds every integer below 2^24 exactly)
+        a = np.asarray(a)
+        exact32 = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24)
+        return a.astype(np.float32 if exact32 else np.float64)
+    sample = None
+    whole = sum(as_float(a).nbytes for a in (off, nodes, kind, warn_order))
+    if whole > limit_bytes and P > 0:
+        # a fixed number of partitions, chosen by a fixed seed: the same ids for the same problem shape on every run
+        k = max(1, min(P, int(limit_bytes * 0.9 / (whole / P + 8))))          # (+ its entry in sample_partitions)
+        sample = np.sort(np.random.default_rng(seed).choice(P, size=k, replace=False)).astype(np.int64)
+        lo, hi = off[sample * M], off[sample * M + M]                     # each sampled partition's lists are contiguous
+        counts = np.diff(off).reshape(P, M)[sample]
+        nodes = np.concatenate([nodes[a:b] for a, b in zip(lo.tolist(), hi.tolist())])
+        off = np.concatenate([[0], np.cumsum(counts.reshape(-1))])
+        kind = kind[sample]
+        warn_order = warn_order[sample]
+    arrays = {"out_kind": kind, "out_off": off, "out_nodes": nodes, "warn_order": warn_order,
+              "summary": np.asarray([res.iterations, int(res.converged), n], dtype=np.int64)}
+    if sample is not None:
+        arrays["sample_partitions"] = sample
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = as_float(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return {"dir": os.path.abspath(out_dir), "arrays": written, "bytes": sum(as_float(a).nbytes for a in arrays.values()),
+            "partitions": P if sample is None else int(sample.size), "sampled": sample is not None}
 
 
 def self_launch(args):
@@ -527,8 +581,8 @@ def main():
     ap.add_argument("--replicas-per-gpu", default="", help="R[,R...]: ONLY the replicas_on_one_gpu block -- R contexts planning at once on one "
                     "GPU (config 5 by default with --config 5, else config 3): aggregate assignments/s, slowest plan, host cores; never the headline")
     ap.add_argument("--replica-budget-s", type=int, default=240, help="time budget of the replicas block (an R predicted to overrun it is skipped)")
-    ap.add_argument("--hw-queues", type=int, default=32, help="GPU_MAX_HW_QUEUES for the replicas block (the runtime's default maps all streams "
-                    "of a process onto 4 hardware queues)")
+    ap.add_argument("--hw-queues", type=int, default=MAX_HW_QUEUES, help="GPU_MAX_HW_QUEUES for the replicas block, at most %d (the "
+                    "GPU is shared with other work)" % MAX_HW_QUEUES)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--replicas-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--problem-npz", default="", help=argparse.SUPPRESS)
@@ -540,6 +594,9 @@ def main():
                     "has taken this long: the headline, roofline, cpu_baseline and other_configs always run")
     ap.add_argument("--no-replicas", action="store_true", help="skip the replicas_on_one_gpu blocks of the default line")
     ap.add_argument("--no-rccl-one-rank", action="store_true", help="skip the one-rank RCCL leg (ncclAllReduce / ncclAllGather timed on this GPU)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the result of the last one (the arrays "
+                    "PlanNextMap hands its caller) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (a fixed seeded sample of "
+                    "the partitions beyond that): two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
 
     if args.replicas_worker:
@@ -634,6 +691,7 @@ def main():
     res = pl.download()                             # (every rank: the sharded leg compares with it)
     download_s = time.perf_counter() - t1
     digest_all = res.digest()
+    dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     replicas_ok = None
     if dist is not None:
         box_ = [None] * world
@@ -847,6 +905,8 @@ def main():
                                                   if xfer and "pageable" in xfer else None)}),
             "result_sha256": digest,
         }
+        if dumped:
+            out["outputs_dumped"] = dumped
         ref = os.path.join(ROOT, "tests", "golden", "config_digests.json")
         if os.path.exists(ref) and headline_shape:
             with open(ref) as f:

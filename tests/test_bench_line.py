@@ -189,3 +189,79 @@ def test_bench_without_the_periodic_form_is_not_a_headline():
     gr = got[False]["general_regime"]
     assert len(gr) == 2 and all("error" not in w and w["headline"] is False and w["ms_per_step"] > 0 for w in gr), gr
     assert "general_regime" not in got[True]
+
+
+def _digest_of_dump(d):
+    """abi.FlatResult.digest() rebuilt from the arrays of `bench.py --dump-outputs` (written as floats, exact)."""
+    import hashlib
+    import numpy as np
+    a = {n: np.load(os.path.join(d, n + ".npy")) for n in ("out_kind", "out_off", "out_nodes", "warn_order", "summary")}
+    order = a["warn_order"].reshape(-1).astype(np.int64)          # the warning list: slots by their 1-based position in it
+    slots = np.flatnonzero(order)
+    slots = slots[np.argsort(order[slots])]
+    M = a["out_kind"].shape[1]
+    h = hashlib.sha256()
+    h.update(a["out_kind"].reshape(-1).astype(np.uint8).tobytes())
+    h.update(a["out_off"].astype(np.int32).tobytes())
+    h.update(a["out_nodes"].astype(np.int32).tobytes())
+    h.update(a["summary"].astype(np.int64).tobytes())
+    h.update((slots // M).astype(np.int32).tobytes())
+    h.update((slots % M).astype(np.int32).tobytes())
+    return h.hexdigest()
+
+
+def test_dump_outputs_are_the_timed_result(tmp_path):
+    """bench.py --dump-outputs DIR on the CPU rehearsal: the arrays written after the timed steps are float32 / float64, none
+    of them empty, within 64 MB, and ARE the result the line's result_sha256 describes (the digest rebuilt from them)."""
+    import subprocess
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_simt_emulated import build_emu
+    env = dict(os.environ, BLANCE_BENCH_REHEARSAL=build_emu())
+    dump = str(tmp_path / "out")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--parts", "600", "--nodes", "256", "--steps", "2",
+                          "--warmup", "1", "--no-sharded", "--no-cpu-baseline", "--no-extra", "--dump-outputs", dump],
+                         env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout + out.stderr
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["outputs_dumped"]["sampled"] is False
+    files = sorted(os.listdir(dump))
+    assert files and all(f.endswith(".npy") for f in files)
+    arrays = [np.load(os.path.join(dump, f)) for f in files]
+    assert all(a.dtype in (np.float32, np.float64) and a.size > 0 for a in arrays)
+    assert sum(a.nbytes for a in arrays) <= 64 << 20
+    assert _digest_of_dump(dump) == d["result_sha256"]
+
+
+def test_dump_outputs_sample_is_fixed_and_exact(tmp_path):
+    """Above the size limit bench.dump_outputs writes a seeded sample of the partitions: the same ids on every run, under the
+    limit, and every sampled partition's lists and warnings exactly as in the whole result.  A result with warnings (a
+    replica that one node cannot hold) is rebuilt exactly from its whole dump."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from blance_amd import synth
+    from oracle import loader
+    res = loader.plan(synth.config_flat(3, P=5000, N=256))
+    whole, a, b = (str(tmp_path / n) for n in ("whole", "a", "b"))
+    assert bench.dump_outputs(res, whole)["sampled"] is False
+    for d in (a, b):
+        info = bench.dump_outputs(res, d, limit_bytes=20000)
+        assert info["sampled"] is True and info["bytes"] <= 20000 and 0 < info["partitions"] < 5000
+    load = lambda d, n: np.load(os.path.join(d, n + ".npy"))            # noqa: E731
+    for n in ("sample_partitions", "out_kind", "out_off", "out_nodes", "warn_order"):
+        assert np.array_equal(load(a, n), load(b, n)), n
+    ids = load(a, "sample_partitions").astype(np.int64)
+    M = res.M
+    off, nodes, soff, snodes = load(whole, "out_off"), load(whole, "out_nodes"), load(a, "out_off"), load(a, "out_nodes")
+    assert np.array_equal(load(a, "out_kind"), load(whole, "out_kind")[ids])
+    assert np.array_equal(load(a, "warn_order"), load(whole, "warn_order")[ids])
+    for j, p in enumerate(ids.tolist()):
+        for m in range(M):
+            want = nodes[int(off[p * M + m]):int(off[p * M + m + 1])]
+            assert np.array_equal(snodes[int(soff[j * M + m]):int(soff[j * M + m + 1])], want)
+    warned = loader.plan(synth.config_flat(2, P=64, N=1))
+    assert warned.n_warnings > 0
+    d = str(tmp_path / "warned")
+    bench.dump_outputs(warned, d)
+    assert _digest_of_dump(d) == warned.digest()
