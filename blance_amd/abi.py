@@ -245,6 +245,12 @@ class FlatResult:
         return h.hexdigest()
 
 
+class BatchInfo(C.Structure):
+    """blance_batch_info of include/blance_hip.h (blance_plan_batch)."""
+    _fields_ = [("n_batched", C.c_int32), ("n_fallback", C.c_int32), ("kernel_launches", C.c_int64),
+                ("steps_total", C.c_int64), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 

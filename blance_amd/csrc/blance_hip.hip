@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <map>
 #include <mutex>
 #include <new>
@@ -25,6 +26,7 @@
 #include "tu_tree.hip"
 #include "tu_queue.hip"
 #include "tu_chain.hip"
+#include "tu_batch.hip"
 #endif
 
 
@@ -297,6 +299,7 @@ struct blance_ctx {
     DevBuf f_tot, f_g, f_top_g, f_top_n, f_row_count, f_m, f_moff, f_keys_a, f_keys_b, f_vals_a, f_vals_b, f_hist, f_comp;
     int64_t steps_batched = 0;
     int64_t out_capacity = 0;
+    DevBuf batch_in, batch_sc, batch_out;   // blance_plan_batch: descriptors + packed problems, working state, results
 
     // device: problem
     DevBuf node_removed, node_added, node_weight, node_has_weight, alive, zeros_nx, node_leaf_pos;
@@ -342,7 +345,7 @@ struct blance_ctx {
                           &ev_key, &ev_oi, &ev_leaf, &ev_w, &ev_perm, &ev_off, &ev_counts, &fl_iota, &fl_zero,
                           &fl_one, &fl_reglo, &fl_reghi, &f_tot, &f_g,
                           &f_top_g, &f_top_n, &f_row_count, &f_m, &f_moff, &f_keys_a, &f_keys_b, &f_vals_a,
-                          &f_vals_b, &f_hist, &f_comp};
+                          &f_vals_b, &f_hist, &f_comp, &batch_in, &batch_sc, &batch_out};
         for (DevBuf* b : more) b->release();
     }
 };
@@ -2750,3 +2753,279 @@ extern "C" int blance_plan(blance_ctx* c, const blance_problem* pb, blance_resul
     });
 }
 
+// ============================================================================
+// blance_plan_batch: many small problems, one upload, one launch per size class (k_plan_batch, one workgroup per
+// problem), one download.  Problems outside the batched envelope go through upload / plan / download one by one.
+// ============================================================================
+namespace {
+struct BatchItem {
+    int idx;            // index in the caller's arrays
+    int threads;        // 64 / 256: k_plan_batch's size class
+    BatchDesc d;
+    int64_t in_words, sc_words, out_words;
+};
+
+int batch_list_len(const blance_problem* pb) {
+    int L = 1;
+    const int M = pb->n_states;
+    for (int m = 0; m < M; m++) if (pb->state_constraints[m] > L) L = pb->state_constraints[m];
+    const int64_t PM = (int64_t)pb->n_parts * M;
+    for (int64_t i = 0; i < PM; i++) {
+        const int a = pb->assign_off[i + 1] - pb->assign_off[i], b = pb->prev_off[i + 1] - pb->prev_off[i];
+        if (a > L) L = a;
+        if (b > L) L = b;
+    }
+    return L;
+}
+
+// the word layout of one problem's three slices (BatchDesc); false when the problem is outside the batched envelope
+bool batch_layout(const blance_problem* pb, BatchItem& it) {
+    const int N = pb->n_nodes, NX = pb->n_nodes_ext, M = pb->n_states, P = pb->n_parts;
+    if (NX > kBatchMaxNX || P > kBatchMaxP || M > kMaxStates) return false;
+    const int L = batch_list_len(pb);
+    if (L > kBatchMaxL) return false;
+    BatchDesc& d = it.d;
+    memset(&d, 0, sizeof d);
+    const int PM = P * M;
+    d.N = N; d.NX = NX; d.M = M; d.P = P; d.L = L;
+    d.n_loads = pb->n_loads; d.n_rules = pb->hierarchy_rules_nil ? 0 : pb->n_rules;
+    d.max_iterations = pb->max_iterations; d.n_prev = pb->n_prev;
+    for (int p = 0; p < P; p++) if (!pb->part_in_prev[p]) d.fresh++;
+    for (int n = 0; n < NX; n++) {
+        if (pb->node_removed[n]) d.any_removed = 1;
+        if (n < N && !pb->node_removed[n]) d.n_alive++;
+    }
+    d.weights_nil = pb->partition_weights_nil; d.add_nil = pb->nodes_to_add_nil; d.hier_nil = pb->hierarchy_rules_nil;
+    d.booster_kind = pb->booster_kind; d.top_state = pb->top_state;
+    d.cap = (int32_t)blance_result_capacity(pb);
+    int passes = 0;
+    for (int m = 0; m < M; m++) if (pb->state_constraints[m] > 0) passes++;
+    d.wcap = P * passes;
+    int32_t o = 0;
+    auto take = [&](int32_t& field, int64_t words) { field = o; o += (int32_t)((words + 3) & ~3ll); };
+    take(d.i_state, 4 * M); take(d.i_rule_off, M + 1); take(d.i_node, 4 * (int64_t)NX); take(d.i_order, P);
+    take(d.i_part, 2 * (int64_t)P); take(d.i_alist, (int64_t)PM * L); take(d.i_ahdr, PM); take(d.i_plist, (int64_t)PM * L);
+    take(d.i_phdr, PM); take(d.i_loads, 4 * (int64_t)pb->n_loads); take(d.i_anch, 4 * (int64_t)d.n_rules * (NX + 1));
+    it.in_words = o;
+    o = 0;
+    take(d.s_live, (int64_t)PM * L); take(d.s_lhdr, PM); take(d.s_prv, (int64_t)PM * L); take(d.s_phdr, PM);
+    take(d.s_pflag, P); take(d.s_order, P); take(d.s_cat, P); take(d.s_ntn, (int64_t)(NX + 1) * (N > 0 ? N : 1));
+    it.sc_words = o;
+    o = kBatchHdr;
+    take(d.o_off, PM + 1); take(d.o_kind, PM); take(d.o_nodes, d.cap); take(d.o_wp, d.wcap); take(d.o_ws, d.wcap);
+    it.out_words = o;
+    it.threads = NX <= 64 ? 64 : 256;
+    return true;
+}
+
+// the problem's input slice (BatchDesc) at dst
+void batch_pack(const blance_problem* pb, const BatchDesc& d, int32_t* dst) {
+    const int NX = d.NX, M = d.M, P = d.P, L = d.L, PM = P * M;
+    for (int m = 0; m < M; m++) {
+        int32_t* s = dst + d.i_state + 4 * m;
+        s[0] = pb->state_priority[m]; s[1] = pb->state_constraints[m];
+        s[2] = pb->state_stickiness[m]; s[3] = pb->state_has_stickiness[m];
+    }
+    for (int m = 0; m <= M; m++) dst[d.i_rule_off + m] = d.hier_nil ? 0 : pb->rule_off[m];
+    for (int n = 0; n < NX; n++) {
+        int32_t* s = dst + d.i_node + 4 * n;
+        s[0] = pb->node_weight[n];
+        s[1] = (pb->node_removed[n] ? 1 : 0) | (pb->node_added[n] ? 2 : 0) | (pb->node_has_weight[n] ? 4 : 0);
+        s[2] = pb->node_leaf_pos[n];
+        s[3] = 0;
+    }
+    memcpy(dst + d.i_order, pb->part_order, sizeof(int32_t) * (size_t)P);
+    for (int p = 0; p < P; p++) {
+        dst[d.i_part + 2 * p] = pb->part_weight[p];
+        dst[d.i_part + 2 * p + 1] = (pb->part_has_weight[p] ? 1 : 0) | (pb->part_in_prev[p] ? 2 : 0) | (pb->part_prev_never_equal[p] ? 4 : 0);
+    }
+    for (int idx = 0; idx < PM; idx++) {
+        const int a0 = pb->assign_off[idx], a1 = pb->assign_off[idx + 1], b0 = pb->prev_off[idx], b1 = pb->prev_off[idx + 1];
+        memcpy(dst + d.i_alist + (int64_t)idx * L, pb->assign_nodes + a0, sizeof(int32_t) * (size_t)(a1 - a0));
+        dst[d.i_ahdr + idx] = (a1 - a0) | (pb->assign_kind[idx] << 16);
+        memcpy(dst + d.i_plist + (int64_t)idx * L, pb->prev_nodes + b0, sizeof(int32_t) * (size_t)(b1 - b0));
+        dst[d.i_phdr + idx] = (b1 - b0) | (pb->prev_kind[idx] << 16);
+    }
+    for (int i = 0; i < d.n_loads; i++) {
+        int32_t* s = dst + d.i_loads + 4 * i;
+        s[0] = pb->load_state[i]; s[1] = pb->load_node[i]; s[2] = pb->load_weight[i]; s[3] = pb->load_first_sweep_only[i];
+    }
+    // leaf-interval table of every (rule, anchor), anchor NX = the "" vertex: plan.go:723-734, :755-774 (as blance_upload)
+    AnchorSet* tab = (AnchorSet*)(dst + d.i_anch);
+    for (int r = 0; r < d.n_rules; r++)
+        for (int a = 0; a <= NX; a++) {
+            const int v = a == NX ? pb->vertex_empty : a;
+            int vi = v, ve = v;
+            for (int l = pb->rule_inc[r]; l > 0; l--) vi = pb->vertex_parent[vi];
+            for (int l = pb->rule_exc[r]; l > 0; l--) ve = pb->vertex_parent[ve];
+            AnchorSet& s = tab[(size_t)r * (NX + 1) + a];
+            s.alo = pb->vertex_leaf_lo[vi]; s.ahi = pb->vertex_leaf_hi[vi];
+            s.blo = pb->vertex_leaf_lo[ve]; s.bhi = pb->vertex_leaf_hi[ve];
+        }
+}
+
+// every check blance_plan would make before it writes a result, and the result buffers' capacities
+int batch_check(const blance_problem* pb, const blance_result* r) {
+    int st = blance_validate(pb);
+    if (st) return st;
+    if (!r || !r->out_off || !r->out_nodes || !r->out_kind || !r->warn_part || !r->warn_state)
+        return fail(BLANCE_ERR_BAD_ARG, "null result buffers");
+    if (pb->max_iterations > 0) {
+        int passes = 0;
+        for (int m = 0; m < pb->n_states; m++) if (pb->state_constraints[m] > 0) passes++;
+        if (r->out_capacity < blance_result_capacity(pb)) return fail(BLANCE_ERR_CAPACITY, "out_capacity too small");
+        if (r->warn_capacity < (int64_t)pb->n_parts * passes) return fail(BLANCE_ERR_CAPACITY, "warn_capacity too small");
+    }
+    return BLANCE_OK;
+}
+}  // namespace
+
+static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                             blance_batch_info* info) {
+    const auto t_start = std::chrono::steady_clock::now();
+    if (c->comm.n_ranks > 1 || c->rccl_comm) return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_batch on a context with a communicator");
+    for (int i = 0; i < n; i++) {
+        const int st = batch_check(pbs[i], res[i]);
+        if (st) {
+            const std::string why = g_last_error;
+            return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
+        }
+    }
+    HIPTRY(hipSetDevice(c->device));
+    c->uploaded = false;                                 // the context holds no problem after a batch
+    c->planned = false;
+    std::vector<BatchItem> items;
+    std::vector<int> fallback;
+    for (int cls : {64, 256})
+        for (int i = 0; i < n; i++) {
+            BatchItem it;
+            it.idx = i;
+            const bool in_env = batch_layout(pbs[i], it);
+            if (!in_env && cls == 64) fallback.push_back(i);
+            if (in_env && it.threads == cls) items.push_back(it);
+        }
+    const int nb = (int)items.size();
+    int64_t launches = 0, steps = 0;
+    double device_ms = 0.0;
+    if (nb > 0) {
+        int64_t in_words = 0, sc_words = 0, out_words = 0;
+        int n64 = 0;
+        size_t lds64 = 0, lds256 = 0;
+        for (BatchItem& it : items) {
+            it.d.in_base = in_words; it.d.sc_base = sc_words; it.d.out_base = out_words;
+            in_words += it.in_words; sc_words += it.sc_words; out_words += it.out_words;
+            const size_t lds = plan_batch_lds(it.threads, it.d.M, it.d.NX);
+            if (it.threads == 64) { n64++; if (lds > lds64) lds64 = lds; }
+            else if (lds > lds256) lds256 = lds;
+        }
+        const size_t desc_bytes = ((sizeof(BatchDesc) * (size_t)nb) + 255) & ~(size_t)255;
+        const size_t in_bytes = desc_bytes + sizeof(int32_t) * (size_t)in_words, out_bytes = sizeof(int32_t) * (size_t)out_words;
+        struct Pinned { void* p = nullptr; ~Pinned() { pin_free(p); } } host;
+        host.p = pin_alloc(in_bytes + out_bytes);
+        if (!host.p) return fail(BLANCE_ERR_DEVICE, "page-locked staging block: hipHostMalloc failed");
+        char* h_in = (char*)host.p;
+        int32_t* h_out = (int32_t*)(h_in + in_bytes);
+        for (int i = 0; i < nb; i++) {
+            memcpy(h_in + sizeof(BatchDesc) * i, &items[i].d, sizeof(BatchDesc));
+            batch_pack(pbs[items[i].idx], items[i].d, (int32_t*)(h_in + desc_bytes) + items[i].d.in_base);
+        }
+        if (c->batch_in.reserve(in_bytes) || c->batch_sc.reserve(sizeof(int32_t) * (size_t)sc_words + 256) ||
+            c->batch_out.reserve(out_bytes))
+            return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        HIPTRY(hipMemcpyAsync(c->batch_in.p, h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
+        BatchParams q;
+        q.desc = c->batch_in.as<BatchDesc>();
+        q.in = (const int32_t*)(c->batch_in.as<char>() + desc_bytes);
+        q.sc = c->batch_sc.as<int32_t>();
+        q.out = c->batch_out.as<int32_t>();
+        HIPTRY(hipEventRecord(c->ev0, c->stream));
+        q.first = 0;
+        if (n64 > 0) { launch_plan_batch(c->stream, q, 64, n64, lds64); launches++; }
+        q.first = n64;
+        if (nb > n64) { launch_plan_batch(c->stream, q, 256, nb - n64, lds256); launches++; }
+        HIPTRY(hipGetLastError());
+        HIPTRY(hipEventRecord(c->ev1, c->stream));
+        HIPTRY(hipMemcpyAsync(h_out, c->batch_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPTRY(stream_sync(c));
+        float ms = 0.f;
+        HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        device_ms = ms;
+        // a problem the kernel could not finish exactly (an interval budget of the hierarchy fold) goes the single path
+        for (const BatchItem& it : items) {
+            const int32_t* o = h_out + it.d.out_base;
+            if (o[5] != 1 || o[4] != 0) fallback.push_back(it.idx);
+        }
+        const double total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        for (const BatchItem& it : items) {
+            const BatchDesc& d = it.d;
+            const int32_t* o = h_out + d.out_base;
+            if (o[5] != 1 || o[4] != 0) continue;
+            blance_result* r = res[it.idx];
+            const int PM = d.P * d.M;
+            const int iters = o[0];
+            memcpy(r->out_off, o + d.o_off, sizeof(int32_t) * ((size_t)PM + 1));
+            for (int i = 0; i < PM; i++) r->out_kind[i] = (uint8_t)o[d.o_kind + i];
+            if (o[3] > 0) memcpy(r->out_nodes, o + d.o_nodes, sizeof(int32_t) * (size_t)o[3]);
+            if (o[2] > 0) {
+                memcpy(r->warn_part, o + d.o_wp, sizeof(int32_t) * (size_t)o[2]);
+                memcpy(r->warn_state, o + d.o_ws, sizeof(int32_t) * (size_t)o[2]);
+            }
+            int passes = 0;
+            for (int m = 0; m < d.M; m++) if (pbs[it.idx]->state_constraints[m] > 0) passes++;
+            r->n_warnings = o[2];
+            r->iterations = iters;
+            r->converged = o[1];
+            r->device_ms = device_ms;
+            r->total_ms = total_ms;
+            r->steps_total = (int64_t)iters * d.P * passes;
+            r->steps_sequential = r->steps_batched = r->kernel_launches = 0;
+            r->pass_kernel_ms = r->flat_pass_ms = r->blank_pass_ms = r->stay_pass_ms = 0.0;
+            r->pass_kernel_launches = r->flat_passes = r->blank_pass_launches = r->stay_pass_launches = r->host_syncs = 0;
+            steps += r->steps_total;
+        }
+    }
+    const int n_fallback = (int)fallback.size();
+    for (int i : fallback) {                             // the single-problem path: blance_plan
+        hipEvent_t t0, t1;
+        HIPTRY(hipEventCreate(&t0));
+        HIPTRY(hipEventCreate(&t1));
+        struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{t0, t1};
+        HIPTRY(hipEventRecord(t0, c->stream));
+        int st = upload_locked(c, pbs[i]);
+        if (!st) st = settle(c, plan_locked(c, res[i]));
+        if (!st) st = settle(c, download_locked(c, res[i]));
+        c->uploaded = c->planned = false;
+        if (st) {
+            const std::string why = g_last_error;
+            return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
+        }
+        (void)hipEventRecord(t1, c->stream);
+        (void)hipEventSynchronize(t1);
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        res[i]->total_ms = ms;
+        launches += res[i]->kernel_launches;
+        steps += res[i]->steps_total;
+        device_ms += res[i]->device_ms;
+    }
+    if (info) {
+        info->n_batched = nb - (n_fallback - (n - nb));
+        info->n_fallback = n_fallback;
+        info->kernel_launches = launches;
+        info->steps_total = steps;
+        info->device_ms = device_ms;
+        info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return BLANCE_OK;
+}
+
+extern "C" int blance_plan_batch(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                                 blance_batch_info* info) {
+    return guarded([&]() -> int {
+    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
+    if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
+    std::lock_guard<std::mutex> g(c->mu);
+    rb_discard(c);
+    return settle(c, plan_batch_locked(c, n, pbs, res, info));
+    });
+}

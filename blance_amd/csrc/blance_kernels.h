@@ -174,4 +174,39 @@ struct FlatParams {
                                    // one radix pass less; any order-preserving injection gives the same sorted values
 };
 
+// Many small problems in one launch, one workgroup each: DESIGN.md §4.8 "k_plan_batch".
+constexpr int kBatchMaxNX = 256;       // node names of a batched problem (one thread per node, 64 or 256 threads)
+constexpr int kBatchMaxP = 16384;      // partitions
+constexpr int kBatchMaxL = 8;          // longest state list (constraints included)
+constexpr int kBatchHdr = 8;           // output header words: iterations, converged, warnings, list entries, error, done
+
+// One problem of a batch.  Its arrays are int32 words at fixed offsets inside three slices: input (packed by the host),
+// scratch (the kernel's working state) and output (what the host unpacks into the caller's blance_result).
+struct BatchDesc {
+    int64_t in_base, sc_base, out_base;   // first word of the problem's slice in each block
+    int32_t N, NX, M, P, L;
+    int32_t n_loads, n_rules, max_iterations, n_prev, fresh, n_alive, any_removed;
+    int32_t weights_nil, add_nil, hier_nil, booster_kind, top_state;
+    int32_t cap, wcap;                    // list entries / warnings the output slice holds
+    // input slice: state words [M][4] (priority, constraints, stickiness, has stickiness); rule_off [M + 1];
+    // node words [NX][4] (weight, removed | added << 1 | has weight << 2, leaf position, 0); part_order [P];
+    // partition words [P][2] (weight, has weight | in prevMap << 1 | never equal << 2); assign lists [P*M][L] and
+    // headers [P*M] (length | kind << 16); the same for prevMap; loads [n_loads][4] (state, node, weight, first sweep
+    // only); AnchorSet [n_rules][NX + 1]
+    int32_t i_state, i_rule_off, i_node, i_order, i_part, i_alist, i_ahdr, i_plist, i_phdr, i_loads, i_anch;
+    // scratch slice: live lists [P*M][L] + headers, prevMap lists [P*M][L] + headers, partition flags [P] (in prevMap |
+    // never equal << 1), pass order [P], category by position [P], nodeToNodeCounts [NX + 1][max(N, 1)]
+    int32_t s_live, s_lhdr, s_prv, s_phdr, s_pflag, s_order, s_cat, s_ntn;
+    // output slice: header [kBatchHdr], out_off [P*M + 1], out_kind [P*M], out_nodes [cap], warn_part [wcap], warn_state [wcap]
+    int32_t o_off, o_kind, o_nodes, o_wp, o_ws;
+};
+
+struct BatchParams {
+    const BatchDesc* desc;
+    const int32_t* in;
+    int32_t* sc;
+    int32_t* out;
+    int32_t first;                        // desc index of workgroup 0 of this launch
+};
+
 }  // namespace blance

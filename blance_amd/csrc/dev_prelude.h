@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include "../../include/blance_hip.h"
+#include "../../include/blance_batch.h"
 #include "blance_kernels.h"
 #include "dev_common.h"
 
@@ -46,4 +47,7 @@ void launch_chain_blank(hipStream_t stream, const ChainParams& q, int max_size);
 bool launch_chain_planes(hipStream_t stream, const ChainParams& q, int max_size);
 // k_stay_by_top (tu_chain.hip): a chain pass of stays, one thread per top priority node; false: shape outside it
 bool launch_stay_by_top(hipStream_t stream, const StayParams& q, int n_wgs, int max_size);
+// k_plan_batch (tu_batch.hip): n problems of one size class, one workgroup of `threads` (64 or 256) each
+void launch_plan_batch(hipStream_t stream, const BatchParams& q, int threads, int n, size_t lds);
+size_t plan_batch_lds(int threads, int M, int NX);   // dynamic LDS of one such workgroup
 }  // namespace blance

@@ -1,0 +1,18 @@
+// Translation unit of k_plan_batch: many small problems in one launch, and its launch wrapper.
+#include "dev_prelude.h"
+#include "k_plan_batch.h"
+
+namespace blance {
+
+size_t plan_batch_lds(int threads, int M, int NX) {
+    const size_t words = (size_t)(M + 1) * NX > (size_t)threads ? (size_t)(M + 1) * NX : (size_t)threads;
+    return sizeof(RedSlot) * 2 * (threads / 64) + sizeof(int) * (32 + kMaxStates * kBatchMaxL + kMaxStates) + sizeof(int) * words;
+}
+
+void launch_plan_batch(hipStream_t stream, const BatchParams& q, int threads, int n, size_t lds) {
+    if (n <= 0) return;
+    if (threads == 64) BLANCE_LAUNCH(k_plan_batch<64>, n, 64, lds, stream, q);
+    else BLANCE_LAUNCH(k_plan_batch<256>, n, 256, lds, stream, q);
+}
+
+}  // namespace blance

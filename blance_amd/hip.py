@@ -78,6 +78,11 @@ def load_library(path=None):
     lib.blance_host_free.argtypes = [C.c_void_p]
     lib.blance_host_trim.restype = None
     lib.blance_host_trim.argtypes = []
+    # additive to ABI 6 (not in EXPORTS): a library without it still loads, Planner.plan_batch then refuses
+    if hasattr(lib, "blance_plan_batch"):
+        lib.blance_plan_batch.restype = C.c_int
+        lib.blance_plan_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
+                                          C.POINTER(C.POINTER(abi.Result)), C.POINTER(abi.BatchInfo)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
@@ -255,6 +260,21 @@ class Planner:
         res = abi.FlatResult(fp)
         self._check(self.lib.blance_plan(self._h, C.byref(fp.as_struct()), C.byref(res.struct)))
         return res
+
+    def plan_batch(self, fps):
+        """blance_plan_batch(): many independent problems in one call.  Returns ([FlatResult], info dict) with
+        n_batched / n_fallback / kernel_launches / steps_total / device_ms / total_ms."""
+        if not hasattr(self.lib, "blance_plan_batch"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch (build the current sources)")
+        fps = list(fps)
+        results = [abi.FlatResult(fp) for fp in fps]
+        structs = [fp.as_struct() for fp in fps]               # (kept alive for the call)
+        n = len(fps)
+        pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
+        rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
+        info = abi.BatchInfo()
+        self._check(self.lib.blance_plan_batch(self._h, n, pbs, rss, C.byref(info)))
+        return results, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
     def plan_stats(self, n_states):
         """Per-state load statistics of the map the last plan produced (blance_plan_stats_get):

@@ -73,20 +73,21 @@ def default_planner():
     return _planner
 
 
-def PlanNextMapEx(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model, options=None,
-                  booster=None, planner=None):
-    """api.go:147-157.  Returns (nextMap, warnings); mutates prevMap and
-    partitionsToAssign the way planNextMapEx does (plan.go:49-52)."""
+def _build_call(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model, options=None, booster=None):
+    """The flat problem of one PlanNextMapEx call (refuses what the device cannot run)."""
     options = options or PlanNextMapOptions()
     if CustomNodeSorter is not None:
         raise problem.Unsupported("CustomNodeSorter is not the default sorter (plan.go:580)")
     if booster is not None and booster != "cbgt":
         raise problem.Unsupported("NodeScoreBooster is an arbitrary callback (plan.go:693)")
-    fp = problem.build_problem(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model,
-                               options.ModelStateConstraints, options.PartitionWeights,
-                               options.StateStickiness, options.NodeWeights, options.NodeHierarchy,
-                               options.HierarchyRules, booster, max_iterations=MaxIterationsPerPlan)
-    res = (planner or default_planner()).plan(fp)
+    return problem.build_problem(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model,
+                                 options.ModelStateConstraints, options.PartitionWeights,
+                                 options.StateStickiness, options.NodeWeights, options.NodeHierarchy,
+                                 options.HierarchyRules, booster, max_iterations=MaxIterationsPerPlan)
+
+
+def _finish_call(fp, res, prevMap, partitionsToAssign):
+    """(nextMap, warnings) of one call from its result, with the caller-visible write-back of plan.go:49-52."""
     if res.iterations == 0:                     # MaxIterationsPerPlan <= 0: (nil, nil)
         return None, None
     flat, warnings = problem.decode_result(fp, res)
@@ -105,6 +106,28 @@ def PlanNextMapEx(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToA
             prevMap[name] = stored
             partitionsToAssign[name] = stored
     return nextMap, warnings
+
+
+def PlanNextMapEx(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model, options=None,
+                  booster=None, planner=None):
+    """api.go:147-157.  Returns (nextMap, warnings); mutates prevMap and
+    partitionsToAssign the way planNextMapEx does (plan.go:49-52)."""
+    fp = _build_call(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model, options, booster)
+    res = (planner or default_planner()).plan(fp)
+    return _finish_call(fp, res, prevMap, partitionsToAssign)
+
+
+def PlanNextMapExBatch(calls, planner=None):
+    """Many independent PlanNextMapEx calls planned by ONE blance_plan_batch (one upload, one launch per size class, one
+    download; problems outside the batched envelope go the single-problem path inside the same call).  `calls` is a list of
+    argument sets of PlanNextMapEx: tuples (prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model
+    [, options [, booster]]) or dicts with those names.  Returns [(nextMap, warnings)] in call order and performs every
+    call's write-back into its own prevMap / partitionsToAssign exactly as PlanNextMapEx does."""
+    names = ("prevMap", "partitionsToAssign", "nodesAll", "nodesToRemove", "nodesToAdd", "model", "options", "booster")
+    args = [dict(c) if isinstance(c, dict) else dict(zip(names, c)) for c in calls]
+    fps = [_build_call(**a) for a in args]
+    results, _ = (planner or default_planner()).plan_batch(fps)
+    return [_finish_call(fp, res, a["prevMap"], a["partitionsToAssign"]) for fp, res, a in zip(fps, results, args)]
 
 
 def PlanNextMap(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model,

@@ -341,3 +341,55 @@ def config3_rebalance_flat(fp, res, every=10, which=3):
     rm[np.arange(N) % every == which] = 1
     fp2.set("node_removed", rm)
     return fp2
+
+
+def cbgt_case(seed, P_range=(64, 2048), N_range=(8, 256), hierarchy=None, rebalance=None):
+    """One PlanNextMapEx call of the shape cbgt makes per index definition (INTEGRATION.md "Batching"): tens to a few
+    thousand partitions over tens to a few hundred nodes, primary + 1-2 replicas, the cbgt booster with a few node weights.
+    hierarchy: replicas outside the primary's server group (includeLevel 2, excludeLevel 1); rebalance: an existing map
+    (a round robin over the old nodes) with a tenth of the nodes removed and a tenth added.  None: decided by the seed.
+    Returns the keyword arguments of problem.build_problem."""
+    import random
+    rng = random.Random(seed)
+    P = rng.randint(*P_range)
+    N = rng.randint(*N_range)
+    R = rng.choice([1, 2])
+    if hierarchy is None:
+        hierarchy = rng.random() < 0.5
+    if rebalance is None:
+        rebalance = rng.random() < 0.5
+    model = {"primary": {"priority": 0, "constraints": 1}, "replica": {"priority": 1, "constraints": R}}
+    nodes = _node_names(N, 4)
+    parts = ["%d" % i for i in range(P)]
+    node_weights = None
+    if rng.random() < 0.5:
+        node_weights = {n: rng.choice([1, 1, 1, 2, -1]) for n in nodes if rng.random() < 0.3}
+    node_hierarchy = rules = None
+    if hierarchy:
+        groups = max(2, N // rng.choice([4, 8, 16]))
+        node_hierarchy = {n: "sg%03d" % (i % groups) for i, n in enumerate(nodes)}
+        rules = {"replica": [{"includeLevel": 2, "excludeLevel": 1}]}
+    to_remove, to_add, prev = [], list(nodes), {}
+    if rebalance and N >= 4:
+        order = nodes[:]
+        rng.shuffle(order)
+        k = max(1, N // 10)
+        to_add = sorted(order[:k])
+        to_remove = sorted(order[k:2 * k])
+        old = [n for n in nodes if n not in set(to_add)]
+        for i, p in enumerate(parts):
+            lst = [old[(i + j) % len(old)] for j in range(min(1 + R, len(old)))]
+            nbs = {"primary": lst[:1]}
+            if lst[1:]:
+                nbs["replica"] = lst[1:]
+            prev[p] = {"name": p, "nodesByState": nbs}
+    assign = prev if prev else {p: {"name": p, "nodesByState": {}} for p in parts}
+    return dict(prev_map=prev, partitions_to_assign=assign, nodes_all=nodes, nodes_to_remove=to_remove,
+                nodes_to_add=to_add, model=model, node_weights=node_weights, node_hierarchy=node_hierarchy,
+                hierarchy_rules=rules, booster="cbgt")
+
+
+def cbgt_batch(B, seed=0, **kw):
+    """B cbgt_case problems as flat problems: half with the server-group rule, half rebalances (alternating)."""
+    return [problem.build_problem(**cbgt_case(seed * 100003 + i, hierarchy=i % 2 == 0, rebalance=(i // 2) % 2 == 0, **kw))
+            for i in range(B)]
