@@ -18,8 +18,8 @@
 #include <string>
 #include <vector>
 
-#include "k_flat.h"
 #include "k_sweep.h"
+#include "k_flat.h"
 #include "k_period.h"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
 #include "tu_seq.hip"
@@ -225,6 +225,8 @@ struct blance_ctx {
     int chain_group_state = -1;     // the state whose chain pass last grouped the steps by region (chain_order, chain_oi, reg_off) ...
     bool chain_group_static = false; // ... and whether it did so from the static order (sweeps >= 2)
     bool tops_moved = true;         // this sweep's top-state pass was not (known to be) one run of stays
+    uint32_t top_gate = 0;          // the words of scal + 4 every launch behind a top-state pass assumed to be one run of stays waits
+                                    // for (plan_locked: kFlagTopMoved, kFlagForced), 0 when that pass's verdict is known
     bool flags_clean = false;       // the chain passes' flag words (scalars[4 .. 11]) are zero: nothing has set one since the last fill
     bool rowcount_clean = false;    // f_row_count is zero (k_flat_row_count adds to it)
     bool top_prio_strict = false;   // every other state with constraints > 0 has a priority strictly behind the top state's
@@ -1247,6 +1249,10 @@ static int run_flat_chain(blance_ctx* c, PassParams q, int beg, int end, bool ld
     return 0;
 }
 
+// words of scal + 4 (a Gate's flags) outside the eight the chain passes reset: k_stay_by_top's "not all stays";
+// BLANCE_SPECULATE=fail; k_flat_stay_live's "the sweep's first pass is NOT one run of stays"
+constexpr int kFlagStayMoved = 22, kFlagForced = 23, kFlagTopMoved = 24;
+
 // The compact records a flat single chain walks (clusters of <= 256 names), made when a pass first needs them: a pass the
 // bulk runs settle entirely (config 2: every pass) never pays for the gather and its round trip.
 struct FlatChainPrep {
@@ -1268,7 +1274,7 @@ static int flat_chain_prepare(blance_ctx* c, FlatChainPrep& fc, int64_t* launche
                          c->state_has_stick.as<uint8_t>(), c->fl_iota.as<int32_t>(),
                          c->fl_zero.as<int32_t>(), c->fl_reglo.as<int32_t>(), c->fl_iota.as<int32_t>(),
                          c->fl_one.as<int32_t>(), 1,
-                         c->crec.as<int32_t>(), scal + 4, (int32_t*)nullptr);
+                         c->crec.as<int32_t>(), scal + 4, (int32_t*)nullptr, kNoGate);
     int32_t bad = 0;
     HIPTRY(read_back(c, &bad, scal + 4, sizeof bad));
     HIPTRY(stream_sync(c));
@@ -1284,8 +1290,11 @@ static int flat_chain_prepare(blance_ctx* c, FlatChainPrep& fc, int64_t* launche
 // over partitions that hold nothing, or the second when the first gave every partition ONE node in a state of higher priority
 // and NumPartitions == 0 (k_flat_scan's test for "fresh": such a node is just not a candidate).  *whole_known: the pass was
 // such a run from its first step to its last.
+// assume_stays: a `settled` pass whose stay test is enqueued and NOT read back: the pass is taken to be one run of stays, and
+// k_flat_stay_live's verdict goes to scal[4 + kFlagTopMoved] for the caller's gates and its sweep's readback (plan_locked).
 static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* launches, int64_t* batched,
-                         FlatChainPrep& fc, bool opening, bool* whole_known, bool settled, bool* nothing_to_apply, bool rows_counted) {
+                         FlatChainPrep& fc, bool opening, bool* whole_known, bool settled, bool assume_stays,
+                         bool* nothing_to_apply, bool rows_counted) {
     *whole_known = false;
     *nothing_to_apply = false;
     hipStream_t sm = c->stream;
@@ -1301,6 +1310,32 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
     fq.row_count = c->f_row_count.as<int32_t>();
     fq.ntn = q.ntn; fq.rec = q.rec; fq.out = q.out; fq.scan = scal + 8;
     fq.int_keys = (q.NP == 0 && !c->any_node_weight) ? 1 : 0;
+    if (assume_stays) {
+        // The stay test of the whole pass on the live lists (no step records: k_gather is not run), its row bound counted
+        // from them as well; the verdict stays on the device.  What the pass would then do -- nothing, see `settled` below --
+        // is done: no output, no k_scatter, and the top priority nodes are where they were.
+        if (q.NP > 0) {
+            if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)q.NX + 1), sm));
+            c->rowcount_clean = false;
+            BLANCE_LAUNCH(k_flat_row_count_live, cdiv(P, 256), 256, 0, sm, fc.d, q.top_state, c->f_row_count.as<int32_t>(), q.NX);
+            *launches += 1;
+        }
+        BLANCE_LAUNCH(k_flat_prepare, 1, 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
+                      c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>());
+        const int scan_blocks = cdiv(P, 256);
+        fq.scan_waves = scan_blocks * 4;
+        if (c->scan_part.reserve(sizeof(int32_t) * 2 * ((size_t)fq.scan_waves + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        fq.scan_part = c->scan_part.as<int32_t>();
+        BLANCE_LAUNCH(k_flat_stay_live, scan_blocks, 256, 0, sm, fq, fc.d, fc.order, c->state_stick.as<int32_t>(),
+                      c->state_has_stick.as<uint8_t>());
+        BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, (int32_t*)nullptr,
+                      scal + 4 + kFlagTopMoved, P);
+        *launches += 3;
+        if (q.s == q.top_state) c->tops_moved = false;
+        *nothing_to_apply = true;
+        *batched += P;
+        return 0;
+    }
     if (q.NP > 0 && !rows_counted) {                // only read by the stay test when NP > 0; (else: k_gather has counted)
         if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)q.NX + 1), sm));
         c->rowcount_clean = false;
@@ -1333,7 +1368,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
             if (c->scan_part.reserve(sizeof(int32_t) * 2 * ((size_t)fq.scan_waves + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
             fq.scan_part = c->scan_part.as<int32_t>();
             BLANCE_LAUNCH(k_flat_scan, scan_blocks, 256, 0, sm, fq, pos, P);
-            BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, scal + 8);
+            BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, scal + 8, (int32_t*)nullptr, P);
             HIPTRY(read_back(c, got, scal + 8, sizeof got));
             HIPTRY(stream_sync(c));
             *launches += 1;
@@ -1717,7 +1752,6 @@ struct ChainRun {
     bool spec = false;             // the classification was assumed
     Gate gate = kNoGate;
 };
-constexpr int kFlagStayMoved = 22, kFlagForced = 23;     // words of scal + 4: k_stay_by_top's "not all stays"; BLANCE_SPECULATE=fail
 
 // 0 = ok (*done tells whether the pass was made; if not, the counters are as before and the caller
 // runs the pass in order), < 0 = error.
@@ -1737,9 +1771,12 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
     const bool sharded = (G > 1 || c->shard_one_rank) && B >= G;
     if (!c->flags_clean) HIPTRY(hipMemsetAsync(scal + 4, 0, 32, sm));
     c->flags_clean = false;
+    // (c->top_gate: the sweep's first pass is taken to be one run of stays -- plan_locked -- and every launch of this pass
+    // waits for that verdict: closed, it returns at once)
+    const Gate top_gate{scal + 4, c->top_gate};
     BLANCE_LAUNCH_NOSYNC(k_chain_classify, cdiv(P + 1, 256), 256, 0, sm, d, m, h.top_state,
                          a.order, rr.node_region.as<int32_t>(), c->regid.as<int32_t>(),
-                         c->n_ev.as<int32_t>(), scal + 4);
+                         c->n_ev.as<int32_t>(), scal + 4, top_gate);
     int nbits = 1;
     while ((1 << nbits) < B) nbits++;
     // The steps grouped by the region of their top priority node (a stable counting sort of the pass order).  A sweep whose
@@ -1768,13 +1805,15 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
     // assume there are none and to look at flags[6], flags[7] only when the pass's own flags come back.
     const bool spec = run.allow_spec && !regroup && !sharded && c->speculate > 0;
     const bool defer = run.defer && !sharded && c->speculate > 0;
+    if (c->top_gate && (regroup || !spec || !defer))               // (plan_locked's top_spec_fits rules these out)
+        return fail(BLANCE_ERR_DEVICE, "a chain pass behind the top-state pass's verdict would read back");
     run.spec = spec;
     run.pending = 0;
     run.redo = false;
     auto gate_on = [&](uint32_t words) {               // (the words of scal + 4 a deferred verdict depends on)
         Gate g;
         g.flags = scal + 4;
-        g.mask = words | (1u << kFlagForced) | (spec ? (1u << 6) | (1u << 7) : 0u);
+        g.mask = words | (1u << kFlagForced) | (spec ? (1u << 6) | (1u << 7) : 0u) | c->top_gate;
         return g;
     };
     int32_t n_events = 0, cfl[8] = {0};
@@ -1852,7 +1891,7 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
                          c->state_has_stick.as<uint8_t>(), c->node_leaf_pos.as<int32_t>(),
                          rr.node_region.as<int32_t>(), rr.reg_lo.as<int32_t>(), rr.leaf_cls.as<int32_t>(),
                          rr.cls_size.as<int32_t>(), 0,
-                         c->crec.as<int32_t>(), scal + 4, group_now ? c->topkey.as<int32_t>() : (int32_t*)nullptr);
+                         c->crec.as<int32_t>(), scal + 4, group_now ? c->topkey.as<int32_t>() : (int32_t*)nullptr, top_gate);
     // steps grouped by the leaf of their top priority node, pass order inside a group (stable counting sort)
     auto group_by_top = [&](hipStream_t st, DevBuf& sums) -> int {
         int lbits = 1;
@@ -1904,6 +1943,7 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
     cq.cnt = c->cnt.as<int32_t>(); cq.ntn = c->ntn.as<int32_t>();
     cq.crec = c->crec.as<int32_t>(); cq.out = c->out.as<int32_t>();
     cq.flags = scal + 4;
+    cq.gate = c->top_gate;
     cq.ev_off = c->ev_off.as<int32_t>(); cq.ev_perm = c->ev_perm.as<int32_t>();
     cq.ev_oi = c->ev_oi.as<int32_t>(); cq.ev_leaf = c->ev_leaf.as<int32_t>(); cq.ev_w = c->ev_w.as<int32_t>();
     if (cfl[6])                                        // nodes of this state that lie in no region
@@ -1934,6 +1974,7 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
         sq.cnt = c->cnt.as<int32_t>(); sq.crec = c->crec.as<int32_t>();
         sq.top_off = c->top_off.as<int32_t>(); sq.top_order = c->top_order.as<int32_t>();
         sq.out = c->out.as<int32_t>(); sq.flag = scal + 4 + kFlagStayMoved;
+        sq.gate = top_gate;
         if (launch_stay_by_top(sm, sq, rr.n_stay_wgs, rr.max_size)) {
             launches += 1;
             if (defer) {
@@ -2199,6 +2240,7 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
     int m_last = -1;                                                 // the last state a sweep makes a pass for
     for (int m = 0; m < M; m++)
         if (c->state_constraints[m] > 0 && P > 0) m_last = m;
+    bool top_spec_plan = true;                                       // (no sweep of this plan has refuted it: see top_spec_off)
     for (int it = 0; it < h.max_iterations; it++) {                 // plan.go:32
         const bool first = it == 0;
         d.node_removed = first ? c->node_removed.as<uint8_t>() : c->zeros_nx.as<uint8_t>();   // plan.go:53-55
@@ -2246,8 +2288,36 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
         int m_from = 0;
         ChainRun retry;
         bool retrying = false, counted = false;
+        // The sweep's first pass, when it is `settled` below, need not be read back either: its stay test leaves a word on the
+        // device (kFlagTopMoved), everything behind it waits for that word, and the word comes back with the convergence word.
+        // Set, the whole sweep runs again from its first pass with that pass read back (top_spec_off).  This holds only when
+        // every later pass of the sweep keeps its own verdict on the device as well (top_spec_fits), so that nothing of the
+        // sweep is read before its one readback.
+        bool top_spec_off = false;
+        const int64_t batched_sw = batched, steps_sw = steps;
+        const int n_pass_sw = n_pass;
+        std::vector<int64_t> last_stays_sw;
+        // run_chain_pass_once makes the pass of state t from the grouping by region it made last sweep, assumes its
+        // classification and defers its verdict: no readback inside
+        auto top_spec_fits = [&](int m0) {
+            if (NP == 0 || !c->top_prio_strict || m0 != h.top_state) return false;
+            for (int t = m0 + 1; t < M; t++) {
+                const int kt = c->state_constraints[t];
+                if (kt <= 0) continue;
+                if (t != m_last) return false;
+                const int q0 = c->rule_off[t], q1 = c->rule_off[t + 1];
+                if (c->engine == BLANCE_ENGINE_SEQUENTIAL || h.hierarchy_rules_nil || q1 - q0 != 1 || !c->rule_regions[q0].ok ||
+                    P < c->chain_min_parts || kt > 4)
+                    return false;
+                const int B = c->rule_regions[q0].n_regions;
+                if ((c->comm.n_ranks > 1 || c->shard_one_rank) && B >= c->comm.n_ranks) return false;
+                if (c->chain_group_state != t || !c->chain_group_static || c->h_reg_off.size() != (size_t)B + 1) return false;
+            }
+            return true;
+        };
         for (;;) {
         ChainRun pend;
+        c->top_gate = 0;
         int64_t batched0 = batched, steps0 = steps;
         int n_pass0 = n_pass, passes0 = passes_this_sweep;
         for (int m = m_from; m < M; m++) {                          // plan.go:307-324
@@ -2312,13 +2382,16 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
             const bool bulk = c->engine != BLANCE_ENGINE_SEQUENTIAL && flat_state && (k == 1 || (k == 2 && NP == 0)) &&
                               P >= c->chain_min_parts;
             const bool count_rows = bulk && NP > 0 && c->f_row_count.p;
-            if (count_rows) {
+            const bool settled = bulk && !first && passes_this_sweep == 1 && !retrying && c->dump_sweep < 0 && c->speculate > 0;
+            const bool assume_stays = settled && top_spec_plan && !top_spec_off && k == 1 && top_spec_fits(m);
+            if (count_rows && !assume_stays) {
                 if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)NX + 1), sm));
                 c->rowcount_clean = false;
             }
-            BLANCE_LAUNCH(k_gather, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (RW | 1) + 64, sm, d, m, h.top_state, RW, order,
-                                 c->state_stick.as<int32_t>(), c->state_has_stick.as<uint8_t>(), c->rec.as<int32_t>(),
-                                 count_rows ? c->f_row_count.as<int32_t>() : (int32_t*)nullptr, NX);
+            if (!assume_stays)
+                BLANCE_LAUNCH(k_gather, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (RW | 1) + 64, sm, d, m, h.top_state, RW, order,
+                                     c->state_stick.as<int32_t>(), c->state_has_stick.as<uint8_t>(), c->rec.as<int32_t>(),
+                                     count_rows ? c->f_row_count.as<int32_t>() : (int32_t*)nullptr, NX);
             PassParams q;
             memset(&q, 0, sizeof q);
             q.N = N; q.NX = NX; q.M = M; q.L = L; q.P = P; q.s = m; q.k = k; q.top_state = h.top_state;
@@ -2367,8 +2440,13 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
                 const bool opening = first && !retrying && !known_broken &&
                                      (known_passes == 0 || (known_passes == 1 && known_k == 1 && NP == 0 && ((higher_mask >> known_state) & 1)));
                 bool whole_known = false;
-                const bool settled = !first && passes_this_sweep == 1 && !retrying && c->dump_sweep < 0 && c->speculate > 0;
-                e = run_flat_pass(c, q, scal, &launches, &batched, fc, opening, &whole_known, settled, &nothing_to_apply, count_rows);
+                if (assume_stays) last_stays_sw = c->last_stays;
+                e = run_flat_pass(c, q, scal, &launches, &batched, fc, opening, &whole_known, settled, assume_stays, &nothing_to_apply,
+                                  count_rows);
+                if (assume_stays) {
+                    c->top_gate = (1u << kFlagTopMoved) | (1u << kFlagForced);
+                    if (c->trace) fprintf(stderr, "[blance] sweep %d: state %d's pass taken to be one run of stays, checked with the sweep's readback\n", it, m);
+                }
                 if (whole_known) { known_passes++; known_state = m; known_k = k; }
                 else known_broken = true;
             } else if (flat_chain) {
@@ -2397,7 +2475,8 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
         counted = true;
         // convergence (plan.go:36-45) + write-back (plan.go:49-52)
         if (P > 0) {
-            BLANCE_LAUNCH(k_converge, cdiv(P, 256), 256, 0, sm, d, scal + 1, pend.pending ? pend.gate : kNoGate);   // (uses a wave ballot)
+            BLANCE_LAUNCH(k_converge, cdiv(P, 256), 256, 0, sm, d, scal + 1,
+                          pend.pending ? pend.gate : c->top_gate ? Gate{scal + 4, c->top_gate} : kNoGate);   // (uses a wave ballot)
             launches++;
         }
         // one readback per sweep: the convergence word with the warnings count, the chain flags (a deferred verdict) and --
@@ -2406,6 +2485,31 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
         HIPTRY(read_back(c, hs, scal, sizeof hs));
         HIPTRY(stream_sync(c));
         HIPTRY(hipGetLastError());
+        if (c->top_gate) {
+            const bool moved = hs[4 + kFlagTopMoved] || c->speculate == 2;
+            c->top_gate = 0;
+            if (c->trace) fprintf(stderr, "[blance] sweep %d: the first pass %s\n", it, moved ? "was not one run of stays: the sweep runs again" : "was one run of stays");
+            if (moved) {
+                // Nothing behind the gate ran: the live lists, prevMap, the counters and the flag words are as the sweep's
+                // first pass found them.  What the host assumed or cached along the way is dropped.
+                c->spec_refuted++;
+                c->last_stays = last_stays_sw;
+                c->tops_moved = true;
+                c->chain_group_state = -1;                          // (a gated k_chain_classify wrote no region ids ...)
+                c->group_epoch++;
+                c->top_group_state = -1;                            // (... and a gated k_gather_chain no top priority keys)
+                c->pass_ntn_ready = false;
+                batched = batched_sw; steps = steps_sw; n_pass = n_pass_sw; passes_this_sweep = 0;
+                known_passes = 0; known_state = -1; known_k = 0; known_broken = false;
+                retry = ChainRun();
+                retrying = false;
+                top_spec_off = true;
+                top_spec_plan = false;                              // (a plan whose top-state pass moves steps in one later
+                                                                    // sweep tends to do so in the next: read them back)
+                m_from = 0;
+                continue;
+            }
+        }
         if (!pend.pending) break;
         {
             const int32_t* f = hs + 4;

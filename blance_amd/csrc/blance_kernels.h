@@ -122,6 +122,7 @@ struct ChainParams {
     int32_t* flags;                // [0] a step is not region-local, [1] a chain had to escape,
                                    // [2] steps committed as verified stays, [3] stay batches,
                                    // [4] flat mode: first step not done, [5] stopped by the key range
+    uint32_t gate;                 // k_pass_chain: words of flags[] (a Gate's mask) that, any of them set, make the launch return
 };
 
 // k_stay_by_top (k_stay.h): a chain pass of stays verified by one thread per top priority node
@@ -144,6 +145,7 @@ struct StayParams {
     const int32_t* top_order;      // chain indices grouped by top leaf
     int32_t* out;
     int32_t* flag;                 // set to 1 by any step that is not a certain stay
+    Gate gate;                     // closed: the launch returns at once
 };
 
 

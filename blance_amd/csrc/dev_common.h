@@ -38,6 +38,18 @@ __device__ __forceinline__ bool better(double s1, int n1, double s2, int n2) {
     return s1 < s2 || (s1 == s2 && n1 < n2);
 }
 
+// A Gate (blance_kernels.h) is closed when one of its words is set.
+__device__ __forceinline__ bool gate_closed(const Gate& g) {
+    uint32_t mk = g.mask;
+    bool closed = false;
+    while (mk) {
+        const int b = __ffsll((long long)mk) - 1;
+        mk &= mk - 1;
+        closed |= g.flags[b] != 0;
+    }
+    return closed;
+}
+
 __device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 struct RedSlot { unsigned hi, lo; int n; int pad; };

@@ -91,13 +91,14 @@ __device__ __forceinline__ void scan_note_first(bool flag, int oi, int32_t* part
         part_row[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = first < 0 ? INT_MAX : oi;
 }
 
-__global__ __launch_bounds__(1024) void k_flat_scan_min(int n_waves, const int32_t* part /* [2][n_waves] */, int32_t* scan) {
+__global__ __launch_bounds__(1024) void k_flat_scan_min(int n_waves, const int32_t* part /* [2][n_waves] */, int32_t* scan,
+                                                        int32_t* not_whole /* or null */, int end) {
     BLANCE_DYN_LDS(lds);
     int* red = (int*)lds;                            // [2][16]
     const int tid = threadIdx.x;
     int m0 = INT_MAX, m1 = INT_MAX;
     for (int i = tid; i < n_waves; i += 1024) {
-        const int a = part[i], b = part[n_waves + i];
+        const int a = part[i], b = scan ? part[n_waves + i] : INT_MAX;
         m0 = a < m0 ? a : m0;
         m1 = b < m1 ? b : m1;
     }
@@ -111,9 +112,67 @@ __global__ __launch_bounds__(1024) void k_flat_scan_min(int n_waves, const int32
     __syncthreads();
     if (tid == 0) {
         for (int w = 0; w < 16; w++) { m0 = red[w] < m0 ? red[w] : m0; m1 = red[16 + w] < m1 ? red[16 + w] : m1; }
-        scan[0] = m0;                                // first step that is not a certain stay (INT_MAX: none)
-        scan[1] = m1;                                // first step that is not fresh-identical to the range's first
+        if (scan) {
+            scan[0] = m0;                            // first step that is not a certain stay (INT_MAX: none)
+            scan[1] = m1;                            // first step that is not fresh-identical to the range's first
+        }
+        if (not_whole) *not_whole = m0 < end ? 1 : 0;    // k_flat_stay_live's verdict: the range is NOT one run of stays
     }
+}
+
+// One step's lists as k_flat_scan's stay test reads them: from its record (k_gather) ...
+struct FlatRecView {
+    const int32_t* r;
+    int SW;
+    __device__ int hdr(int t) const { return r[kRecHead + t * SW]; }
+    __device__ bool absent(int t) const { return (hdr(t) >> 16) == kListAbsent; }
+    __device__ int len(int t) const { const int h = hdr(t); return (h >> 16) == kListAbsent ? 0 : (h & 0xffff); }
+    __device__ int node(int t, int j) const { return r[kRecHead + t * SW + 1 + j]; }
+};
+// ... or from the partition's live lists, where k_gather would have copied them from
+struct FlatLiveView {
+    const DevProblem* d;
+    int p;
+    __device__ bool absent(int t) const { return d->live_kind[p * d->M + t] == kListAbsent; }
+    __device__ int len(int t) const { const int idx = p * d->M + t; return d->live_kind[idx] == kListAbsent ? 0 : d->live_len[idx]; }
+    __device__ int node(int t, int j) const { return d->live[(size_t)(p * d->M + t) * d->L + j]; }
+};
+
+// Is the step a certain stay (k = 1)?  top: the partition's top priority node or -1, stick: its stickiness.
+template <class V>
+__device__ __forceinline__ bool flat_certain_stay(const FlatParams& q, const V& v, int top, double stick) {
+    bool stay = false;
+    if (q.k == 1 && v.len(q.s) == 1) {
+        int o = v.node(q.s, 0);
+        bool ok = o < q.N && q.alive[o];
+        for (int t = 0; t < q.M && ok; t++) {           // o in another list of the partition: promoted / excluded
+            if (t == q.s) continue;
+            if (v.absent(t)) continue;
+            const int n_t = v.len(t);
+            for (int j = 0; j < n_t; j++) if (v.node(t, j) == o) ok = false;
+        }
+        if (ok) {
+            int ub = q.NP > 0 ? q.row_count[top < 0 ? q.NX : top] : 0;
+            double s_hi = node_score(q.cnt[q.s * q.NX + o], ub, q.tot[o], q.node_has_weight[o], q.node_weight[o],
+                                     q.NP, stick, q.booster_kind);
+            // smallest other candidate: first listed node that is neither o nor excluded
+            bool found = false;
+            for (int e = 0; e < kTopList && !found; e++) {
+                int n = q.top_n[e];
+                if (n == INT_MAX) { found = true; stay = true; break; }        // no other candidate at all
+                bool excl = n == o;
+                for (int t = 0; t < q.M && !excl; t++) {
+                    if (v.absent(t) || !((q.higher_mask >> t) & 1)) continue;
+                    const int n_t = v.len(t);
+                    for (int j = 0; j < n_t; j++) if (v.node(t, j) == n) excl = true;
+                }
+                if (excl) continue;
+                found = true;
+                stay = better(s_hi, o, q.top_g[e], n);
+            }
+        }
+    }
+    return stay;
 }
 
 __global__ void k_flat_scan(FlatParams q, int beg, int end) {
@@ -126,8 +185,6 @@ __global__ void k_flat_scan(FlatParams q, int beg, int end) {
     const double stick = __hiloint2double(r[3], r[2]);
     int hT = r[kRecHead + q.top_state * SW];
     int top = ((hT >> 16) != kListAbsent && (hT & 0xffff) > 0) ? r[kRecHead + q.top_state * SW + 1] : -1;
-    int hs = r[kRecHead + q.s * SW];
-    int own_len = (hs >> 16) == kListAbsent ? 0 : (hs & 0xffff);
     int all_len = 0, high_len = 0;                     // nodes the partition holds in any / in higher priority states
     for (int t = 0; t < q.M; t++) {
         int h = r[kRecHead + t * SW];
@@ -147,38 +204,41 @@ __global__ void k_flat_scan(FlatParams q, int beg, int end) {
         scan_note_first(in_range && !fresh, oi, q.scan_part + q.scan_waves);
     }
     // ---- certain stay?
-    bool stay = false;
-    if (q.k == 1 && own_len == 1) {
-        int o = r[kRecHead + q.s * SW + 1];
-        bool ok = o < q.N && q.alive[o];
-        for (int t = 0; t < q.M && ok; t++) {           // o in another list of the partition: promoted / excluded
-            if (t == q.s) continue;
-            int h = r[kRecHead + t * SW];
-            if ((h >> 16) == kListAbsent) continue;
-            for (int j = 0; j < (h & 0xffff); j++) if (r[kRecHead + t * SW + 1 + j] == o) ok = false;
-        }
-        if (ok) {
-            int ub = q.NP > 0 ? q.row_count[top < 0 ? q.NX : top] : 0;
-            double s_hi = node_score(q.cnt[q.s * q.NX + o], ub, q.tot[o], q.node_has_weight[o], q.node_weight[o],
-                                     q.NP, stick, q.booster_kind);
-            // smallest other candidate: first listed node that is neither o nor excluded
-            bool found = false;
-            for (int e = 0; e < kTopList && !found; e++) {
-                int n = q.top_n[e];
-                if (n == INT_MAX) { found = true; stay = true; break; }        // no other candidate at all
-                bool excl = n == o;
-                for (int t = 0; t < q.M && !excl; t++) {
-                    int h = r[kRecHead + t * SW];
-                    if ((h >> 16) == kListAbsent || !((q.higher_mask >> t) & 1)) continue;
-                    for (int j = 0; j < (h & 0xffff); j++) if (r[kRecHead + t * SW + 1 + j] == n) excl = true;
-                }
-                if (excl) continue;
-                found = true;
-                stay = better(s_hi, o, q.top_g[e], n);
-            }
-        }
-    }
+    const bool stay = flat_certain_stay(q, FlatRecView{r, SW}, top, stick);
     scan_note_first(in_range && !stay, oi, q.scan_part);
+}
+
+// The stay test of a whole pass that is expected to be one run of stays (the first pass of a sweep >= 2), on the live lists
+// themselves: no step records.  Row [0] of scan_part only, as k_flat_scan leaves it; k_flat_scan_min turns it into a
+// verdict word.  The partitions' weights and stickiness as k_gather puts them into a record.
+__global__ void k_flat_stay_live(FlatParams q, DevProblem d, const int32_t* order, const int32_t* state_stickiness,
+                                 const uint8_t* state_has_stickiness) {
+    int oi = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in_range = oi < q.P;
+    if (!in_range) oi = q.P - 1;                     // keep the wave whole for the ballot below
+    const int p = order[oi];
+    double stick = 1.5;                              // plan.go:104-115
+    if (!d.weights_nil) {
+        if (d.part_has_weight[p]) stick = (double)d.part_weight[p];
+        else if (state_has_stickiness[q.s]) stick = (double)state_stickiness[q.s];
+    }
+    const int idxT = p * d.M + q.top_state;
+    const int top = (d.live_kind[idxT] != kListAbsent && d.live_len[idxT] > 0) ? d.live[(size_t)idxT * d.L] : -1;
+    const bool stay = flat_certain_stay(q, FlatLiveView{&d, p}, top, stick);
+    scan_note_first(in_range && !stay, oi, q.scan_part);
+}
+
+// k_flat_stay_live's row bound (k_flat_row_count) from the live lists: the steps of the pass per top priority node
+__global__ void k_flat_row_count_live(DevProblem d, int top_state, int32_t* row_count, int NX) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    int top = -1;
+    if (p < d.P) {
+        const int idxT = p * d.M + top_state;
+        if (d.live_kind[idxT] != kListAbsent && d.live_len[idxT] > 0) top = d.live[(size_t)idxT * d.L];
+        if (top >= 0) atomicAdd(&row_count[top], 1);
+    }
+    const unsigned long long none = __ballot(p < d.P && top < 0);      // the "" row: one atomic per wave
+    if (none && (int)(threadIdx.x & 63) == __ffsll((long long)none) - 1) atomicAdd(&row_count[NX], __popcll(none));
 }
 
 // commit a run of certain stays: the lists do not change; nodeToNodeCounts does (plan.go:238-245)

@@ -157,7 +157,7 @@ constexpr int chain_waves_max() { return NPTC >= 8 ? 4 : kChainWaves; }
 template <int NPTC, int KM, bool FAST>
 __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(ChainParams q) {
     BLANCE_DYN_LDS(lds);
-    if (q.flags[0]) return;
+    if (q.flags[0] || gate_closed(Gate{q.flags, q.gate})) return;
     const int lane = threadIdx.x & 63;
     const int wave = uni((int)(threadIdx.x >> 6)), NWv = uni((int)(blockDim.x >> 6));
     const int rg = q.region_base + blockIdx.x;

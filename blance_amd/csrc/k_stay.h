@@ -51,6 +51,7 @@ __device__ __forceinline__ double stay_score(int cnt, int ntn, int tot, int hasw
 template <int KM>
 __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
     BLANCE_DYN_LDS(lds);
+    if (gate_closed(q.gate)) return;               // (the sweep's top-state pass was not one run of stays after all)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wgi = blockIdx.x / kStaySplit, sub = blockIdx.x % kStaySplit;
     const int rg = q.wg_region[wgi];

@@ -260,7 +260,8 @@ __global__ __launch_bounds__(64) void k_part_scatter(int n, const int32_t* key32
 // says there are any; flags[6] is raised if some lie in no region at all --
 // k_chain_orphans un-counts those).
 __global__ void k_chain_classify(DevProblem d, int m, int top_state, const int32_t* order,
-                                 const int32_t* node_region, int32_t* regid, int32_t* n_ev, int32_t* flags) {
+                                 const int32_t* node_region, int32_t* regid, int32_t* n_ev, int32_t* flags, Gate gate) {
+    if (gate_closed(gate)) return;                 // (the host runs the sweep again from its first pass)
     int oi = blockIdx.x * blockDim.x + threadIdx.x;
     if (oi > d.P) return;
     if (oi == d.P) { n_ev[oi] = 0; return; }
@@ -395,7 +396,14 @@ __global__ void k_gather_chain(DevProblem d, int m, int top_state, int higher_ma
                                const int32_t* state_stickiness, const uint8_t* state_has_stickiness,
                                const int32_t* node_leaf_pos, const int32_t* node_region, const int32_t* reg_lo,
                                const int32_t* leaf_cls, const int32_t* cls_size, int flat, int32_t* crec,
-                               int32_t* flags, int32_t* topkey /* or null: global leaf of the step's top priority node */) {
+                               int32_t* flags, int32_t* topkey /* or null: global leaf of the step's top priority node */, Gate gate) {
+    if (gate_closed(gate)) {
+        // (the host runs the sweep again from its first pass; the second stream may already be grouping the steps by these
+        // keys, and a key must stay a valid bucket there: 0)
+        const int i = blockIdx.x * blockDim.x + threadIdx.x;
+        if (topkey && i < d.P) topkey[i] = 0;
+        return;
+    }
     // a thread builds its record in LDS (row stride kCW + 1: no bank conflicts); the workgroup then writes its
     // 256 records as one contiguous block -- per-thread 24-word rows written straight to HBM cost 3.7 times
     // their bytes in write traffic (rocprofv3 WRITE_SIZE, round 2)
@@ -602,17 +610,6 @@ __global__ __launch_bounds__(256) void k_ntn_bits(int N, int rows, int BW, const
 
 // Apply the pass's choices to the live lists (plan.go:290-299); list edits only
 // touch the step's own partition, so this runs in parallel after the pass.
-__device__ __forceinline__ bool gate_closed(const Gate& g) {
-    uint32_t mk = g.mask;
-    bool closed = false;
-    while (mk) {
-        const int b = __ffsll((long long)mk) - 1;
-        mk &= mk - 1;
-        closed |= g.flags[b] != 0;
-    }
-    return closed;
-}
-
 __global__ void k_scatter(DevProblem d, int m, int OW, const int32_t* order, const int32_t* out, Gate gate) {
     int oi = blockIdx.x * blockDim.x + threadIdx.x;
     if (oi >= d.P) return;
