@@ -251,6 +251,23 @@ class BatchInfo(C.Structure):
                 ("steps_total", C.c_int64), ("device_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class BatchMoves(C.Structure):
+    """blance_batch_moves of include/blance_batch.h (blance_plan_batch_moves): one problem's moves request and buffers."""
+    _fields_ = [("favor_min_nodes", C.c_int32), ("beg_other_off", _i32p), ("beg_other_nodes", _i32p),
+                ("out", MovesResult)]
+
+
+# blance_batch_moves as a numpy record (pointers as addresses): Planner.plan_batch_moves fills many at once
+BATCH_MOVES_DTYPE = np.dtype({
+    "names": ["favor_min_nodes", "beg_other_off", "beg_other_nodes", "op_off", "op_node", "op_state", "op_kind",
+              "capacity", "device_ms"],
+    "formats": [np.int32, np.uint64, np.uint64, np.uint64, np.uint64, np.uint64, np.uint64, np.int64, np.float64],
+    "offsets": [BatchMoves.favor_min_nodes.offset, BatchMoves.beg_other_off.offset, BatchMoves.beg_other_nodes.offset] +
+               [BatchMoves.out.offset + getattr(MovesResult, f).offset
+                for f in ("op_off", "op_node", "op_state", "op_kind", "capacity", "device_ms")],
+    "itemsize": C.sizeof(BatchMoves)})
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
 
 

@@ -2679,10 +2679,7 @@ static int download_locked(blance_ctx* c, blance_result* res) {
     return BLANCE_OK;
 }
 
-extern "C" int blance_calc_moves(blance_ctx* c, const blance_moves_problem* pb, blance_moves_result* res) {
-    return guarded([&]() -> int {
-    if (!c || !pb || !res) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
+static int calc_moves_locked(blance_ctx* c, const blance_moves_problem* pb, blance_moves_result* res) {
     const int P = pb->n_parts, M = pb->n_states;
     if (P < 0 || M < 0 || !pb->beg_off || !pb->end_off || !pb->beg_nodes || !pb->end_nodes || !res->op_off ||
         !res->op_node || !res->op_state || !res->op_kind)
@@ -2748,6 +2745,13 @@ extern "C" int blance_calc_moves(blance_ctx* c, const blance_moves_problem* pb, 
     HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     res->device_ms = ms;
     return BLANCE_OK;
+}
+
+extern "C" int blance_calc_moves(blance_ctx* c, const blance_moves_problem* pb, blance_moves_result* res) {
+    return guarded([&]() -> int {
+    if (!c || !pb || !res) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    return calc_moves_locked(c, pb, res);
     });
 }
 
@@ -2867,6 +2871,7 @@ struct BatchItem {
     int threads;        // 64 / 256: k_plan_batch's size class
     BatchDesc d;
     int64_t in_words, sc_words, out_words;
+    int mi = -1;        // its BatchMovesDesc, when the caller asks for its moves
 };
 
 int batch_list_len(const blance_problem* pb) {
@@ -2968,6 +2973,26 @@ void batch_pack(const blance_problem* pb, const BatchDesc& d, int32_t* dst) {
         }
 }
 
+// the moves request of one problem: buffers, the beg_other CSR, the capacity
+int batch_moves_check(const blance_problem* pb, const blance_batch_moves* mv) {
+    const blance_moves_result& o = mv->out;
+    if (!o.op_off || !o.op_node || !o.op_state || !o.op_kind) return fail(BLANCE_ERR_BAD_ARG, "null moves buffers");
+    if (!mv->beg_other_off != !mv->beg_other_nodes)
+        return fail(BLANCE_ERR_BAD_ARG, "beg_other_off and beg_other_nodes: both or neither");
+    if (pb->max_iterations <= 0) return fail(BLANCE_ERR_BAD_ARG, "moves asked for a problem with max_iterations <= 0 (no map)");
+    if (mv->beg_other_off) {
+        const int32_t* off = mv->beg_other_off;
+        if (off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets must start at 0");
+        for (int p = 0; p < pb->n_parts; p++)
+            if (off[p + 1] < off[p]) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets not monotone");
+        for (int32_t j = 0; j < off[pb->n_parts]; j++)
+            if (mv->beg_other_nodes[j] < 0 || mv->beg_other_nodes[j] >= pb->n_nodes_ext)
+                return fail(BLANCE_ERR_BAD_ARG, "beg_other node id outside [0, n_nodes_ext)");
+    }
+    if (o.capacity < blance_batch_moves_capacity(pb, mv)) return fail(BLANCE_ERR_CAPACITY, "moves capacity too small");
+    return BLANCE_OK;
+}
+
 // every check blance_plan would make before it writes a result, and the result buffers' capacities
 int batch_check(const blance_problem* pb, const blance_result* r) {
     int st = blance_validate(pb);
@@ -2984,12 +3009,51 @@ int batch_check(const blance_problem* pb, const blance_result* r) {
 }
 }  // namespace
 
+// the moves of a problem the single path planned: blance_calc_moves's path on its prevMap lists (keys outside the model
+// as pseudo state M) and its downloaded result
+static int batch_moves_single(blance_ctx* c, const blance_problem* pb, const blance_result* r, blance_batch_moves* mv,
+                              int64_t* launches) {
+    const int P = pb->n_parts, M = pb->n_states;
+    std::vector<int32_t> boff(1, 0), bnod, eoff(1, 0), enod;
+    boff.reserve((size_t)P * (M + 1) + 1);
+    eoff.reserve((size_t)P * (M + 1) + 1);
+    bnod.reserve((size_t)pb->prev_off[(size_t)P * M] + (mv->beg_other_off ? mv->beg_other_off[P] : 0) + 1);
+    enod.reserve((size_t)r->out_off[(size_t)P * M] + 1);       // (+ 1: data() is never NULL)
+    for (int p = 0; p < P; p++) {
+        for (int m = 0; m < M; m++) {
+            const size_t idx = (size_t)p * M + m;
+            bnod.insert(bnod.end(), pb->prev_nodes + pb->prev_off[idx], pb->prev_nodes + pb->prev_off[idx + 1]);
+            boff.push_back((int32_t)bnod.size());
+            enod.insert(enod.end(), r->out_nodes + r->out_off[idx], r->out_nodes + r->out_off[idx + 1]);
+            eoff.push_back((int32_t)enod.size());
+        }
+        if (mv->beg_other_off)
+            bnod.insert(bnod.end(), mv->beg_other_nodes + mv->beg_other_off[p], mv->beg_other_nodes + mv->beg_other_off[p + 1]);
+        boff.push_back((int32_t)bnod.size());
+        eoff.push_back((int32_t)enod.size());
+    }
+    blance_moves_problem q;
+    q.n_parts = P; q.n_states = M; q.favor_min_nodes = mv->favor_min_nodes ? 1 : 0;
+    q.beg_off = boff.data(); q.beg_nodes = bnod.data(); q.end_off = eoff.data(); q.end_nodes = enod.data();
+    const int st = calc_moves_locked(c, &q, &mv->out);
+    if (!st && P > 0) *launches += 2 + (P + 1 <= 4 * kScanTile ? 1 : 3);    // k_calc_moves, the scan, k_moves_compact
+    return st;
+}
+
+extern "C" int64_t blance_batch_moves_capacity(const blance_problem* pb, const blance_batch_moves* mv) {
+    if (!pb || !pb->prev_off || pb->n_parts < 0 || pb->n_states < 0) return 0;
+    int64_t cap = pb->prev_off[(size_t)pb->n_parts * pb->n_states] + blance_result_capacity(pb);
+    if (mv && mv->beg_other_off) cap += mv->beg_other_off[pb->n_parts];
+    return cap;
+}
+
 static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
-                             blance_batch_info* info) {
+                             blance_batch_moves* const* mvs, blance_batch_info* info) {
     const auto t_start = std::chrono::steady_clock::now();
     if (c->comm.n_ranks > 1 || c->rccl_comm) return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_batch on a context with a communicator");
     for (int i = 0; i < n; i++) {
-        const int st = batch_check(pbs[i], res[i]);
+        int st = batch_check(pbs[i], res[i]);
+        if (!st && mvs && mvs[i]) st = batch_moves_check(pbs[i], mvs[i]);
         if (st) {
             const std::string why = g_last_error;
             return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
@@ -3009,6 +3073,32 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             if (in_env && it.threads == cls) items.push_back(it);
         }
     const int nb = (int)items.size();
+    // the moves regions of the batched problems that ask for them, behind the plan's words of each slice
+    std::vector<BatchMovesDesc> mds;
+    for (int j = 0; j < nb && mvs; j++) {
+        BatchItem& it = items[j];
+        const blance_batch_moves* mv = mvs[it.idx];
+        if (!mv) continue;
+        const BatchDesc& d = it.d;
+        BatchMovesDesc md;
+        memset(&md, 0, sizeof md);
+        md.desc = j;
+        md.favor_min_nodes = mv->favor_min_nodes ? 1 : 0;
+        int n_other = 0, other_len = 0;
+        if (mv->beg_other_off) {
+            n_other = mv->beg_other_off[d.P];
+            for (int p = 0; p < d.P; p++) other_len = std::max(other_len, mv->beg_other_off[p + 1] - mv->beg_other_off[p]);
+        }
+        md.stride = std::min(2 * d.M * d.L + other_len, d.NX);   // >= the distinct nodes of a partition's two maps
+        md.cap = (int32_t)blance_batch_moves_capacity(pbs[it.idx], mv);
+        auto take = [](int32_t& field, int64_t& words, int64_t n_words) { field = (int32_t)words; words += (n_words + 3) & ~3ll; };
+        take(md.i_ooff, it.in_words, d.P + 1); take(md.i_onodes, it.in_words, n_other);
+        take(md.s_cnt, it.sc_words, d.P); take(md.s_mv, it.sc_words, (int64_t)d.P * md.stride);
+        take(md.o_moff, it.out_words, d.P + 1); take(md.o_mops, it.out_words, md.cap);
+        it.mi = (int)mds.size();
+        mds.push_back(md);
+    }
+    const int nm = (int)mds.size();
     int64_t launches = 0, steps = 0;
     double device_ms = 0.0;
     if (nb > 0) {
@@ -3023,7 +3113,8 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             else if (lds > lds256) lds256 = lds;
         }
         const size_t desc_bytes = ((sizeof(BatchDesc) * (size_t)nb) + 255) & ~(size_t)255;
-        const size_t in_bytes = desc_bytes + sizeof(int32_t) * (size_t)in_words, out_bytes = sizeof(int32_t) * (size_t)out_words;
+        const size_t head_bytes = desc_bytes + (((sizeof(BatchMovesDesc) * (size_t)nm) + 255) & ~(size_t)255);
+        const size_t in_bytes = head_bytes + sizeof(int32_t) * (size_t)in_words, out_bytes = sizeof(int32_t) * (size_t)out_words;
         struct Pinned { void* p = nullptr; ~Pinned() { pin_free(p); } } host;
         host.p = pin_alloc(in_bytes + out_bytes);
         if (!host.p) return fail(BLANCE_ERR_DEVICE, "page-locked staging block: hipHostMalloc failed");
@@ -3031,15 +3122,28 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         int32_t* h_out = (int32_t*)(h_in + in_bytes);
         for (int i = 0; i < nb; i++) {
             memcpy(h_in + sizeof(BatchDesc) * i, &items[i].d, sizeof(BatchDesc));
-            batch_pack(pbs[items[i].idx], items[i].d, (int32_t*)(h_in + desc_bytes) + items[i].d.in_base);
+            batch_pack(pbs[items[i].idx], items[i].d, (int32_t*)(h_in + head_bytes) + items[i].d.in_base);
+            if (items[i].mi >= 0) {                      // beg_other behind the input slice
+                const BatchMovesDesc& md = mds[items[i].mi];
+                const blance_batch_moves* mv = mvs[items[i].idx];
+                int32_t* dst = (int32_t*)(h_in + head_bytes) + items[i].d.in_base;
+                const int P = items[i].d.P;
+                if (mv->beg_other_off) {
+                    memcpy(dst + md.i_ooff, mv->beg_other_off, sizeof(int32_t) * ((size_t)P + 1));
+                    memcpy(dst + md.i_onodes, mv->beg_other_nodes, sizeof(int32_t) * (size_t)mv->beg_other_off[P]);
+                } else {
+                    memset(dst + md.i_ooff, 0, sizeof(int32_t) * ((size_t)P + 1));
+                }
+            }
         }
+        if (nm > 0) memcpy(h_in + desc_bytes, mds.data(), sizeof(BatchMovesDesc) * (size_t)nm);
         if (c->batch_in.reserve(in_bytes) || c->batch_sc.reserve(sizeof(int32_t) * (size_t)sc_words + 256) ||
             c->batch_out.reserve(out_bytes))
             return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
         HIPTRY(hipMemcpyAsync(c->batch_in.p, h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
         BatchParams q;
         q.desc = c->batch_in.as<BatchDesc>();
-        q.in = (const int32_t*)(c->batch_in.as<char>() + desc_bytes);
+        q.in = (const int32_t*)(c->batch_in.as<char>() + head_bytes);
         q.sc = c->batch_sc.as<int32_t>();
         q.out = c->batch_out.as<int32_t>();
         HIPTRY(hipEventRecord(c->ev0, c->stream));
@@ -3047,6 +3151,14 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         if (n64 > 0) { launch_plan_batch(c->stream, q, 64, n64, lds64); launches++; }
         q.first = n64;
         if (nb > n64) { launch_plan_batch(c->stream, q, 256, nb - n64, lds256); launches++; }
+        if (nm > 0) {
+            BatchMovesParams qm;
+            qm.desc = q.desc;
+            qm.mdesc = (const BatchMovesDesc*)(c->batch_in.as<char>() + desc_bytes);
+            qm.in = q.in; qm.sc = q.sc; qm.out = q.out;
+            launch_batch_moves(c->stream, qm, nm);
+            launches++;
+        }
         HIPTRY(hipGetLastError());
         HIPTRY(hipEventRecord(c->ev1, c->stream));
         HIPTRY(hipMemcpyAsync(h_out, c->batch_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -3086,6 +3198,17 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             r->pass_kernel_ms = r->flat_pass_ms = r->blank_pass_ms = r->stay_pass_ms = 0.0;
             r->pass_kernel_launches = r->flat_passes = r->blank_pass_launches = r->stay_pass_launches = r->host_syncs = 0;
             steps += r->steps_total;
+            if (it.mi >= 0) {                            // moves: node | (state + 1) << 16 | kind << 24
+                const BatchMovesDesc& md = mds[it.mi];
+                blance_moves_result& mo = mvs[it.idx]->out;
+                memcpy(mo.op_off, o + md.o_moff, sizeof(int32_t) * ((size_t)d.P + 1));
+                const int32_t* w = o + md.o_mops;
+                for (int32_t j = 0; j < mo.op_off[d.P]; j++) {
+                    mo.op_node[j] = w[j] & 0xffff;
+                    mo.op_state[j] = ((w[j] >> 16) & 0xff) - 1;
+                    mo.op_kind[j] = (w[j] >> 24) & 0xff;
+                }
+            }
         }
     }
     const int n_fallback = (int)fallback.size();
@@ -3111,7 +3234,17 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         launches += res[i]->kernel_launches;
         steps += res[i]->steps_total;
         device_ms += res[i]->device_ms;
+        if (mvs && mvs[i]) {
+            st = batch_moves_single(c, pbs[i], res[i], mvs[i], &launches);
+            if (st) {
+                const std::string why = g_last_error;
+                return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
+            }
+            device_ms += mvs[i]->out.device_ms;
+        }
     }
+    for (int i = 0; i < n && mvs; i++)
+        if (mvs[i]) mvs[i]->out.device_ms = device_ms;
     if (info) {
         info->n_batched = nb - (n_fallback - (n - nb));
         info->n_fallback = n_fallback;
@@ -3130,6 +3263,17 @@ extern "C" int blance_plan_batch(blance_ctx* c, int32_t n, const blance_problem*
     if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
     std::lock_guard<std::mutex> g(c->mu);
     rb_discard(c);
-    return settle(c, plan_batch_locked(c, n, pbs, res, info));
+    return settle(c, plan_batch_locked(c, n, pbs, res, nullptr, info));
+    });
+}
+
+extern "C" int blance_plan_batch_moves(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                                       blance_batch_moves* const* mvs, blance_batch_info* info) {
+    return guarded([&]() -> int {
+    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
+    if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
+    std::lock_guard<std::mutex> g(c->mu);
+    rb_discard(c);
+    return settle(c, plan_batch_locked(c, n, pbs, res, mvs, info));
     });
 }

@@ -211,4 +211,22 @@ struct BatchParams {
     int32_t first;                        // desc index of workgroup 0 of this launch
 };
 
+// The moves of one batched problem (DESIGN.md §4.9 "k_batch_moves"): offsets relative to its BatchDesc's slices.
+constexpr int kBatchMovesThreads = 256;
+struct BatchMovesDesc {
+    int32_t desc;                         // index of the problem's BatchDesc
+    int32_t favor_min_nodes;
+    int32_t i_ooff, i_onodes;             // input slice: beg_other CSR, offsets [P + 1] and node ids
+    int32_t s_cnt, s_mv, stride;          // scratch slice: move counts [P], each partition's moves [P][stride]
+    int32_t o_moff, o_mops, cap;          // output slice: op_off [P + 1], moves [cap] as node | (state + 1) << 16 | kind << 24
+};
+
+struct BatchMovesParams {
+    const BatchDesc* desc;
+    const BatchMovesDesc* mdesc;          // one workgroup each
+    const int32_t* in;
+    int32_t* sc;
+    int32_t* out;
+};
+
 }  // namespace blance

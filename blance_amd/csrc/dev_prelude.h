@@ -50,4 +50,6 @@ bool launch_stay_by_top(hipStream_t stream, const StayParams& q, int n_wgs, int 
 // k_plan_batch (tu_batch.hip): n problems of one size class, one workgroup of `threads` (64 or 256) each
 void launch_plan_batch(hipStream_t stream, const BatchParams& q, int threads, int n, size_t lds);
 size_t plan_batch_lds(int threads, int M, int NX);   // dynamic LDS of one such workgroup
+// k_batch_moves (tu_batch.hip): the partition moves of n batched problems, one workgroup each
+void launch_batch_moves(hipStream_t stream, const BatchMovesParams& q, int n);
 }  // namespace blance

@@ -1,6 +1,7 @@
-// Translation unit of k_plan_batch: many small problems in one launch, and its launch wrapper.
+// Translation unit of k_plan_batch and k_batch_moves: many small problems in one launch, and their launch wrappers.
 #include "dev_prelude.h"
 #include "k_plan_batch.h"
+#include "k_batch_moves.h"
 
 namespace blance {
 
@@ -13,6 +14,11 @@ void launch_plan_batch(hipStream_t stream, const BatchParams& q, int threads, in
     if (n <= 0) return;
     if (threads == 64) BLANCE_LAUNCH(k_plan_batch<64>, n, 64, lds, stream, q);
     else BLANCE_LAUNCH(k_plan_batch<256>, n, 256, lds, stream, q);
+}
+
+void launch_batch_moves(hipStream_t stream, const BatchMovesParams& q, int n) {
+    if (n <= 0) return;
+    BLANCE_LAUNCH(k_batch_moves, n, kBatchMovesThreads, sizeof(int) * kBatchMovesThreads, stream, q);
 }
 
 }  // namespace blance

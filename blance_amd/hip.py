@@ -83,6 +83,13 @@ def load_library(path=None):
         lib.blance_plan_batch.restype = C.c_int
         lib.blance_plan_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
                                           C.POINTER(C.POINTER(abi.Result)), C.POINTER(abi.BatchInfo)]
+    if hasattr(lib, "blance_plan_batch_moves"):
+        lib.blance_plan_batch_moves.restype = C.c_int
+        lib.blance_plan_batch_moves.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
+                                                C.POINTER(C.POINTER(abi.Result)), C.POINTER(C.POINTER(abi.BatchMoves)),
+                                                C.POINTER(abi.BatchInfo)]
+        lib.blance_batch_moves_capacity.restype = C.c_int64
+        lib.blance_batch_moves_capacity.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.BatchMoves)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
@@ -275,6 +282,63 @@ class Planner:
         info = abi.BatchInfo()
         self._check(self.lib.blance_plan_batch(self._h, n, pbs, rss, C.byref(info)))
         return results, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
+
+    def plan_batch_moves(self, fps, favor_min_nodes, beg_other=None):
+        """blance_plan_batch_moves(): plan_batch, and for each problem CalcPartitionMoves from its prevMap as passed to its
+        plan for every partition in partition id order.  favor_min_nodes: one bool, or one per problem where None asks for
+        no moves; beg_other: None, or per problem None or (offsets [P + 1], node ids) of prevMap's keys outside the model.
+        Returns ([FlatResult], [(op_off, op_node, op_state, op_kind) or None], info dict)."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_batch_moves"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_moves (build the current sources)")
+        fps = list(fps)
+        n = len(fps)
+        favor = list(favor_min_nodes) if isinstance(favor_min_nodes, (list, tuple)) else [favor_min_nodes] * n
+        other = list(beg_other) if beg_other is not None else [None] * n
+        results = [abi.FlatResult(fp) for fp in fps]
+        structs = [fp.as_struct() for fp in fps]
+        ask = [i for i in range(n) if favor[i] is not None]
+        # the requests as one numpy block viewed as blance_batch_moves[], the moves of all problems in one block:
+        # per problem op_off [P + 1], then op_node, op_state, op_kind [capacity] (no per-array ctypes conversions)
+        req = np.zeros(max(len(ask), 1), dtype=abi.BATCH_MOVES_DTYPE)
+        keep = []
+        P = np.array([fps[i].scalars["n_parts"] for i in ask], dtype=np.int64)
+        # = blance_batch_moves_capacity: prevMap entries + keys outside the model + blance_result_capacity
+        cap = np.array([fps[i].arrays["prev_off"][-1] for i in ask], dtype=np.int64) + \
+            np.array([results[i].struct.out_capacity for i in ask], dtype=np.int64)
+        req["favor_min_nodes"][:len(ask)] = [bool(favor[i]) for i in ask]
+        for j, i in enumerate(ask):
+            if other[i] is not None:
+                off, nodes = [np.ascontiguousarray(a, dtype=np.int32) for a in other[i]]
+                nodes = nodes if nodes.size else np.zeros(1, dtype=np.int32)
+                keep += [off, nodes]
+                cap[j] += int(off[P[j]])
+                req["beg_other_off"][j], req["beg_other_nodes"][j] = off.ctypes.data, nodes.ctypes.data
+        words = P + 1 + 3 * np.maximum(cap, 1)
+        base = np.zeros(len(ask) + 1, np.int64)
+        base[1:] = np.cumsum(words)
+        block = np.empty(max(int(base[-1]), 1), dtype=np.int32)          # every word read back is written by the call
+        addr = block.ctypes.data + 4 * base[:-1]
+        req["op_off"][:len(ask)] = addr
+        req["op_node"][:len(ask)] = addr + 4 * (P + 1)
+        req["op_state"][:len(ask)] = addr + 4 * (P + 1 + np.maximum(cap, 1))
+        req["op_kind"][:len(ask)] = addr + 4 * (P + 1 + 2 * np.maximum(cap, 1))
+        req["capacity"][:len(ask)] = cap
+        ptrs = np.zeros(max(n, 1), dtype=np.uint64)
+        ptrs[ask] = req.ctypes.data + req.itemsize * np.arange(len(ask), dtype=np.uint64)
+        pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
+        rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
+        info = abi.BatchInfo()
+        self._check(self.lib.blance_plan_batch_moves(self._h, n, pbs, rss,
+                                                     ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
+                                                     C.byref(info)))
+        moves = [None] * n
+        ends = (base[:-1] + P).tolist()
+        totals = block[base[:-1] + P].tolist() if ask else []
+        for j, i in enumerate(ask):
+            e, t, c = ends[j] + 1, totals[j], max(int(cap[j]), 1)
+            moves[i] = (block[e - int(P[j]) - 1:e], block[e:e + t], block[e + c:e + c + t], block[e + 2 * c:e + 2 * c + t])
+        return results, moves, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
     def plan_stats(self, n_states):
         """Per-state load statistics of the map the last plan produced (blance_plan_stats_get):

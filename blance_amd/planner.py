@@ -130,6 +130,58 @@ def PlanNextMapExBatch(calls, planner=None):
     return [_finish_call(fp, res, a["prevMap"], a["partitionsToAssign"]) for fp, res, a in zip(fps, results, args)]
 
 
+def PlanNextMapExBatchMoves(calls, favorMinNodes=False, planner=None):
+    """PlanNextMapExBatch, and each plan's partition moves from the same device call (blance_plan_batch_moves): for every
+    partition of partitionsToAssign, CalcPartitionMoves(sortStateNames(model), prevMap[name].NodesByState,
+    nextMap[name].NodesByState, favorMinNodes) with prevMap as it was before the call -- what OrchestrateMoves computes
+    next (orchestrate.go:273-287).  favorMinNodes: one bool or one per call.  Returns [(nextMap, warnings,
+    {partition name: [NodeStateOp]})] in call order, with every call's write-back done as PlanNextMapEx does; a call
+    whose plan returns no map (MaxIterationsPerPlan <= 0) gets (None, None, None)."""
+    from . import abi
+    names = ("prevMap", "partitionsToAssign", "nodesAll", "nodesToRemove", "nodesToAdd", "model", "options", "booster")
+    args = [dict(c) if isinstance(c, dict) else dict(zip(names, c)) for c in calls]
+    fps = [_build_call(**a) for a in args]
+    favor = list(favorMinNodes) if isinstance(favorMinNodes, (list, tuple)) else [favorMinNodes] * len(fps)
+    if len(favor) != len(fps):
+        raise ValueError("favorMinNodes: one bool or one per call")
+    ask, other = [], []
+    for fp, a, f in zip(fps, args, favor):
+        ask.append(bool(f) if fp.max_iterations > 0 else None)
+        other.append(_beg_other(fp, a["prevMap"]))
+    results, moves, _ = (planner or default_planner()).plan_batch_moves(fps, ask, other)
+    out = []
+    for fp, res, a, mv in zip(fps, results, args, moves):
+        nextMap, warnings = _finish_call(fp, res, a["prevMap"], a["partitionsToAssign"])
+        if nextMap is None or mv is None:
+            out.append((nextMap, warnings, None))
+            continue
+        op_off, op_node, op_state, op_kind = mv
+        byname = {}
+        for p, name in enumerate(fp.part_names):
+            byname[name] = [NodeStateOp(fp.node_names[op_node[j]], "" if op_state[j] < 0 else fp.state_names[op_state[j]],
+                                        abi.OP_NAMES[op_kind[j]]) for j in range(op_off[p], op_off[p + 1])]
+        out.append((nextMap, warnings, byname))
+    return out
+
+
+def _beg_other(fp, prevMap):
+    """prevMap's nodes under state keys outside the model, CSR over fp's partitions in its node id space (None if none)."""
+    import numpy as np
+    known = set(fp.state_names)
+    ids = {x: i for i, x in enumerate(fp.node_names)}
+    off, nodes = [0], []
+    for name in fp.part_names:
+        prev = (prevMap or {}).get(name)
+        nbs = (prev.NodesByState if hasattr(prev, "NodesByState") else (prev or {}).get("nodesByState")) or {}
+        for s, lst in nbs.items():
+            if s not in known:
+                nodes.extend(ids[x] for x in (lst or []))
+        off.append(len(nodes))
+    if not nodes:
+        return None
+    return np.asarray(off, dtype=np.int32), np.asarray(nodes, dtype=np.int32)
+
+
 def PlanNextMap(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model,
                 modelStateConstraints=None, partitionWeights=None, stateStickiness=None, nodeWeights=None,
                 nodeHierarchy=None, hierarchyRules=None, planner=None):

@@ -39,6 +39,34 @@ typedef struct blance_batch_info {
 int blance_plan_batch(blance_ctx* ctx, int32_t n, const blance_problem* const* pbs,
                       blance_result* const* res, blance_batch_info* info /* may be NULL */);
 
+/* ---- the same batch, and the partition moves of each plan --------------------
+ * For every problem i with mvs[i] != NULL, mvs[i]->out receives what blance_calc_moves would return for
+ * CalcPartitionMoves(sortStateNames(model), prevMap[name].NodesByState, nextMap[name].NodesByState,
+ * favor_min_nodes) over the partitions of partitionsToAssign in partition id order (orchestrate.go:273-287):
+ * prevMap as the call passes it (before the write-back of plan.go:49-52), nextMap the plan's result, node ids in
+ * the problem's own id space.  Batched problems get theirs from k_batch_moves in the same call (one launch after
+ * the plan launches, moves in the same download); every other problem from the path of blance_calc_moves.
+ * Every request is checked with its problem before anything runs (null arrays, CSR offsets that do not start at 0
+ * or are not monotone, other-node ids outside [0, n_nodes_ext), a capacity below blance_batch_moves_capacity(),
+ * max_iterations <= 0: PlanNextMapEx returns no map there): a refusal names the problem's index and writes no
+ * result and no moves.  mvs == NULL is exactly blance_plan_batch.  out.device_ms is the batch's. */
+typedef struct blance_batch_moves {
+    int32_t favor_min_nodes;          /* in */
+    /* in, may both be NULL: prevMap[name]'s nodes under state keys that are not in the model, CSR over partitions
+     * ([P + 1], ids < n_nodes_ext).  They only feed flattenNodesByState (moves.go:60-64), like blance_moves_problem's
+     * pseudo state M; partitionsToAssign never has such keys, so the result never has them. */
+    const int32_t* beg_other_off;
+    const int32_t* beg_other_nodes;
+    blance_moves_result out;          /* op_off [P + 1], op_node / op_state / op_kind [capacity]; device_ms = the batch's */
+} blance_batch_moves;
+
+/* prev_off[P*M] + beg_other_off[P] + blance_result_capacity(pb): enough for every partition's moves */
+int64_t blance_batch_moves_capacity(const blance_problem* pb, const blance_batch_moves* mv);
+
+int blance_plan_batch_moves(blance_ctx* ctx, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                            blance_batch_moves* const* mvs /* mvs[i] may be NULL: no moves for problem i */,
+                            blance_batch_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
