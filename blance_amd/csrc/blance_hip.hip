@@ -255,6 +255,7 @@ struct blance_ctx {
     bool assign_empty = false, counts_start_zero = false;
     int chain_waves = 0;                     // k_pass_chain's workgroup: 0 = 8 waves when the LDS is there, else 4 (BLANCE_CHAIN_WAVES=4|8)
     int speculate = 1;                       // host decisions taken before their words are read back (BLANCE_SPECULATE=0|1|fail)
+    bool fused_tail = true;                  // a sweep ends with k_sweep_tail instead of k_scatter + k_converge (BLANCE_FUSED_TAIL=0: off)
     int64_t spec_refuted = 0;                // ... and how often one had to be taken back
 
     // host copy of the small parts of the problem
@@ -294,6 +295,7 @@ struct blance_ctx {
     };
     std::vector<RuleRegions> rule_regions;
     DevBuf leaf_node, regid, chain_order, bucket_counts, reg_off, cnt_save, crec;
+    DevBuf chain_inv;               // chain_inv[p]: p's place in chain_order (k_invert, with every regrouping)
     DevBuf period, cnt_p1;          // k_period.h: per-region period tables, the counters after the first period
     DevBuf fl_iota, fl_zero, fl_one, fl_reglo, fl_reghi;   // the whole cluster as one region (flat single chain)
     DevBuf n_ev, chain_oi, ev_key, ev_oi, ev_leaf, ev_w, ev_perm, ev_off, ev_counts;   // chain events
@@ -314,6 +316,8 @@ struct blance_ctx {
     // device: working state
     DevBuf live, live_len, live_kind, prv, prv_len, prv_kind, in_prev, never_equal;
     DevBuf cnt, ntn, cat, order, chunk_counts, rec, out, warn_part, warn_state, scalars;
+    DevBuf cnt_next;                // stateNodeCounts of the next sweep, counted by this sweep's k_sweep_tail (swapped with cnt)
+    bool tail_counted = false;      // the last sweep's k_sweep_tail counted cnt_next and refreshed the kinds (plan.go:94, 418)
     // scalars: [0] warn_count, [1] not_match, [2] err
     int32_t iterations = 0, converged = 0;
     int64_t n_warnings = 0, steps_total = 0, kernel_launches = 0, pass_launches = 0;
@@ -331,7 +335,7 @@ struct blance_ctx {
                          &vparent, &vlo, &vhi, &anchors, &state_stick, &state_has_stick, &live,
                          &live_len, &live_kind, &prv, &prv_len, &prv_kind, &in_prev, &never_equal,
                          &cnt, &ntn, &cat, &order, &chunk_counts, &rec, &out, &warn_part,
-                         &warn_state, &scalars};
+                         &warn_state, &scalars, &cnt_next};
         for (DevBuf* b : all) b->release();
         for (auto& rr : rule_regions) { rr.node_region.release(); rr.reg_lo.release(); rr.reg_hi.release(); rr.leaf_cls.release(); rr.cls_size.release(); rr.wg_region.release(); rr.wg_chunk.release(); }
         rule_regions.clear();
@@ -343,7 +347,7 @@ struct blance_ctx {
         if (rb_buf) pin_free(rb_buf);
         rb_buf = nullptr;
         for (DevBuf& b : mv) b.release();
-        DevBuf* more[] = {&leaf_node, &regid, &chain_order, &bucket_counts, &reg_off, &cnt_save, &crec, &period, &cnt_p1, &n_ev, &chain_oi,
+        DevBuf* more[] = {&leaf_node, &regid, &chain_order, &chain_inv, &bucket_counts, &reg_off, &cnt_save, &crec, &period, &cnt_p1, &n_ev, &chain_oi,
                           &ev_key, &ev_oi, &ev_leaf, &ev_w, &ev_perm, &ev_off, &ev_counts, &fl_iota, &fl_zero,
                           &fl_one, &fl_reglo, &fl_reghi, &f_tot, &f_g,
                           &f_top_g, &f_top_n, &f_row_count, &f_m, &f_moff, &f_keys_a, &f_keys_b, &f_vals_a,
@@ -545,6 +549,7 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     c->trace = getenv("BLANCE_TRACE") != nullptr;
     if (const char* cw = getenv("BLANCE_CHAIN_WAVES")) c->chain_waves = atoi(cw);
     if (const char* sp = getenv("BLANCE_SPECULATE")) c->speculate = !strcmp(sp, "fail") ? 2 : atoi(sp) != 0;   // 0: every decision read back first
+    if (const char* ft = getenv("BLANCE_FUSED_TAIL")) c->fused_tail = atoi(ft) != 0;      // BLANCE_FUSED_TAIL=0: the unfused tail
     if (const char* ds = getenv("BLANCE_DUMP_SWEEP")) c->dump_sweep = atoi(ds);
     if (hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
         hipEventCreate(&c->ev1) != hipSuccess ||
@@ -708,12 +713,15 @@ struct FillCopyJob {
     FillCopy a{};
     int nz = 0;
     int64_t most = 0;
+    bool over = false;              // more zero fills than kFillZeros, or a range past INT32_MAX words: run_fill_copy refuses
     void zero(void* p, int64_t words) {
         if (words <= 0) return;
+        if (nz == kFillZeros || words > INT32_MAX) { over = true; return; }
         a.z[nz] = (int32_t*)p; a.zn[nz] = (int32_t)words; nz++;
         if (words > most) most = words;
     }
     void copy(void* dst, const void* src, int64_t words) {
+        if (words > INT32_MAX) { over = true; return; }
         a.cd = (int32_t*)dst; a.cs = (const int32_t*)src; a.cn = (int32_t)words;
         if (words > most) most = words;
     }
@@ -721,6 +729,7 @@ struct FillCopyJob {
 static int run_fill_copy(blance_ctx* c, FillCopyJob& j);
 
 static int run_fill_copy(blance_ctx* c, FillCopyJob& j) {
+    if (j.over) return fail(BLANCE_ERR_DEVICE, "k_fill_copy job over its slots");
     if (j.most > 0) BLANCE_LAUNCH_NOSYNC(k_fill_copy, cdiv(j.most, 256), 256, 0, c->stream, j.a);
     return 0;
 }
@@ -1000,6 +1009,7 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     RESERVE(in_prev, (size_t)P + 1);
     RESERVE(never_equal, (size_t)P + 1);
     RESERVE(cnt, sizeof(int32_t) * (size_t)(M + 1) * (NX + 1));
+    RESERVE(cnt_next, sizeof(int32_t) * (size_t)(M + 1) * (NX + 1));
     RESERVE(ntn, sizeof(int32_t) * (size_t)(NX + 1) * (N > 0 ? N : 1));
     RESERVE(cat, (size_t)P + 1);
     RESERVE(order, sizeof(int32_t) * ((size_t)P + 1));
@@ -1015,6 +1025,7 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
         for (auto& rr : c->rule_regions) if (rr.ok && rr.n_regions > maxB) maxB = rr.n_regions;
         RESERVE(regid, sizeof(int32_t) * ((size_t)P + 1));
         RESERVE(chain_order, sizeof(int32_t) * ((size_t)P + 1));
+        RESERVE(chain_inv, sizeof(int32_t) * ((size_t)P + 1));
         RESERVE(bucket_counts, sizeof(int32_t) * ((size_t)maxB * (cdiv(P, kPartChunk) + 1) + 1));
         RESERVE(reg_off, sizeof(int32_t) * ((size_t)maxB + 2));
         RESERVE(cnt_save, sizeof(int32_t) * (size_t)(M + 1) * (NX + 1));
@@ -1697,6 +1708,15 @@ static int comm_allgather(blance_ctx* c, int32_t* buf, int64_t per_rank) {
 }
 #define COMMTRY(expr) do { int e__ = (expr); if (e__) return e__; } while (0)
 
+static DevProblem dev_problem(blance_ctx* c);
+// The planned map, for the readers after a plan: prevMap as the last sweep wrote it back (k_converge / k_sweep_tail).  It is
+// the live lists as planned, but for their kinds: k_sweep_tail has already made the live ones the next sweep's (plan.go:418).
+static DevProblem result_problem(blance_ctx* c) {
+    DevProblem d = dev_problem(c);
+    d.live = d.prv; d.live_len = d.prv_len; d.live_kind = d.prv_kind;
+    return d;
+}
+
 static DevProblem dev_problem(blance_ctx* c) {
     const blance_problem& h = c->h;
     DevProblem d;
@@ -1716,11 +1736,22 @@ static DevProblem dev_problem(blance_ctx* c) {
 // Header of the buffer the ranks of a sharded plan sum up after such a pass (collective A):
 // [0..7] the chain kernels' flags, [8] poison (a rank failed), then the load-vector change.
 constexpr int kXHead = 16;
+// The sweep's last pass hands its list edits (k_scatter's arguments) to the sweep's tail, k_sweep_tail, instead of launching
+// them: plan_locked launches the tail after the pass.  scatter = false: the pass changed no list (run_flat_pass's
+// nothing_to_apply).  inv: the inverse of `order` (k_sweep_tail goes by partition), or null -- then k_scatter runs first.
+struct SweepTail {
+    bool set = false, scatter = false;
+    int m = 0, OW = 0;
+    const int32_t* order = nullptr;
+    const int32_t* inv = nullptr;
+    Gate gate = kNoGate;
+};
 struct ChainPassArgs {
     DevProblem d;
     int m, k, NP, OW, RW, higher_mask, r0, it;
     const int32_t* order;          // the pass order: the stable partition of sweep 1, the static order itself afterwards
     bool same_tops;                // no partition has changed its top priority node since this state's last chain pass
+    SweepTail* tail;               // non-null: the sweep's last pass, its k_scatter goes to the sweep's tail
 };
 
 // this rank failed before collective A of a sharded chain pass: take part in it with the poison word set
@@ -1794,6 +1825,8 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
         BLANCE_LAUNCH(k_part_scatter, nbc, 64, sizeof(int32_t) * B + 64, sm, P, c->regid.as<int32_t>(),
                       (const uint8_t*)nullptr, (const int32_t*)nullptr, a.order, nbc, B, nbits,
                       c->bucket_counts.as<int32_t>(), c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>());
+        BLANCE_LAUNCH_NOSYNC(k_invert, cdiv(P, 256), 256, 0, sm, P, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>());
+        launches++;
         c->chain_group_state = m;
         c->group_epoch++;
         c->chain_group_static = a.order == c->part_order.as<int32_t>();
@@ -2004,9 +2037,14 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
         n_pass++;
         c->last_stays[m] = P;
         if (dump_pass(c, a.it, m, P, OW, c->chain_oi.as<int32_t>())) return BLANCE_ERR_DEVICE;
-        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(),
-                             run.pending ? run.gate : kNoGate);
-        launches++;
+        if (a.tail) {
+            *a.tail = SweepTail{true, true, m, OW, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>(),
+                                run.pending ? run.gate : kNoGate};
+        } else {
+            BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(),
+                                 run.pending ? run.gate : kNoGate);
+            launches++;
+        }
         *batched_io += P;
         *done = true;
         *launches_io += launches;
@@ -2179,9 +2217,14 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
             }
         }
         if (dump_pass(c, a.it, m, P, OW, c->chain_oi.as<int32_t>())) return BLANCE_ERR_DEVICE;
-        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(),
-                             run.pending ? run.gate : kNoGate);
-        launches++;
+        if (a.tail) {
+            *a.tail = SweepTail{true, true, m, OW, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>(),
+                                run.pending ? run.gate : kNoGate};
+        } else {
+            BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(),
+                                 run.pending ? run.gate : kNoGate);
+            launches++;
+        }
         *batched_io += P;
         *done = true;
     } else {                                        // not region-local after all: redo in order
@@ -2222,8 +2265,12 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
     c->chain_group_state = -1;
     c->group_epoch++;
     c->top_group_state = -1;
+    c->tail_counted = false;
     if (c->side_pending) { HIPTRY(hipStreamSynchronize(c->side)); c->side_pending = false; }
     const int64_t syncs0 = c->n_syncs;
+    // Each sweep ends with k_sweep_tail (the last pass's list edits, the convergence test and write-back, and the next
+    // sweep's counters and kinds) -- not on a sharded plan, whose ranks scatter the pass's gathered outputs one by one.
+    const bool fuse = c->fused_tail && !(c->comm.n_ranks > 1 || c->shard_one_rank);
 
     HIPTRY(hipEventRecord(c->ev0, sm));
     HIPTRY(hipMemsetAsync(scal, 0, 256, sm));
@@ -2249,17 +2296,23 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
         const int any_removed = first ? c->any_removed : 0;
         const int NP = first ? h.n_prev : c->np_later;
         c->tops_moved = true;                                       // until this sweep's top-state pass turns out to be one run of stays
-        {   // one launch: warn_count / not_match, the chain flags, stateNodeCounts (plan.go:94), the flat passes' row counts
+        // the last sweep's k_sweep_tail counted this sweep's prevMap into cnt_next and made every present list a non-nil slice
+        const bool opened = c->tail_counted;
+        c->tail_counted = false;
+        if (opened) std::swap(c->cnt, c->cnt_next);
+        {   // one launch: warn_count / not_match, the chain flags, stateNodeCounts (plan.go:94) unless counted already, the flat
+            // passes' row counts, and the counters this sweep's tail counts the next sweep's into
             FillCopyJob fj;
             fj.zero(scal, 2);
             fj.zero(scal + 4, 8);
-            fj.zero(c->cnt.p, (int64_t)(M + 1) * (NX + 1));
+            if (!opened) fj.zero(c->cnt.p, (int64_t)(M + 1) * (NX + 1));
             if (NP > 0 && c->f_row_count.p) fj.zero(c->f_row_count.p, (int64_t)NX + 1);
+            if (fuse) fj.zero(c->cnt_next.p, (int64_t)(M + 1) * (NX + 1));
             if (run_fill_copy(c, fj)) return BLANCE_ERR_DEVICE;
             c->flags_clean = true;
             c->rowcount_clean = NP > 0 && c->f_row_count.p;
         }
-        if (PM > 0) {
+        if (PM > 0 && !opened) {
             if (first)
                 BLANCE_LAUNCH_NOSYNC(k_live_init, cdiv(PM, 256), 256, 0, sm, d, c->a_off.as<int32_t>(),
                                      c->a_nodes.as<int32_t>(), c->a_kind.as<uint8_t>(), c->p_off.as<int32_t>(),
@@ -2275,7 +2328,7 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
                                  c->load_weight.as<int32_t>(), c->load_first.as<uint8_t>(), c->cnt.as<int32_t>());
             launches++;
         }
-        if (PM > 0) {
+        if (PM > 0 && !opened) {
             BLANCE_LAUNCH_NOSYNC(k_count_prev, cdiv(PM, 256), 256, 0, sm, d, c->cnt.as<int32_t>());
             launches++;
         }
@@ -2294,6 +2347,7 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
         // every later pass of the sweep keeps its own verdict on the device as well (top_spec_fits), so that nothing of the
         // sweep is read before its one readback.
         bool top_spec_off = false;
+        bool tail_counts = false;                                    // (this round of the loop below ended with a counting tail)
         const int64_t batched_sw = batched, steps_sw = steps;
         const int n_pass_sw = n_pass;
         std::vector<int64_t> last_stays_sw;
@@ -2317,6 +2371,8 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
         };
         for (;;) {
         ChainRun pend;
+        SweepTail tail;
+        tail_counts = false;
         c->top_gate = 0;
         int64_t batched0 = batched, steps0 = steps;
         int n_pass0 = n_pass, passes0 = passes_this_sweep;
@@ -2361,7 +2417,8 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
                 // (same_tops: the top state's pass was one run of stays AND no other state can take a partition's top priority
                 // node away in between -- plan.go:146-154 keeps only nodes of STRICTLY higher priority states out of a pass)
                 ChainPassArgs ca{d, m, k, NP, OW, RW, higher_mask, r0, it, order,
-                                 !first && !c->tops_moved && m != h.top_state && c->top_prio_strict};
+                                 !first && !c->tops_moved && m != h.top_state && c->top_prio_strict,
+                                 fuse && m == m_last ? &tail : nullptr};
                 bool a_done = false;
                 ChainRun run;
                 if (retrying) run = retry;
@@ -2465,7 +2522,9 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
             HIPTRY(hipEventRecord(c->pass_events[2 * n_pass + 1], sm));
             n_pass++;
             if (dump_pass(c, it, m, P, q.OW, nullptr)) return BLANCE_ERR_DEVICE;
-            if (!nothing_to_apply)
+            if (fuse && m == m_last)
+                tail = SweepTail{true, !nothing_to_apply, m, q.OW, order, nullptr, kNoGate};
+            else if (!nothing_to_apply)
                 BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, q.OW, order, c->out.as<int32_t>(), kNoGate);
             }
             launches += 7;
@@ -2475,8 +2534,24 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
         counted = true;
         // convergence (plan.go:36-45) + write-back (plan.go:49-52)
         if (P > 0) {
-            BLANCE_LAUNCH(k_converge, cdiv(P, 256), 256, 0, sm, d, scal + 1,
-                          pend.pending ? pend.gate : c->top_gate ? Gate{scal + 4, c->top_gate} : kNoGate);   // (uses a wave ballot)
+            const Gate cg = pend.pending ? pend.gate : c->top_gate ? Gate{scal + 4, c->top_gate} : kNoGate;
+            if (tail.set && tail.scatter && (!tail.inv || tail.gate.flags != cg.flags || tail.gate.mask != cg.mask)) {
+                // (no inverse of the pass order -- a flat pass --, or the list edits wait for other words than the convergence
+                // test: on their own, as before)
+                BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.order, c->out.as<int32_t>(), tail.gate);
+                launches++;
+                tail.scatter = false;
+            }
+            if (tail.set) {
+                // the sweep's tail: the list edits, the convergence test and write-back, and -- when another sweep may follow --
+                // that sweep's counters and kinds, in one pass over the partitions
+                int32_t* next = it + 1 < h.max_iterations ? c->cnt_next.as<int32_t>() : nullptr;
+                BLANCE_LAUNCH(k_sweep_tail, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.scatter ? tail.inv : nullptr,
+                              tail.scatter ? c->out.as<int32_t>() : nullptr, scal + 1, next, cg);   // (uses a wave ballot)
+                tail_counts = next != nullptr;
+            } else {
+                BLANCE_LAUNCH(k_converge, cdiv(P, 256), 256, 0, sm, d, scal + 1, cg);   // (uses a wave ballot)
+            }
             launches++;
         }
         // one readback per sweep: the convergence word with the warnings count, the chain flags (a deferred verdict) and --
@@ -2539,6 +2614,7 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
             m_from = m_last;
         }
         }
+        c->tail_counted = tail_counts;                              // (the tail that stood: a closed gate's wrote nothing)
         if (hs[2]) return fail(BLANCE_ERR_UNSUPPORTED, "hierarchy fold overflowed the device's interval budget");
         c->n_warnings = hs[0];
         if (!hs[1]) { converged = 1; break; }
@@ -2638,7 +2714,7 @@ static int download_locked(blance_ctx* c, blance_result* res) {
     if (PM) {
         // the CSR is made on the device (lengths -> exclusive scan -> gather) and lands in the caller's arrays: directly when
         // they are page-locked, through the staging buffer otherwise
-        DevProblem d = dev_problem(c);
+        DevProblem d = result_problem(c);
         RESERVE(dl_off, sizeof(int32_t) * (PM + 2));
         BLANCE_LAUNCH_NOSYNC(k_result_len, cdiv((int64_t)PM + 1, 256), 256, 0, c->stream, d, c->dl_off.as<int32_t>());
         SCANTRY((int)PM + 1, c->dl_off.as<int32_t>());
@@ -2651,7 +2727,7 @@ static int download_locked(blance_ctx* c, blance_result* res) {
                              c->dl_nodes.as<int32_t>());
         if ((e = down.copy(res->out_off, c->dl_off.p, sizeof(int32_t) * (PM + 1)))) return e;
         if (total && (e = down.copy(res->out_nodes, c->dl_nodes.p, sizeof(int32_t) * (size_t)total))) return e;
-        if ((e = down.copy(res->out_kind, c->live_kind.p, PM))) return e;
+        if ((e = down.copy(res->out_kind, c->prv_kind.p, PM))) return e;
     }
     if (c->n_warnings) {
         if ((e = down.copy(res->warn_part, c->warn_part.p, sizeof(int32_t) * (size_t)c->n_warnings))) return e;
@@ -2796,7 +2872,7 @@ extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
         HIPTRY(hipMemsetAsync(load.p, 0, sizeof(int32_t) * (size_t)M * (NX > 0 ? NX : 1), sm));
         HIPTRY(hipMemsetAsync(unmet.p, 0, sizeof(long long) * 2 * (size_t)M, sm));
         HIPTRY(hipMemcpyAsync(cons.p, c->state_constraints.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, sm));
-        DevProblem d = dev_problem(c);
+        DevProblem d = result_problem(c);
         if ((int64_t)P * M > 0)
             BLANCE_LAUNCH_NOSYNC(k_stats_load, cdiv((int64_t)P * M, 256), 256, 0, sm, d, load.as<int32_t>(), cons.as<int32_t>(),
                                  unmet.as<unsigned long long>());

@@ -500,9 +500,10 @@ __global__ void k_vec_add(int n, const int32_t* a, const int32_t* b, int32_t* ou
 
 // Several small fills and one copy in ONE launch: the driver used to enqueue each as a hipMemsetAsync / hipMemcpyAsync of its
 // own (a fill kernel of the runtime per call, 25 of them per PlanNextMap at config 3).  All int32 words.
+constexpr int kFillZeros = 5;
 struct FillCopy {
-    int32_t* z[4];          // zero z[i][0 .. zn[i])
-    int32_t zn[4];
+    int32_t* z[kFillZeros]; // zero z[i][0 .. zn[i])
+    int32_t zn[kFillZeros];
     int32_t* cd;            // cd[0 .. cn) = cs[0 .. cn)
     const int32_t* cs;
     int32_t cn;
@@ -510,7 +511,7 @@ struct FillCopy {
 __global__ void k_fill_copy(FillCopy a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
 #pragma unroll
-    for (int j = 0; j < 4; j++) if (i < a.zn[j]) a.z[j][i] = 0;
+    for (int j = 0; j < kFillZeros; j++) if (i < a.zn[j]) a.z[j][i] = 0;
     if (i < a.cn) a.cd[i] = a.cs[i];
 }
 
@@ -608,14 +609,9 @@ __global__ __launch_bounds__(256) void k_ntn_bits(int N, int rows, int BW, const
     }
 }
 
-// Apply the pass's choices to the live lists (plan.go:290-299); list edits only
-// touch the step's own partition, so this runs in parallel after the pass.
-__global__ void k_scatter(DevProblem d, int m, int OW, const int32_t* order, const int32_t* out, Gate gate) {
-    int oi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (oi >= d.P) return;
-    if (gate_closed(gate)) return;                   // (the pass did not stand: the host runs it again and scatters then)
-    int p = order[oi];
-    const int32_t* o = out + (size_t)oi * OW;
+// Apply one step's choices to its partition's live lists (plan.go:290-299); list edits only touch the step's own partition,
+// so this runs in parallel after the pass.
+__device__ __forceinline__ void scatter_lists(const DevProblem& d, int m, int p, const int32_t* o) {
     int n_out = o[0] & 0xffff, is_nil = o[0] >> 16;
     // the partition's list in this state as the pass saw it: the pass itself only wrote `out`
     const int idx_m = p * d.M + m;
@@ -644,15 +640,18 @@ __global__ void k_scatter(DevProblem d, int m, int OW, const int32_t* order, con
     d.live_kind[idx] = is_nil ? kListNil : kListSet;
 }
 
-// Convergence test (plan.go:36-45) fused with the write-back prevMap[name] =
-// partitionsToAssign[name] = nextMap[name] (plan.go:49-52).
-__global__ void k_converge(DevProblem d, int32_t* not_match, Gate gate) {
-    if (gate_closed(gate)) return;                   // (uniform: the sweep's last pass did not stand, the host comes back)
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool in_range = p < d.P;
-    if (!in_range) p = d.P - 1;                      // keep the wave whole for the ballot below
+__global__ void k_scatter(DevProblem d, int m, int OW, const int32_t* order, const int32_t* out, Gate gate) {
+    int oi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (oi >= d.P) return;
+    if (gate_closed(gate)) return;                   // (the pass did not stand: the host runs it again and scatters then)
+    scatter_lists(d, m, order[oi], out + (size_t)oi * OW);
+}
+
+// Convergence test (plan.go:36-45) fused with the write-back prevMap[name] = partitionsToAssign[name] = nextMap[name]
+// (plan.go:49-52), for one partition: true when its lists differ from prevMap's.
+__device__ __forceinline__ bool converge_lists(const DevProblem& d, int p) {
     bool diff = !d.in_prev[p] || d.never_equal[p];
-    for (int m = 0; m < d.M && in_range; m++) {
+    for (int m = 0; m < d.M; m++) {
         int idx = p * d.M + m;
         int len = d.live_len[idx];
         if (d.live_kind[idx] != d.prv_kind[idx] || len != d.prv_len[idx]) diff = true;
@@ -664,14 +663,59 @@ __global__ void k_converge(DevProblem d, int32_t* not_match, Gate gate) {
         d.prv_len[idx] = len;
         d.prv_kind[idx] = d.live_kind[idx];
     }
-    if (in_range) {
-        d.in_prev[p] = 1;
-        d.never_equal[p] = 0;
-    }
-    // one word for the whole sweep: one atomic per wave, and none once it is set (in a first sweep
-    // every partition differs)
-    const unsigned long long dm = __ballot(in_range && diff);
+    d.in_prev[p] = 1;
+    d.never_equal[p] = 0;
+    return diff;
+}
+
+// one word for the whole sweep: one atomic per wave, and none once it is set (in a first sweep every partition differs).
+// Every lane of the wave calls this.
+__device__ __forceinline__ void publish_not_match(bool diff, int32_t* not_match) {
+    const unsigned long long dm = __ballot(diff);
     if (dm && (int)(threadIdx.x & 63) == __ffsll((long long)dm) - 1 && *(volatile int32_t*)not_match == 0) atomicOr(not_match, 1);
+}
+
+__global__ void k_converge(DevProblem d, int32_t* not_match, Gate gate) {
+    if (gate_closed(gate)) return;                   // (uniform: the sweep's last pass did not stand, the host comes back)
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool diff = p < d.P && converge_lists(d, p);     // (out-of-range lanes stay for the ballot)
+    publish_not_match(diff, not_match);
+}
+
+// inv[perm[i]] = i: where each partition's step is in a pass order (perm: a permutation of 0 .. n - 1)
+__global__ void k_invert(int n, const int32_t* perm, int32_t* inv) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) inv[perm[i]] = i;
+}
+
+// The sweep's tail in one pass over the partitions (DESIGN.md 4.5 "The sweep's tail"): the last pass's list edits
+// (k_scatter; out == nullptr: that pass changed no list, or they were applied already), the convergence test and
+// write-back (k_converge), and, when another sweep may follow (cnt_next != nullptr), that sweep's opening while the lists
+// are in registers: stateNodeCounts of the new prevMap (k_count_prev: every partition is in prevMap now) into the second
+// counter buffer, which the host zeroed at this sweep's start and swaps in at the next, and every present list made a
+// non-nil slice (k_live_refresh, plan.go:418) -- after prv_kind took the kind as planned, so prv / prv_kind hold the
+// result.  Behind the same Gate the two kernels had: closed, nothing at all is written.  Thread p takes partition p, so
+// every per-partition array streams; only the step's output is looked up, at its place inv[p] in the pass order (a
+// thread per step in pass order made every one of those arrays a random access: 69 us instead of 55 for the three
+// kernels at config 3).
+__global__ void k_sweep_tail(DevProblem d, int m, int OW, const int32_t* inv, const int32_t* out, int32_t* not_match,
+                             int32_t* cnt_next, Gate gate) {
+    if (gate_closed(gate)) return;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    bool diff = false;
+    if (p < d.P) {                                   // (out-of-range lanes stay for the ballot)
+        if (out) scatter_lists(d, m, p, out + (size_t)inv[p] * OW);
+        diff = converge_lists(d, p);
+        if (cnt_next) {
+            const int w = (!d.weights_nil && d.part_has_weight[p]) ? d.part_weight[p] : 1;
+            for (int t = 0; t < d.M; t++) {
+                const int idx = p * d.M + t;
+                for (int i = 0; i < d.prv_len[idx]; i++) atomicAdd(&cnt_next[t * d.NX + d.live[(size_t)idx * d.L + i]], w);
+                if (d.live_kind[idx] != kListAbsent) d.live_kind[idx] = kListSet;
+            }
+        }
+    }
+    publish_not_match(diff, not_match);
 }
 
 
