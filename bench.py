@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the PlanNextMap hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|2|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|2|5] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the problem, uploads it, warms up, times the
+steps, writes the result if --dump-outputs is given and prints the line (value, ms_per_step, the roofline figures that follow
+from the timed steps' own event timings).  Everything else this file measures or checks -- the CPU baselines, the other
+configurations and regimes, the digest against the oracle's, the transfers, the live PMC passes, the RCCL and replica
+legs -- runs with --full only, and is described below as part of that line.
 
 One "step" = one whole PlanNextMap call (every sweep of planNextMapEx, plan.go:23-58) on
 BASELINE.json's config 3: 1,048,576 partitions x 4,096 nodes, primary + 2 replicas, 3-level
@@ -16,7 +22,7 @@ when it is not already running under it):
   * "sharded": ONE plan with its region chains sharded over the ranks -- per chain pass one RCCL sum
     all-reduce of [flags | load-vector change] and one all-gather of the output slices (BASELINE.json
     config 4) -- timed the same way and reported beside it, whatever it is (DESIGN.md "Multi-GPU").
-N = 1 also reports "sharded_on_one_gpu": the same sharded plan with 8 ranks as 8 contexts of this one
+N = 1 with --full also reports "sharded_on_one_gpu": the same sharded plan with 8 ranks as 8 contexts of this one
 device (collectives staged through the host) -- it proves the path on real kernels, it is not a speed --
 "general_regime": config 3's size in its general regime (a rebalance after every tenth node left; scrambled
 non-numeric partition names + Zipf partition weights), each checked against the oracle's digest -- and
@@ -178,7 +184,7 @@ def live_pmc(args):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             cmd = [exe, "--kernel-trace", "--pmc", counter, "-d", os.path.join(work, counter), "-o", "p", "--",
                    sys.executable, os.path.abspath(__file__), "--config", str(args.config), "--steps", "1", "--warmup", "0",
-                   "--no-cpu-baseline", "--no-sharded", "--no-extra", "--no-live-pmc", "--no-other-configs", "--no-transfers",
+                   "--full", "--no-cpu-baseline", "--no-sharded", "--no-extra", "--no-live-pmc", "--no-other-configs", "--no-transfers",
                    "--no-replicas", "--no-rccl-one-rank"]
             if args.parts:
                 cmd += ["--parts", str(args.parts)]
@@ -566,6 +572,10 @@ def main():
     ap.add_argument("--config", type=int, default=3, help="BASELINE.json config: 3 (headline), 2, or 5 (weighted rebalance)")
     ap.add_argument("--parts", type=int, default=0, help="override partition count (not the headline)")
     ap.add_argument("--nodes", type=int, default=0, help="override node count (not the headline)")
+    ap.add_argument("--full", action="store_true", help="beside the headline, run every other block of the line: the result's digest "
+                    "against the oracle's, transfers, live PMC traffic, cpu_baseline, other_configs, general_regime, rccl_one_rank, "
+                    "replicas_on_one_gpu, sharded_on_one_gpu, host_end_to_end (minutes; each has a --no-... option).  Without it a run "
+                    "sets up, warms up, times the steps and prints the headline line, and the --no-... options have nothing to skip")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sharded", action="store_true", help="skip the 8-contexts-on-one-GPU leg of N = 1")
     ap.add_argument("--no-periodic", action="store_true", help="the all-blank chain pass without its periodic form (blance_amd/csrc/"
@@ -687,10 +697,14 @@ def main():
     assignments = synth.assignments(fp)
     value = assignments * args.steps * world / dt
 
-    t1 = time.perf_counter()
-    res = pl.download()                             # (every rank: the sharded leg compares with it)
-    download_s = time.perf_counter() - t1
-    digest_all = res.digest()
+    # the result comes back to the host only where something reads it: --dump-outputs, the checks of --full, and N > 1
+    # (every rank: the sharded leg compares with it)
+    res, download_s, digest_all = None, None, None
+    if args.full or args.dump_outputs or world > 1:
+        t1 = time.perf_counter()
+        res = pl.download()
+        download_s = time.perf_counter() - t1
+        digest_all = res.digest()
     dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     replicas_ok = None
     if dist is not None:
@@ -702,7 +716,7 @@ def main():
     # through the context's page-locked buffer by a few threads) and arrays from blance_host_alloc (DMA where they lie)
     xfer = None
     t_x = time.perf_counter()
-    if rank == 0 and not rehearsal and not args.no_transfers:
+    if rank == 0 and not rehearsal and args.full and not args.no_transfers:
         try:
             def again(f, arena):
                 r_ = None
@@ -735,7 +749,8 @@ def main():
             arena.close()
         except Exception as e:
             xfer = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-    T_BLOCKS["transfers"] = round(time.perf_counter() - t_x, 2)
+    if args.full:
+        T_BLOCKS["transfers"] = round(time.perf_counter() - t_x, 2)
     out = None
     if rank == 0:
         digest = digest_all
@@ -749,8 +764,8 @@ def main():
         headline_shape = not args.parts and not args.nodes
         # HBM traffic per kernel: measured in this run when rocprofv3 is here (N = 1, not the rehearsal), else quoted from a
         # committed profile of EXACTLY these kernel sources (hash checked, no exceptions), else null
-        hbm, hbm_src = None, "not measured (--no-live-pmc)"
-        if world == 1 and not rehearsal and not args.no_live_pmc:
+        hbm, hbm_src = None, "not measured (--no-live-pmc)" if args.full else "not measured (a run with --full measures it)"
+        if world == 1 and not rehearsal and args.full and not args.no_live_pmc:
             t_p = time.perf_counter()
             hbm, hbm_src = live_pmc(args)
             T_BLOCKS["live_pmc"] = round(time.perf_counter() - t_p, 2)
@@ -896,19 +911,20 @@ def main():
             # launched next; VERDICT r5 item 4 asked for <= 4 -- it is what it was
             "host_syncs_per_call": int(r.host_syncs),
             "pass_kernel_ms_per_step": acc["pass_ms"] / args.steps, "flat_pass_ms_per_step": acc["flat_ms"] / args.steps,
-            "transfers": dict(xfer or {}, **{
+        }
+        if res is not None:                             # (a plain run without --dump-outputs leaves the result on the device)
+            out["transfers"] = dict(xfer or {}, **{
                 "first_upload_s": upload_s, "first_download_s": download_s,
                 "first_call_note": "the first upload allocates every device buffer, the first download the result arrays: one-time costs",
                 "value_incl_transfers": (assignments / (dt / args.steps + xfer["page_locked"]["upload_s"] + xfer["page_locked"]["download_s"])
                                          if xfer and "page_locked" in xfer else assignments / (dt / args.steps + upload_s + download_s)),
                 "value_incl_transfers_pageable": (assignments / (dt / args.steps + xfer["pageable"]["upload_s"] + xfer["pageable"]["download_s"])
-                                                  if xfer and "pageable" in xfer else None)}),
-            "result_sha256": digest,
-        }
+                                                  if xfer and "pageable" in xfer else None)})
+            out["result_sha256"] = digest
         if dumped:
             out["outputs_dumped"] = dumped
         ref = os.path.join(ROOT, "tests", "golden", "config_digests.json")
-        if os.path.exists(ref) and headline_shape:
+        if args.full and os.path.exists(ref) and headline_shape:
             with open(ref) as f:
                 want = json.load(f).get("config%d" % args.config)
             if want:
@@ -925,16 +941,17 @@ def main():
             r_ = fn()
             blocks[name] = round(time.perf_counter() - t_, 2)
             return r_
-        if world == 1:
+        side = world == 1 and args.full                 # the blocks beside the headline run with --full only
+        if side:
             out["sharded"] = ("see sharded_on_one_gpu; N > 1 runs report the RCCL plan here" if args.config == 3 else
                               "not applicable: flat passes are one chain (DESIGN.md 7); only config 3's region chains shard")
-        if world == 1 and not args.no_cpu_baseline:
+        if side and not args.no_cpu_baseline:
             out["cpu_baseline"] = timed_block("cpu_baseline", lambda: cpu_baseline(
                 args.parts or (1 << 20) if args.config == 5 else P, N, args.config, full=not args.cpu_sample), optional=False)
             if args.config != 3:
                 pl.upload(fp)                           # (config 5's sample planned another problem on this context)
         fp5 = [None]
-        if world == 1 and args.config == 3 and headline_shape and not args.no_other_configs and not rehearsal:
+        if side and args.config == 3 and headline_shape and not args.no_other_configs and not rehearsal:
             out["other_configs"] = timed_block("other_configs", lambda: other_configs(
                 pl, max(1, min(args.steps, 5)), cpu=not args.no_cpu_baseline, keep=fp5), optional=False)
             pl.upload(fp)                               # (what follows plans the headline problem)
@@ -942,12 +959,12 @@ def main():
                 if oc.get("config") == 2 and "error" not in oc and "cpu_baseline" in out:
                     c2 = out["cpu_baseline"].get("config2_full") or {}
                     oc["cpu_baseline"] = dict(c2, cores=1, kind="port", sample="oracle/blance_oracle.c on all of config 2, one core")
-        if world == 1 and args.config == 3 and not args.no_extra:
+        if side and args.config == 3 and not args.no_extra:
             out["general_regime"] = timed_block("general_regime", lambda: general_regime(pl, fp, res, max(1, min(args.steps, 3))))
-        if world == 1 and args.config == 3 and not args.no_rccl_one_rank and not rehearsal:
+        if side and args.config == 3 and not args.no_rccl_one_rank and not rehearsal:
             out["rccl_one_rank"] = timed_block("rccl_one_rank", lambda: rccl_one_rank(
                 fp, digest, local_rank, max(3, min(args.steps, 10)), dt * 1e3 / args.steps))
-        if world == 1 and args.config == 3 and headline_shape and not args.no_replicas and not rehearsal:
+        if side and args.config == 3 and headline_shape and not args.no_replicas and not rehearsal:
             # (children of their own: GPU_MAX_HW_QUEUES has to be in the environment before the HIP runtime starts)
             def both():
                 r3 = replicas_block(args, 3, 40)
@@ -966,9 +983,9 @@ def main():
                 return [r3, r5]
             out["replicas_on_one_gpu"] = timed_block("replicas_on_one_gpu", both)
         fp5[0] = None
-        if world == 1 and args.config == 3 and not args.no_sharded:
+        if side and args.config == 3 and not args.no_sharded:
             out["sharded_on_one_gpu"] = timed_block("sharded_on_one_gpu", lambda: sharded_on_one_gpu(fp, digest, local_rank, dt / args.steps))
-        if world == 1 and not args.no_extra and not rehearsal:
+        if side and not args.no_extra and not rehearsal:
             out["host_end_to_end"] = timed_block("host_end_to_end", lambda: host_end_to_end(args.config))
         blocks["total"] = round(time.perf_counter() - T_START, 2)
     # ---- one plan over all ranks (config 4).  The line of the replicas is ready before this starts: RCCL is bound at

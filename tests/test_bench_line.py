@@ -52,7 +52,7 @@ def test_cpu_baseline_states_its_sample():
 
 def test_quoted_counters_are_tied_to_kernel_sources():
     """bench.py quotes a committed PMC profile only for the kernel sources it was taken from -- no list of "equivalent"
-    sources: any other hash gives traffic null (the default run measures its traffic live anyway, bench.live_pmc)."""
+    sources: any other hash gives traffic null (a run with --full measures its traffic live anyway, bench.live_pmc)."""
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import bench
@@ -140,14 +140,14 @@ def test_round6_line_items():
 
 
 def test_live_line_of_a_rehearsal_has_the_same_fields():
-    """bench.py itself, N = 1, on the CPU (BLANCE_BENCH_REHEARSAL: emulated kernels; the numbers mean nothing): the line it
+    """bench.py --full itself, N = 1, on the CPU (BLANCE_BENCH_REHEARSAL: emulated kernels; the numbers mean nothing): the line it
     prints carries the contract's fields, so an edit of bench.py cannot drop one unnoticed until the next device run."""
     import subprocess
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_simt_emulated import build_emu
     env = dict(os.environ, BLANCE_BENCH_REHEARSAL=build_emu())
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--parts", "600", "--nodes", "256", "--steps", "2",
-                          "--warmup", "1", "--no-sharded"], env=env, capture_output=True, text=True, timeout=900)
+                          "--warmup", "1", "--full", "--no-sharded"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -164,10 +164,48 @@ def test_live_line_of_a_rehearsal_has_the_same_fields():
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["sample"]
 
 
+FULL_ONLY = ("cpu_baseline", "other_configs", "general_regime", "rccl_one_rank", "replicas_on_one_gpu", "sharded_on_one_gpu",
+             "host_end_to_end", "matches_oracle_digest", "transfers")
+
+
+def test_plain_run_prints_the_headline_and_nothing_beside_it():
+    """bench.py without --full on the CPU rehearsal: the line has the headline's fields and none of the blocks that --full adds
+    -- whichever --no-... options are given --, the result stays on the device (no digest), and the blocks it timed are its
+    set-up and the headline alone.  The same arguments with --full bring the blocks back."""
+    import subprocess
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_simt_emulated import build_emu
+    env = dict(os.environ, BLANCE_BENCH_REHEARSAL=build_emu())
+    got = {}
+    for flags in ([], ["--no-extra"], ["--full", "--no-cpu-baseline"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--parts", "600", "--nodes", "256",
+                              "--steps", "2", "--warmup", "1"] + flags, env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stdout + out.stderr
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        got[" ".join(flags)] = json.loads(lines[0])
+    committed = _line()
+    for flags in ("", "--no-extra"):
+        d = got[flags]
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                    "vs_baseline", "dtype", "data", "config", "roofline", "roofline_per_kernel"):
+            assert key in d, key
+        assert d["metric"] == committed["metric"] and d["unit"] == committed["unit"] and d["dtype"] == committed["dtype"]
+        assert d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        per_call = d["value"] * d["ms_per_step"] * 1e-3
+        assert abs(per_call - d["config"]["assignments_per_call"]) < 1e-6 * per_call
+        assert not [k for k in FULL_ONLY + ("result_sha256", "outputs_dumped") if k in d]
+        assert set(d["block_seconds"]) == {"setup_and_first_upload", "headline", "total"}
+        assert "--full" in d["roofline"]["traffic_from"]
+    full = got["--full --no-cpu-baseline"]
+    assert "general_regime" in full and "sharded_on_one_gpu" in full and "transfers" in full and full["result_sha256"]
+    assert "cpu_baseline" not in full
+
+
 def test_bench_without_the_periodic_form_is_not_a_headline():
-    """bench.py --no-periodic (every step of the all-blank chain pass walked) on the CPU rehearsal: same result as the default
-    run of the same shape, the line says it is not the default; the default line carries both byte models of the roofline
-    block and the general_regime block (two more workloads of the same size)."""
+    """bench.py --full --no-periodic (every step of the all-blank chain pass walked) on the CPU rehearsal: same result as the
+    run of the same shape with the periodic form, the line says it is not the default; the line with the periodic form carries
+    both byte models of the roofline block and the general_regime block (two more workloads of the same size)."""
     import subprocess
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_simt_emulated import build_emu
@@ -175,7 +213,7 @@ def test_bench_without_the_periodic_form_is_not_a_headline():
     got = {}
     for flag in ([], ["--no-periodic", "--no-extra"]):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--parts", "4096", "--nodes", "256", "--steps", "1",
-                              "--warmup", "0", "--no-sharded", "--no-cpu-baseline"] + flag, env=env, capture_output=True,
+                              "--warmup", "0", "--full", "--no-sharded", "--no-cpu-baseline"] + flag, env=env, capture_output=True,
                              text=True, timeout=900)
         assert out.returncode == 0, out.stdout + out.stderr
         got[bool(flag)] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -3,7 +3,7 @@
 # from the upload) off and on, three runs each; `full`: then the parity suite in both modes and with every speculation forced
 # to fail.
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
-F="--no-extra --no-other-configs --no-replicas --no-cpu-baseline --no-sharded --no-transfers --no-live-pmc --no-rccl-one-rank"
+F="--full --no-extra --no-other-configs --no-replicas --no-cpu-baseline --no-sharded --no-transfers --no-live-pmc --no-rccl-one-rank"
 mkdir -p gpurun_out/ab
 for cfg in 3 2; do
 for r in 1 2 3; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # On the GPU box: config 3 with k_pass_chain on four and on eight waves per region, three runs each.
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
-F="--no-extra --no-other-configs --no-replicas --no-cpu-baseline --no-sharded --no-transfers --no-live-pmc --no-rccl-one-rank"
+F="--full --no-extra --no-other-configs --no-replicas --no-cpu-baseline --no-sharded --no-transfers --no-live-pmc --no-rccl-one-rank"
 mkdir -p gpurun_out/ab
 for r in 1 2 3; do
 for w in 4 8; do

@@ -8,9 +8,9 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/r6e
 mkdir -p "$out"
-(time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5) > "$out/bench_default.json" 2> "$out/bench_default.err"; tail -c 300 "$out/bench_default.err"
-timeout 300 python bench.py --config 2 --steps 20 --warmup 5 --no-replicas > "$out/bench_config2.json" 2> "$out/bench_config2.err"
-BLANCE_QUEUE_STATS=1 timeout 600 python bench.py --config 5 --steps 2 --warmup 1 --no-replicas > "$out/bench_config5.json" 2> "$out/bench_config5.err"
+(time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full) > "$out/bench_default.json" 2> "$out/bench_default.err"; tail -c 300 "$out/bench_default.err"
+timeout 300 python bench.py --config 2 --steps 20 --warmup 5 --full --no-replicas > "$out/bench_config2.json" 2> "$out/bench_config2.err"
+BLANCE_QUEUE_STATS=1 timeout 600 python bench.py --config 5 --steps 2 --warmup 1 --full --no-replicas > "$out/bench_config5.json" 2> "$out/bench_config5.err"
 python - <<'PY'
 import json, os
 o = os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out", "r6e")
