@@ -51,9 +51,18 @@ static int fail(int code, const char* fmt, const char* a = "", long b = 0) {
             return fail(BLANCE_ERR_DEVICE, "%s failed: line %ld", hipGetErrorString(e_), __LINE__); \
     } while (0)
 
-struct DevBuf {
+struct DevBuf {                                     // device memory, freed with its owner
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int reserve(size_t bytes) {
         if (bytes <= cap && p) return 0;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -188,15 +197,48 @@ static std::atomic<int> g_live_contexts{0};
 struct HostStage {                                   // a page-locked staging buffer of the context
     void* p = nullptr;
     size_t cap = 0, used = 0;
+    HostStage() = default;
+    HostStage(const HostStage&) = delete;
+    HostStage& operator=(const HostStage&) = delete;
+    ~HostStage() { release(); }
     void release() { if (p) pin_free(p); p = nullptr; cap = used = 0; }
 };
 
-struct blance_ctx {
+// What one plan did, written once when it ends (plan_locked's finish_plan); blance_result's counters are filled from it.
+struct PlanStats {
+    int32_t iterations = 0, converged = 0;
+    int64_t n_warnings = 0, steps_total = 0, steps_batched = 0, kernel_launches = 0, host_syncs = 0;
+    int64_t pass_launches = 0, flat_passes = 0, blank_launches = 0, stay_launches = 0;
+    double device_ms = 0.0, pass_ms = 0.0, flat_ms = 0.0, blank_ms = 0.0, stay_ms = 0.0;
+};
+
+// The context's streams and events.  A base of blance_ctx, so that they go after its members: ~blance_ctx synchronises the
+// streams and releases the communicator, the buffers free themselves, then events and streams are destroyed.
+struct CtxHandles {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t side = nullptr;     // the second stream (run_chain_pass_once: group_ahead)
+    hipEvent_t side_go = nullptr, side_done = nullptr;
+    std::vector<hipEvent_t> pass_events;     // begin/end pairs around every pass kernel
+    std::vector<hipEvent_t> comm_events;     // begin / end pairs around the collectives of the current plan (RCCL path)
+    ~CtxHandles() {
+        for (hipEvent_t e : pass_events) (void)hipEventDestroy(e);
+        for (hipEvent_t e : comm_events) (void)hipEventDestroy(e);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (side_go) (void)hipEventDestroy(side_go);
+        if (side_done) (void)hipEventDestroy(side_done);
+        if (side) (void)hipStreamDestroy(side);
+    }
+};
+
+enum PassKind { kPassKernel = 0, kPassFlatBulk = 1, kPassBlank = 2, kPassStayTop = 3 };   // what ran a state pass (statistics)
+
+struct blance_ctx : CtxHandles {
     int device = 0;
     int engine = BLANCE_ENGINE_AUTO;
     int force_threads = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::mutex mu;
     bool uploaded = false;
     bool planned = false;
@@ -208,8 +250,7 @@ struct blance_ctx {
     DevBuf topkey, top_counts, top_off, top_order;   // k_stay_by_top: steps grouped by the leaf of their top priority node
     // That grouping made AHEAD of the sweep that wants it: on a second stream, beside the chain kernel of the sweep before (a
     // few dozen workgroups on 256 CUs).  It holds as long as the grouping by region it was made from does (group_epoch).
-    hipStream_t side = nullptr;
-    hipEvent_t side_go = nullptr, side_done = nullptr;
+    // (CtxHandles: side, side_go, side_done)
     DevBuf side_sums;               // (launch_scan_excl's tile totals on that stream)
     bool side_pending = false;      // work on `side` the planner's stream has not waited for yet
     int top_group_state = -1;       // top_off / top_order are those of this state's chain order ...
@@ -218,16 +259,15 @@ struct blance_ctx {
     bool no_stay_top = false;       // test knob (& 64): never k_stay_by_top
     bool force_stay_top = false;    // test knob (& 128): try k_stay_by_top in every chain pass with NumPartitions > 0
     bool periodic = true;           // an all-blank chain pass with periodic records walks two periods (k_period.h); off: & 256, or BLANCE_PERIODIC=0
-    int64_t periodic_passes = 0;
     int periodic_cut = 0;           // test knob BLANCE_PERIODIC_CUT (k_period_clamp)
     DevBuf cnt_base, xbuf, gath;    // sharded pass: loads at pass start, [flags | load change], gathered output slices
     std::vector<int32_t> h_reg_off; // host copy of the chain offsets (slice sizes of the all-gather)
     int chain_group_state = -1;     // the state whose chain pass last grouped the steps by region (chain_order, chain_oi, reg_off) ...
     bool chain_group_static = false; // ... and whether it did so from the static order (sweeps >= 2)
     bool tops_moved = true;         // this sweep's top-state pass was not (known to be) one run of stays
-    uint32_t top_gate = 0;          // the words of scal + 4 every launch behind a top-state pass assumed to be one run of stays waits
+    uint32_t top_gate = 0;          // the words of scal + kScalFlags every launch behind a top-state pass assumed to be one run of stays waits
                                     // for (plan_locked: kFlagTopMoved, kFlagForced), 0 when that pass's verdict is known
-    bool flags_clean = false;       // the chain passes' flag words (scalars[4 .. 11]) are zero: nothing has set one since the last fill
+    bool flags_clean = false;       // the chain flags (scalars[kScalFlags ..], kChainFlags words) are zero: nothing has set one since the last fill
     bool rowcount_clean = false;    // f_row_count is zero (k_flat_row_count adds to it)
     bool top_prio_strict = false;   // every other state with constraints > 0 has a priority strictly behind the top state's
     // every partition gets the same partitionSorter category in sweep 1 (decided at upload): the pass order IS the static
@@ -246,17 +286,15 @@ struct blance_ctx {
     DevBuf vres, vseen;             // blance_upload: the device's part of the validation (k_validate_parts)
     DevBuf mv[11];                  // blance_calc_moves: inputs, per-partition slices, offsets, compacted outputs (kept between calls)
     int64_t comm_calls = 0, comm_bytes = 0;
-    std::vector<hipEvent_t> comm_events;     // begin / end pairs around the collectives of the current plan (RCCL path)
-    size_t comm_events_used = 0;
+    size_t comm_events_used = 0;             // (comm_events: CtxHandles)
     double comm_ms = 0.0;                    // device time between those pairs, all plans so far
-    int64_t n_syncs = 0, plan_syncs = 0;     // stream_sync() calls so far / inside the last plan
+    int64_t n_syncs = 0;                     // stream_sync() calls so far
     // known at upload (no readback needed for them in the first sweep's first pass): the partitions to assign hold no node at
     // all; no load counter starts above zero (no extra loads, nothing counted from prevMap)
     bool assign_empty = false, counts_start_zero = false;
     int chain_waves = 0;                     // k_pass_chain's workgroup: 0 = 8 waves when the LDS is there, else 4 (BLANCE_CHAIN_WAVES=4|8)
     int speculate = 1;                       // host decisions taken before their words are read back (BLANCE_SPECULATE=0|1|fail)
     bool fused_tail = true;                  // a sweep ends with k_sweep_tail instead of k_scatter + k_converge (BLANCE_FUSED_TAIL=0: off)
-    int64_t spec_refuted = 0;                // ... and how often one had to be taken back
 
     // host copy of the small parts of the problem
     blance_problem h{};
@@ -301,7 +339,6 @@ struct blance_ctx {
     DevBuf n_ev, chain_oi, ev_key, ev_oi, ev_leaf, ev_w, ev_perm, ev_off, ev_counts;   // chain events
     bool flat_chain_ok = false;
     DevBuf f_tot, f_g, f_top_g, f_top_n, f_row_count, f_m, f_moff, f_keys_a, f_keys_b, f_vals_a, f_vals_b, f_hist, f_comp;
-    int64_t steps_batched = 0;
     int64_t out_capacity = 0;
     DevBuf batch_in, batch_sc, batch_out;   // blance_plan_batch: descriptors + packed problems, working state, results
 
@@ -318,42 +355,9 @@ struct blance_ctx {
     DevBuf cnt, ntn, cat, order, chunk_counts, rec, out, warn_part, warn_state, scalars;
     DevBuf cnt_next;                // stateNodeCounts of the next sweep, counted by this sweep's k_sweep_tail (swapped with cnt)
     bool tail_counted = false;      // the last sweep's k_sweep_tail counted cnt_next and refreshed the kinds (plan.go:94, 418)
-    // scalars: [0] warn_count, [1] not_match, [2] err
-    int32_t iterations = 0, converged = 0;
-    int64_t n_warnings = 0, steps_total = 0, kernel_launches = 0, pass_launches = 0;
-    double device_ms = 0.0, pass_ms = 0.0;
-    std::vector<hipEvent_t> pass_events;     // begin/end pairs around every pass kernel
-    std::vector<int> pass_kind;              // 0 = one pass kernel, 1 = flat bulk driver
-    double flat_ms = 0.0, blank_ms = 0.0, stay_ms = 0.0;
-    int64_t flat_passes = 0, blank_launches = 0, stay_launches = 0;
-
-    void free_all() {
-        DevBuf* all[] = {&node_removed, &node_added, &node_weight, &node_has_weight, &alive, &zeros_nx,
-                         &node_leaf_pos, &part_order, &part_weight, &part_has_weight, &part_in_prev,
-                         &part_never_equal, &a_off, &a_nodes, &a_kind, &p_off, &p_nodes, &p_kind,
-                         &load_state, &load_node, &load_weight, &load_first, &rule_inc, &rule_exc,
-                         &vparent, &vlo, &vhi, &anchors, &state_stick, &state_has_stick, &live,
-                         &live_len, &live_kind, &prv, &prv_len, &prv_kind, &in_prev, &never_equal,
-                         &cnt, &ntn, &cat, &order, &chunk_counts, &rec, &out, &warn_part,
-                         &warn_state, &scalars, &cnt_next};
-        for (DevBuf* b : all) b->release();
-        for (auto& rr : rule_regions) { rr.node_region.release(); rr.reg_lo.release(); rr.reg_hi.release(); rr.leaf_cls.release(); rr.cls_size.release(); rr.wg_region.release(); rr.wg_chunk.release(); }
-        rule_regions.clear();
-        topkey.release(); top_counts.release(); top_off.release(); top_order.release();
-        alive_ids.release(); alive_rank.release(); side_sums.release();
-        cnt_base.release(); xbuf.release(); gath.release(); scan_sums.release(); scan_part.release(); ntn_bits.release();
-        dl_off.release(); dl_nodes.release(); vres.release(); vseen.release();
-        stage.release();
-        if (rb_buf) pin_free(rb_buf);
-        rb_buf = nullptr;
-        for (DevBuf& b : mv) b.release();
-        DevBuf* more[] = {&leaf_node, &regid, &chain_order, &chain_inv, &bucket_counts, &reg_off, &cnt_save, &crec, &period, &cnt_p1, &n_ev, &chain_oi,
-                          &ev_key, &ev_oi, &ev_leaf, &ev_w, &ev_perm, &ev_off, &ev_counts, &fl_iota, &fl_zero,
-                          &fl_one, &fl_reglo, &fl_reghi, &f_tot, &f_g,
-                          &f_top_g, &f_top_n, &f_row_count, &f_m, &f_moff, &f_keys_a, &f_keys_b, &f_vals_a,
-                          &f_vals_b, &f_hist, &f_comp, &batch_in, &batch_sc, &batch_out};
-        for (DevBuf* b : more) b->release();
-    }
+    PlanStats stats;                         // of the last plan
+    ~blance_ctx();
+    std::vector<PassKind> pass_kind;         // of every pass so far in this plan (pass_events holds their begin / end pairs)
 };
 
 static void comm_release(blance_ctx* c);
@@ -554,7 +558,7 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     if (hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
         hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreate(&c->side_go) != hipSuccess || hipEventCreate(&c->side_done) != hipSuccess) {
-        delete c;
+        delete c;                                    // (releases what was made)
         return fail(BLANCE_ERR_DEVICE, "stream/event creation failed");
     }
     *out = c;
@@ -562,21 +566,18 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     return BLANCE_OK;
 }
 
+// Nothing is in flight when the buffers go: both streams are synchronised first.  The members free themselves after this body,
+// events and streams last (CtxHandles).
+blance_ctx::~blance_ctx() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (side) (void)hipStreamSynchronize(side);
+    comm_release(this);
+    if (rb_buf) pin_free(rb_buf);
+}
+
 extern "C" void blance_ctx_destroy(blance_ctx* c) {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->side) (void)hipStreamSynchronize(c->side);
-    comm_release(c);
-    c->free_all();
-    for (hipEvent_t e : c->pass_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->comm_events) (void)hipEventDestroy(e);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->side_go) (void)hipEventDestroy(c->side_go);
-    if (c->side_done) (void)hipEventDestroy(c->side_done);
-    if (c->side) (void)hipStreamDestroy(c->side);
     delete c;
     if (--g_live_contexts == 0) pin_trim();          // the process's last context: the cache of page-locked blocks goes too
 }
@@ -726,8 +727,6 @@ struct FillCopyJob {
         if (words > most) most = words;
     }
 };
-static int run_fill_copy(blance_ctx* c, FillCopyJob& j);
-
 static int run_fill_copy(blance_ctx* c, FillCopyJob& j) {
     if (j.over) return fail(BLANCE_ERR_DEVICE, "k_fill_copy job over its slots");
     if (j.most > 0) BLANCE_LAUNCH_NOSYNC(k_fill_copy, cdiv(j.most, 256), 256, 0, c->stream, j.a);
@@ -881,7 +880,6 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     c->counts_start_zero = pb->n_loads == 0 && ps.aprev == 0;
     c->out_capacity = ps.cap;
 
-    for (auto& rr : c->rule_regions) { rr.node_region.release(); rr.reg_lo.release(); rr.reg_hi.release(); rr.leaf_cls.release(); rr.cls_size.release(); rr.wg_region.release(); rr.wg_chunk.release(); }
     c->rule_regions.clear();
     c->any_node_weight = 0;
     c->last_stays.assign((size_t)M, 0);
@@ -1018,7 +1016,7 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     RESERVE(out, sizeof(int32_t) * ((size_t)P * (1 + kmax) + 1));
     RESERVE(warn_part, sizeof(int32_t) * (size_t)(PM + 1));
     RESERVE(warn_state, sizeof(int32_t) * (size_t)(PM + 1));
-    RESERVE(scalars, 256);           // [16..17] k_pass_queue's stop words, [18..25] its statistics (long long x 4)
+    RESERVE(scalars, sizeof(int32_t) * kScalWords);   // (blance_kernels.h: ScalarWord)
     RESERVE(ntn_bits, sizeof(uint32_t) * (queue_bits_words(NX) + 4));
     {
         int maxB = 1;
@@ -1077,6 +1075,35 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     return BLANCE_OK;
 }
 
+// is a collective of this context's communicator more than a no-op? / does a chain pass over n_regions regions run sharded?
+static bool comm_active(const blance_ctx* c) { return c->comm.n_ranks > 1 || c->shard_one_rank; }
+static bool pass_sharded(const blance_ctx* c, int n_regions) { return comm_active(c) && n_regions >= c->comm.n_ranks; }
+
+// The fields the parameter blocks of the pass kernels (PassParams, ChainParams, StayParams, FlatParams) share, for the pass
+// of state s with k constraints; everything else is zero.
+template <class Q>
+static void fill_pass_common(const blance_ctx* c, Q& q, int s, int k, int NP) {
+    const blance_problem& h = c->h;
+    memset(&q, 0, sizeof q);
+    q.N = h.n_nodes; q.NX = h.n_nodes_ext; q.M = h.n_states; q.s = s; q.k = k; q.NP = NP; q.OW = 1 + k;
+    q.booster_kind = h.booster_kind;
+    q.alive = c->alive.as<uint8_t>(); q.node_weight = c->node_weight.as<int32_t>(); q.node_has_weight = c->node_has_weight.as<uint8_t>();
+    q.cnt = c->cnt.as<int32_t>();
+}
+// ... and a rule's region tables (ChainParams, StayParams)
+template <class Q>
+static void fill_region_tables(const blance_ctx* c, const blance_ctx::RuleRegions& rr, Q& q) {
+    q.reg_lo = rr.reg_lo.as<int32_t>(); q.reg_hi = rr.reg_hi.as<int32_t>();
+    q.leaf_node = c->leaf_node.as<int32_t>(); q.leaf_cls = rr.leaf_cls.as<int32_t>(); q.cls_size = rr.cls_size.as<int32_t>();
+}
+
+// f_row_count zeroed for a kernel that adds to it (k_flat_row_count, k_flat_row_count_live, k_gather)
+static int rowcount_reset(blance_ctx* c) {
+    if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)c->h.n_nodes_ext + 1), c->stream));
+    c->rowcount_clean = false;
+    return 0;
+}
+
 // plan.go:266: a state pass starts from an empty nodeToNodeCounts.  Called by whatever is about to read or bump the matrix
 // in HBM (NumPartitions > 0); the first such call of a pass zeroes it (a pass that never calls this -- region chains with their
 // rows in LDS, a pass that is one run of stays -- does not pay for the 67 MB).
@@ -1119,8 +1146,8 @@ static int dispatch_pass(blance_ctx* c, const PassParams& q0) {
     if (q.NP > 0) NTNTRY();
     int32_t* scal = c->scalars.as<int32_t>();
     q.ntn_bits = c->ntn_bits.as<uint32_t>();
-    q.stop = scal + 16;
-    q.qstats = (long long*)(scal + 18);
+    q.stop = scal + kScalQueueStop;
+    q.qstats = (long long*)(scal + kScalQueueStats);
     q.spec = (c->queue_general ? 8 : 0) | (c->queue_force_dense ? 16 : 0) | (c->queue_no_asm ? 32 : 0) | (c->queue_exact_rebuild ? 64 : 0) |
              (c->queue_bits_self ? 128 : 0);
     int pos = q0.beg, chunk = 64;
@@ -1133,7 +1160,7 @@ static int dispatch_pass(blance_ctx* c, const PassParams& q0) {
         }
         if (!launch_pass_queue(c->stream, q)) { q.beg = pos; return dispatch_pass_tree_or_seq(c, q); }
         int32_t st[2] = {0, 0};
-        HIPTRY(read_back(c, st, scal + 16, sizeof st));
+        HIPTRY(read_back(c, st, scal + kScalQueueStop, sizeof st));
         HIPTRY(stream_sync(c));
         c->queue_launches++;
         if (c->trace) fprintf(stderr, "[blance] k_pass_queue state %d steps [%d, %d) k %d: stopped at %d (%d)\n", q.s, pos, q0.end, q.k, st[0], st[1]);
@@ -1165,6 +1192,21 @@ static int launch_scan_excl_on(blance_ctx* c, hipStream_t stream, DevBuf& sums, 
     BLANCE_LAUNCH(k_scan_apply, tiles, 1024, 256, stream, n, data, sums.as<int32_t>());
     return 0;
 }
+// Stable counting sort of n items by key[i] < B: offs[B + 1] = where each key's items begin, out[] = src[i] (or i, src null)
+// in key order, out_oi[] (or null) = i in that order.  counts: B * cdiv(n, kPartChunk) + 1 words of scratch.
+static int group_by_key(blance_ctx* c, hipStream_t st, DevBuf& sums, int n, const int32_t* key, const int32_t* src, int B,
+                        int32_t* counts, int32_t* offs, int32_t* out, int32_t* out_oi) {
+    const int nch = cdiv(n, kPartChunk);
+    int bits = 1;
+    while ((1 << bits) < B) bits++;
+    BLANCE_LAUNCH(k_part_count, nch, 64, sizeof(int32_t) * B + 64, st, n, key, (const uint8_t*)nullptr, (const int32_t*)nullptr, nch, B, counts);
+    const int se = launch_scan_excl_on(c, st, sums, B * nch, counts);
+    if (se) return se;
+    BLANCE_LAUNCH_NOSYNC(k_region_offsets, cdiv(B + 1, 64), 64, 0, st, B, nch, n, counts, offs);
+    BLANCE_LAUNCH(k_part_scatter, nch, 64, sizeof(int32_t) * B + 64, st, n, key, (const uint8_t*)nullptr, (const int32_t*)nullptr, src, nch, B, bits,
+                  counts, out, out_oi);
+    return 0;
+}
 static int launch_scan_excl(blance_ctx* c, int n, int32_t* data) { return launch_scan_excl_on(c, c->stream, c->scan_sums, n, data); }
 #define SCANTRY(n, data) do { int e__ = launch_scan_excl(c, (n), (data)); if (e__) return e__; } while (0)
 
@@ -1181,7 +1223,7 @@ static int radix_sort_pairs(blance_ctx* c, int n, int64_t* launches, int32_t** s
     int32_t* va = c->f_vals_a.as<int32_t>();
     int32_t* vb = c->f_vals_b.as<int32_t>();
     // byte positions equal in every key need no pass (scores of one pass share most of their bits)
-    unsigned long long* vbits = (unsigned long long*)(c->scalars.as<int32_t>() + 14);
+    unsigned long long* vbits = (unsigned long long*)(c->scalars.as<int32_t>() + kScalSortVarying);
     unsigned long long varying = 0;
     if (known_varying) {
         varying = *known_varying;
@@ -1192,7 +1234,6 @@ static int radix_sort_pairs(blance_ctx* c, int n, int64_t* launches, int32_t** s
         HIPTRY(stream_sync(c));
         *launches += 1;
     }
-    int done = 0;
     for (int shift = 0; shift < 64; shift += 8) {
         if (((varying >> shift) & 0xff) == 0) continue;
         BLANCE_LAUNCH(k_sort_hist, n_tiles, 64, 1024 + 64, c->stream, n, shift, ka, n_tiles, c->f_hist.as<int32_t>());
@@ -1202,9 +1243,7 @@ static int radix_sort_pairs(blance_ctx* c, int n, int64_t* launches, int32_t** s
         std::swap(ka, kb);
         std::swap(va, vb);
         *launches += 3;
-        done++;
     }
-    (void)done;
     *sorted_vals = va;                               // (the loop swapped the roles after every pass)
     *other_vals = vb;
     return 0;
@@ -1221,35 +1260,34 @@ static int run_flat_chain(blance_ctx* c, PassParams q, int beg, int end, bool ld
     hipStream_t sm = c->stream;
     if (q.NP > 0) NTNTRY();
     c->bits_stale = true;
+    int32_t* flags = scal + kScalFlags;
     ChainParams cq;
-    memset(&cq, 0, sizeof cq);
-    cq.N = q.N; cq.NX = q.NX; cq.M = q.M; cq.L = q.L; cq.s = q.s; cq.k = q.k; cq.NP = q.NP; cq.OW = q.OW;
-    cq.booster_kind = q.booster_kind;
+    fill_pass_common(c, cq, q.s, q.k, q.NP);
+    cq.L = q.L;
     cq.n_regions = 1; cq.n_launch = 1; cq.flat = 1; cq.waves = c->chain_waves;
     cq.reg_lo = c->fl_reglo.as<int32_t>(); cq.reg_hi = c->fl_reghi.as<int32_t>();
     cq.reg_off = c->reg_off.as<int32_t>();
     cq.leaf_node = c->fl_iota.as<int32_t>(); cq.leaf_cls = c->fl_iota.as<int32_t>(); cq.cls_size = c->fl_one.as<int32_t>();
-    cq.alive = q.alive; cq.node_weight = q.node_weight; cq.node_has_weight = q.node_has_weight;
-    cq.cnt = q.cnt; cq.ntn = q.ntn; cq.crec = c->crec.as<int32_t>(); cq.out = q.out; cq.flags = scal + 4;
+    cq.ntn = q.ntn; cq.crec = c->crec.as<int32_t>(); cq.out = q.out; cq.flags = flags;
     int pos = beg;
     c->chain_group_state = -1;                       // (reg_off is this chain's range from here on)
     c->group_epoch++;
     while (pos < end) {
         int32_t range[2] = {pos, end};
         HIPTRY(hipMemcpyAsync(c->reg_off.p, range, sizeof range, hipMemcpyHostToDevice, sm));
-        HIPTRY(hipMemsetAsync(scal + 4, 0, 32, sm));
+        HIPTRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * kChainFlags, sm));
         c->flags_clean = false;
         cq.ntn_in_lds = lds_rows ? 1 : 0;
         if (!dispatch_chain(c, cq, q.NX)) return fail(BLANCE_ERR_UNSUPPORTED, "flat chain shape");
-        int32_t fl[8] = {0};
-        HIPTRY(read_back(c, fl, scal + 4, sizeof fl));
+        int32_t fl[kChainFlags] = {0};
+        HIPTRY(read_back(c, fl, flags, sizeof fl));
         HIPTRY(stream_sync(c));
         *launches += 1;
         lds_rows = false;                          // a stopped chain handed its rows to global memory
-        if (fl[0]) return 1;                       // a step the compact record cannot hold: caller falls back
-        if (!fl[1]) break;                         // ran to the end
-        if (fl[5]) c->no_fast_keys = true;
-        int stop = fl[4];
+        if (fl[kFlagNotLocal]) return 1;           // a step the compact record cannot hold: caller falls back
+        if (!fl[kFlagEscaped]) break;              // ran to the end
+        if (fl[kFlagStopRange]) c->no_fast_keys = true;
+        int stop = fl[kFlagStopAt];
         int nseq = end - stop < 16 ? end - stop : 16;
         q.beg = stop; q.end = stop + nseq;
         int e = dispatch_pass(c, q);
@@ -1259,10 +1297,6 @@ static int run_flat_chain(blance_ctx* c, PassParams q, int beg, int end, bool ld
     }
     return 0;
 }
-
-// words of scal + 4 (a Gate's flags) outside the eight the chain passes reset: k_stay_by_top's "not all stays";
-// BLANCE_SPECULATE=fail; k_flat_stay_live's "the sweep's first pass is NOT one run of stays"
-constexpr int kFlagStayMoved = 22, kFlagForced = 23, kFlagTopMoved = 24;
 
 // The compact records a flat single chain walks (clusters of <= 256 names), made when a pass first needs them: a pass the
 // bulk runs settle entirely (config 2: every pass) never pays for the gather and its round trip.
@@ -1277,17 +1311,17 @@ static int flat_chain_prepare(blance_ctx* c, FlatChainPrep& fc, int64_t* launche
     fc.done = true;
     const blance_problem& h = c->h;
     hipStream_t sm = c->stream;
-    int32_t* scal = c->scalars.as<int32_t>();
-    HIPTRY(hipMemsetAsync(scal + 4, 0, 32, sm));
+    int32_t* flags = c->scalars.as<int32_t>() + kScalFlags;
+    HIPTRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * kChainFlags, sm));
     c->flags_clean = false;
     BLANCE_LAUNCH(k_gather_chain, cdiv(h.n_parts, 256), 256, sizeof(int32_t) * 256 * (kCW + 1) + 64, sm, fc.d, fc.m, h.top_state, fc.higher_mask,
                          fc.order, (const int32_t*)nullptr, c->state_stick.as<int32_t>(),
                          c->state_has_stick.as<uint8_t>(), c->fl_iota.as<int32_t>(),
                          c->fl_zero.as<int32_t>(), c->fl_reglo.as<int32_t>(), c->fl_iota.as<int32_t>(),
                          c->fl_one.as<int32_t>(), 1,
-                         c->crec.as<int32_t>(), scal + 4, (int32_t*)nullptr, kNoGate);
+                         c->crec.as<int32_t>(), flags, (int32_t*)nullptr, kNoGate);
     int32_t bad = 0;
-    HIPTRY(read_back(c, &bad, scal + 4, sizeof bad));
+    HIPTRY(read_back(c, &bad, flags + kFlagNotLocal, sizeof bad));
     HIPTRY(stream_sync(c));
     *launches += 1;
     fc.ok = !bad;                                  // (bad: some step does not fit the compact record)
@@ -1302,7 +1336,7 @@ static int flat_chain_prepare(blance_ctx* c, FlatChainPrep& fc, int64_t* launche
 // and NumPartitions == 0 (k_flat_scan's test for "fresh": such a node is just not a candidate).  *whole_known: the pass was
 // such a run from its first step to its last.
 // assume_stays: a `settled` pass whose stay test is enqueued and NOT read back: the pass is taken to be one run of stays, and
-// k_flat_stay_live's verdict goes to scal[4 + kFlagTopMoved] for the caller's gates and its sweep's readback (plan_locked).
+// k_flat_stay_live's verdict goes to scal[kScalFlags + kFlagTopMoved] for the caller's gates and its sweep's readback (plan_locked).
 static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* launches, int64_t* batched,
                          FlatChainPrep& fc, bool opening, bool* whole_known, bool settled, bool assume_stays,
                          bool* nothing_to_apply, bool rows_counted) {
@@ -1311,28 +1345,32 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
     hipStream_t sm = c->stream;
     c->bits_stale = true;                           // (the bulk kernels below bump nodeToNodeCounts, not k_pass_queue's bit maps)
     const int P = q.P;
+    // (the driver's own words: outside the chain flags, which only chain code writes -- blance_ctx::flags_clean)
+    int32_t* scan_words = scal + kScalFlatScan;
+    int32_t* bad_word = scal + kScalFlatBad;
     FlatParams fq;
-    memset(&fq, 0, sizeof fq);
-    fq.N = q.N; fq.NX = q.NX; fq.M = q.M; fq.L = q.L; fq.P = P; fq.s = q.s; fq.k = q.k; fq.top_state = q.top_state;
-    fq.NP = q.NP; fq.RW = q.RW; fq.OW = q.OW; fq.higher_mask = q.higher_mask; fq.booster_kind = q.booster_kind;
-    fq.alive = q.alive; fq.node_weight = q.node_weight; fq.node_has_weight = q.node_has_weight;
-    fq.cnt = q.cnt; fq.tot = c->f_tot.as<int32_t>(); fq.g = c->f_g.as<double>();
+    fill_pass_common(c, fq, q.s, q.k, q.NP);
+    fq.L = q.L; fq.P = P; fq.top_state = q.top_state; fq.RW = q.RW; fq.higher_mask = q.higher_mask;
+    fq.tot = c->f_tot.as<int32_t>(); fq.g = c->f_g.as<double>();
     fq.top_g = c->f_top_g.as<double>(); fq.top_n = c->f_top_n.as<int32_t>();
     fq.row_count = c->f_row_count.as<int32_t>();
-    fq.ntn = q.ntn; fq.rec = q.rec; fq.out = q.out; fq.scan = scal + 8;
+    fq.ntn = q.ntn; fq.rec = q.rec; fq.out = q.out; fq.scan = scan_words;
     fq.int_keys = (q.NP == 0 && !c->any_node_weight) ? 1 : 0;
+    // the load totals and the smallest partition-independent scores: what the scan and the fresh run's threshold test against
+    auto prepare = [&]() {
+        BLANCE_LAUNCH(k_flat_prepare, 1, 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
+                      c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>());
+    };
     if (assume_stays) {
         // The stay test of the whole pass on the live lists (no step records: k_gather is not run), its row bound counted
         // from them as well; the verdict stays on the device.  What the pass would then do -- nothing, see `settled` below --
         // is done: no output, no k_scatter, and the top priority nodes are where they were.
         if (q.NP > 0) {
-            if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)q.NX + 1), sm));
-            c->rowcount_clean = false;
+            if (rowcount_reset(c)) return BLANCE_ERR_DEVICE;
             BLANCE_LAUNCH(k_flat_row_count_live, cdiv(P, 256), 256, 0, sm, fc.d, q.top_state, c->f_row_count.as<int32_t>(), q.NX);
             *launches += 1;
         }
-        BLANCE_LAUNCH(k_flat_prepare, 1, 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
-                      c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>());
+        prepare();
         const int scan_blocks = cdiv(P, 256);
         fq.scan_waves = scan_blocks * 4;
         if (c->scan_part.reserve(sizeof(int32_t) * 2 * ((size_t)fq.scan_waves + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
@@ -1340,7 +1378,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
         BLANCE_LAUNCH(k_flat_stay_live, scan_blocks, 256, 0, sm, fq, fc.d, fc.order, c->state_stick.as<int32_t>(),
                       c->state_has_stick.as<uint8_t>());
         BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, (int32_t*)nullptr,
-                      scal + 4 + kFlagTopMoved, P);
+                      scal + kScalFlags + kFlagTopMoved, P);
         *launches += 3;
         if (q.s == q.top_state) c->tops_moved = false;
         *nothing_to_apply = true;
@@ -1348,8 +1386,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
         return 0;
     }
     if (q.NP > 0 && !rows_counted) {                // only read by the stay test when NP > 0; (else: k_gather has counted)
-        if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)q.NX + 1), sm));
-        c->rowcount_clean = false;
+        if (rowcount_reset(c)) return BLANCE_ERR_DEVICE;
         BLANCE_LAUNCH(k_flat_row_count, cdiv(P, 256), 256, 0, sm, fq, c->f_row_count.as<int32_t>());
         *launches += 1;
     }
@@ -1368,9 +1405,8 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
         if (known_run) {
             got[0] = 0; got[1] = P;
         } else {
-            if (dirty) {                            // the load totals and the smallest partition-independent scores: what the scan tests against
-                BLANCE_LAUNCH(k_flat_prepare, 1, 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
-                              c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>());
+            if (dirty) {
+                prepare();
                 dirty = false;
                 *launches += 1;
             }
@@ -1379,8 +1415,8 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
             if (c->scan_part.reserve(sizeof(int32_t) * 2 * ((size_t)fq.scan_waves + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
             fq.scan_part = c->scan_part.as<int32_t>();
             BLANCE_LAUNCH(k_flat_scan, scan_blocks, 256, 0, sm, fq, pos, P);
-            BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, scal + 8, (int32_t*)nullptr, P);
-            HIPTRY(read_back(c, got, scal + 8, sizeof got));
+            BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, scan_words, (int32_t*)nullptr, P);
+            HIPTRY(read_back(c, got, scan_words, sizeof got));
             HIPTRY(stream_sync(c));
             *launches += 1;
         }
@@ -1426,8 +1462,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
                 *launches += 1;
             } else {
                 if (dirty) {
-                    BLANCE_LAUNCH(k_flat_prepare, 1, 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
-                                  c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>());
+                    prepare();
                     dirty = false;
                     *launches += 1;
                 }
@@ -1441,15 +1476,15 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
             const int32_t* picks = sorted_vals;
             if (excl) {
                 int32_t bad = INT_MAX;
-                HIPTRY(hipMemcpyAsync(scal + 10, &bad, sizeof bad, hipMemcpyHostToDevice, sm));
+                HIPTRY(hipMemcpyAsync(bad_word, &bad, sizeof bad, hipMemcpyHostToDevice, sm));
                 // (threads of a few steps each: coalesced record reads; up to 64 workgroups)
                 int G = cdiv(R, 4 * 1024);
                 G = G < 1 ? 1 : G > 64 ? 64 : G;
                 RESERVE(f_comp, (size_t)G * 1024 + 64 + 64);
                 unsigned char* comp = c->f_comp.as<unsigned char>();
                 BLANCE_LAUNCH(k_fresh_excl_scan, G, 1024, 2048 + 64, sm, fq, pos, R, sorted_vals, comp, comp + (size_t)G * 1024);
-                BLANCE_LAUNCH_NOSYNC(k_fresh_excl_apply, G, 1024, 0, sm, fq, pos, R, sorted_vals, comp, comp + (size_t)G * 1024, other_vals, scal + 10);
-                HIPTRY(read_back(c, &bad, scal + 10, sizeof bad));
+                BLANCE_LAUNCH_NOSYNC(k_fresh_excl_apply, G, 1024, 0, sm, fq, pos, R, sorted_vals, comp, comp + (size_t)G * 1024, other_vals, bad_word);
+                HIPTRY(read_back(c, &bad, bad_word, sizeof bad));
                 HIPTRY(stream_sync(c));
                 *launches += 1;
                 if (bad < R) R = bad;               // a pending node came up again: the run ends before that step
@@ -1664,7 +1699,7 @@ static void comm_sum_up(blance_ctx* c) {            // (after the stream has bee
 
 // in-place int32 sum over the ranks, ordered with the kernels of the planner's stream
 static int comm_allreduce(blance_ctx* c, int32_t* buf, int64_t n) {
-    if ((c->comm.n_ranks <= 1 && !c->shard_one_rank) || n <= 0) return 0;
+    if (!comm_active(c) || n <= 0) return 0;
     c->comm_calls++;
     c->comm_bytes += n * 4;
     if (c->comm.allreduce_sum_i32) {
@@ -1686,7 +1721,7 @@ static int comm_allreduce(blance_ctx* c, int32_t* buf, int64_t n) {
 
 // in-place all-gather of n_ranks blocks of `per_rank` int32 values (this rank's block filled in)
 static int comm_allgather(blance_ctx* c, int32_t* buf, int64_t per_rank) {
-    if ((c->comm.n_ranks <= 1 && !c->shard_one_rank) || per_rank <= 0) return 0;
+    if (!comm_active(c) || per_rank <= 0) return 0;
     c->comm_calls++;
     c->comm_bytes += per_rank * 4 * c->comm.n_ranks;
     if (c->comm.allreduce_sum_i32) {
@@ -1734,8 +1769,8 @@ static DevProblem dev_problem(blance_ctx* c) {
 
 // ---- one state pass as region chains ----------------------------------------
 // Header of the buffer the ranks of a sharded plan sum up after such a pass (collective A):
-// [0..7] the chain kernels' flags, [8] poison (a rank failed), then the load-vector change.
-constexpr int kXHead = 16;
+// [0 .. kChainFlags) the chain kernels' flags, [kXPoison] poison (a rank failed), then the load-vector change.
+constexpr int kXHead = 16, kXPoison = kChainFlags;
 // The sweep's last pass hands its list edits (k_scatter's arguments) to the sweep's tail, k_sweep_tail, instead of launching
 // them: plan_locked launches the tail after the pass.  scatter = false: the pass changed no list (run_flat_pass's
 // nothing_to_apply).  inv: the inverse of `order` (k_sweep_tail goes by partition), or null -- then k_scatter runs first.
@@ -1747,8 +1782,7 @@ struct SweepTail {
     Gate gate = kNoGate;
 };
 struct ChainPassArgs {
-    DevProblem d;
-    int m, k, NP, OW, RW, higher_mask, r0, it;
+    int m, k, NP, higher_mask, r0, it;
     const int32_t* order;          // the pass order: the stable partition of sweep 1, the static order itself afterwards
     bool same_tops;                // no partition has changed its top priority node since this state's last chain pass
     SweepTail* tail;               // non-null: the sweep's last pass, its k_scatter goes to the sweep's tail
@@ -1761,11 +1795,31 @@ static void comm_poison(blance_ctx* c) {
     if (c->xbuf.reserve(sizeof(int32_t) * (n + 1))) return;
     if (hipMemsetAsync(c->xbuf.p, 0, sizeof(int32_t) * n, c->stream) != hipSuccess) return;
     const int32_t one = 1;
-    if (hipMemcpyAsync(c->xbuf.as<int32_t>() + 8, &one, sizeof one, hipMemcpyHostToDevice, c->stream) != hipSuccess) return;
+    if (hipMemcpyAsync(c->xbuf.as<int32_t>() + kXPoison, &one, sizeof one, hipMemcpyHostToDevice, c->stream) != hipSuccess) return;
     if (stream_sync(c) != hipSuccess) return;
     (void)comm_allreduce(c, c->xbuf.as<int32_t>(), (int64_t)n);
     (void)stream_sync(c);
 }
+
+// What a plan has done so far.  Saved by value where a sweep or a pass may have to run again, and put back then.
+struct Progress {
+    int64_t steps = 0, batched = 0;
+    int n_pass = 0;                // passes timed so far (pass_events, pass_kind)
+    int passes_this_sweep = 0;
+};
+// One plan, from plan_locked's first line to its last.
+struct PlanRun {
+    DevProblem d;
+    int64_t launches = 0;
+    Progress at;
+    int32_t hs[kScalReadback] = {0};   // the scalar words read back after every sweep
+    int m_last = -1;               // the last state a sweep makes a pass for
+    // Each sweep ends with k_sweep_tail (the last pass's list edits, the convergence test and write-back, and the next
+    // sweep's counters and kinds) -- not on a sharded plan, whose ranks scatter the pass's gathered outputs one by one.
+    bool fuse = false;
+    bool top_spec_plan = true;     // (no sweep of this plan has refuted it: see Sweep::top_spec_off)
+    int iterations = 0, converged = 0;
+};
 
 // The host round trips a chain pass may save, and what it left open.
 //   allow_spec: the classification of a pass that reuses its grouping is ASSUMED clean (no events, no orphans) instead of
@@ -1776,57 +1830,107 @@ static void comm_poison(blance_ctx* c) {
 //     caller which words to look at with its next readback (the sweep's convergence word: one round trip for both).  A
 //     verdict that comes back bad has changed nothing but the counters (cnt_save holds them): the caller runs the pass
 //     again with no_stay / no_lean / skip set accordingly.
+enum class Pending { kNone, kStayTop, kBlank, kChain };   // whose verdict is still on the device
 struct ChainRun {
     bool allow_spec = true, defer = false, no_stay = false, no_lean = false, skip = false;
     bool redo = false;
-    int pending = 0;               // 0: settled; 1: k_stay_by_top's verdict, 2: the all-blank kernel's, 3: the chain kernel's is still on the device
+    Pending pending = Pending::kNone;
     bool spec = false;             // the classification was assumed
     Gate gate = kNoGate;
+    bool done = false;             // the pass was made; if not (and no redo), the counters are as before and the caller
+                                   // runs the pass in order
+    bool a_done = false;           // collective A of a sharded pass has been entered
 };
 
-// 0 = ok (*done tells whether the pass was made; if not, the counters are as before and the caller
-// runs the pass in order), < 0 = error.
-static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* launches_io, int64_t* batched_io, int* n_pass_io,
-                               bool* done, bool* a_done, ChainRun& run) {
-    const blance_problem& h = c->h;
-    const DevProblem& d = a.d;
-    const int N = h.n_nodes, NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts, L = c->L;
-    const int m = a.m, k = a.k, NP = a.NP, OW = a.OW;
-    hipStream_t sm = c->stream;
-    int32_t* scal = c->scalars.as<int32_t>();
-    int64_t launches = 0;
-    int& n_pass = *n_pass_io;
-    blance_ctx::RuleRegions& rr = c->rule_regions[a.r0];
-    const int B = rr.n_regions, nbc = cdiv(P, kPartChunk);
-    const int G = c->comm.n_ranks, rank = c->comm.rank;
-    const bool sharded = (G > 1 || c->shard_one_rank) && B >= G;
-    if (!c->flags_clean) HIPTRY(hipMemsetAsync(scal + 4, 0, 32, sm));
+// One attempt at a chain pass: what its phases share.  Every phase returns 0 or an error; a phase that finds the attempt's
+// assumptions refuted sets run.redo (run() then ends at once).
+struct ChainPass {
+    blance_ctx* const c;
+    PlanRun& pr;
+    const ChainPassArgs& a;
+    ChainRun& run;
+    const blance_problem& h;
+    const DevProblem& d;
+    blance_ctx::RuleRegions& rr;
+    const int m, OW, P, B, nbc, G, rank;
+    const bool sharded;
+    const size_t cnt_words;
+    const hipStream_t sm;
+    int32_t* const flags;                    // the chain flags on the device
+    Gate top_gate = kNoGate;
+    bool regroup = false, spec = false, defer = false, gather_out = false;
+    int32_t cfl[kChainFlags] = {0};          // the classification's flags (all zero when they were assumed)
+    int32_t n_events = 0;
+    bool stay_fits = false, try_stay = false, group_stands = false, group_ahead = false;
+    ChainParams cq;
+
+    ChainPass(blance_ctx* c_, PlanRun& pr_, const ChainPassArgs& a_, ChainRun& run_)
+        : c(c_), pr(pr_), a(a_), run(run_), h(c_->h), d(pr_.d), rr(c_->rule_regions[a_.r0]), m(a_.m), OW(1 + a_.k), P(c_->h.n_parts), B(rr.n_regions),
+          nbc(cdiv(c_->h.n_parts, kPartChunk)), G(c_->comm.n_ranks), rank(c_->comm.rank), sharded(pass_sharded(c_, rr.n_regions)),
+          cnt_words((size_t)(c_->h.n_states + 1) * c_->h.n_nodes_ext), sm(c_->stream),
+          flags(c_->scalars.as<int32_t>() + kScalFlags) {}
+
+    int slice_lo(int r) const { return (int)((int64_t)B * r / G); }   // a sharded plan: rank r walks regions [slice_lo(r), slice_lo(r + 1))
+    Gate gate_on(uint32_t words) const {               // (the flag words a deferred verdict depends on)
+        return Gate{flags, words | (1u << kFlagForced) | (spec ? (1u << kFlagOrphans) | (1u << kFlagEvents) : 0u) | c->top_gate};
+    }
+    // (speculate == 2, tests: every assumption is treated as refuted)
+    bool refuted(const int32_t* f) const { return spec && (f[kFlagOrphans] || f[kFlagEvents] || c->speculate == 2); }
+    void uncount_orphans() {                           // nodes of this state that lie in no region
+        BLANCE_LAUNCH_NOSYNC(k_chain_orphans, cdiv(P, 256), 256, 0, sm, d, m, h.top_state, a.order,
+                             rr.node_region.as<int32_t>(), c->cnt.as<int32_t>());
+    }
+    int restore_counters() {
+        HIPTRY(hipMemcpyAsync(c->cnt.p, c->cnt_save.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
+        return 0;
+    }
+    int open_timing() { HIPTRY(hipEventRecord(c->pass_events[2 * pr.at.n_pass], sm)); return 0; }
+    int close_timing(PassKind kind) {
+        HIPTRY(hipEventRecord(c->pass_events[2 * pr.at.n_pass + 1], sm));
+        c->pass_kind.resize(pr.at.n_pass + 1);
+        c->pass_kind[pr.at.n_pass] = kind;
+        pr.at.n_pass++;
+        return 0;
+    }
+
+    int classify_and_group();
+    int events();
+    int gather_records();
+    int group_by_top(hipStream_t st, DevBuf& sums);
+    void fill_chain_params();
+    int start_counters();
+    int stay_attempt(bool* stayed);
+    int blank_walk(bool* lean);
+    int periodic_walk(bool* walked);
+    int collective_a(int32_t* fl);
+    int collective_b();
+    int commit();
+    int run_once();
+};
+
+// The pass's steps classified by the region of their top priority node and grouped by it; the classification's flags read
+// back, or assumed.
+int ChainPass::classify_and_group() {
+    if (!c->flags_clean) HIPTRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * kChainFlags, sm));
     c->flags_clean = false;
     // (c->top_gate: the sweep's first pass is taken to be one run of stays -- plan_locked -- and every launch of this pass
     // waits for that verdict: closed, it returns at once)
-    const Gate top_gate{scal + 4, c->top_gate};
+    top_gate = Gate{flags, c->top_gate};
     BLANCE_LAUNCH_NOSYNC(k_chain_classify, cdiv(P + 1, 256), 256, 0, sm, d, m, h.top_state,
                          a.order, rr.node_region.as<int32_t>(), c->regid.as<int32_t>(),
-                         c->n_ev.as<int32_t>(), scal + 4, top_gate);
-    int nbits = 1;
-    while ((1 << nbits) < B) nbits++;
+                         c->n_ev.as<int32_t>(), flags, top_gate);
     // The steps grouped by the region of their top priority node (a stable counting sort of the pass order).  A sweep whose
     // top-state pass was one run of stays has moved no top priority node, and from sweep 2 on the pass order is the static
     // order: the grouping of this state's last chain pass -- chain_order, chain_oi, reg_off -- still stands (config 3's
     // third sweep: six launches less).
-    const bool regroup = !(a.same_tops && c->chain_group_state == m && c->chain_group_static && a.order == c->part_order.as<int32_t>() &&
-                           c->h_reg_off.size() == (size_t)B + 1);
+    regroup = !(a.same_tops && c->chain_group_state == m && c->chain_group_static && a.order == c->part_order.as<int32_t>() &&
+                c->h_reg_off.size() == (size_t)B + 1);
     if (regroup) {
-        BLANCE_LAUNCH(k_part_count, nbc, 64, sizeof(int32_t) * B + 64, sm, P, c->regid.as<int32_t>(),
-                      (const uint8_t*)nullptr, (const int32_t*)nullptr, nbc, B, c->bucket_counts.as<int32_t>());
-        SCANTRY(B * nbc, c->bucket_counts.as<int32_t>());
-        BLANCE_LAUNCH_NOSYNC(k_region_offsets, cdiv(B + 1, 64), 64, 0, sm, B, nbc, P,
-                             c->bucket_counts.as<int32_t>(), c->reg_off.as<int32_t>());
-        BLANCE_LAUNCH(k_part_scatter, nbc, 64, sizeof(int32_t) * B + 64, sm, P, c->regid.as<int32_t>(),
-                      (const uint8_t*)nullptr, (const int32_t*)nullptr, a.order, nbc, B, nbits,
-                      c->bucket_counts.as<int32_t>(), c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>());
+        const int ge = group_by_key(c, sm, c->scan_sums, P, c->regid.as<int32_t>(), a.order, B, c->bucket_counts.as<int32_t>(),
+                                    c->reg_off.as<int32_t>(), c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>());
+        if (ge) return ge;
         BLANCE_LAUNCH_NOSYNC(k_invert, cdiv(P, 256), 256, 0, sm, P, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>());
-        launches++;
+        pr.launches++;
         c->chain_group_state = m;
         c->group_epoch++;
         c->chain_group_static = a.order == c->part_order.as<int32_t>();
@@ -1835,79 +1939,86 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
     // plan reads the chain offsets in the same round trip (the slice sizes of collective B)
     // A pass that reuses its grouping has nothing else to learn from this round trip: with the top priority nodes where they
     // were, events and orphans come from this state's own nodes having left their partition's region since -- rare enough to
-    // assume there are none and to look at flags[6], flags[7] only when the pass's own flags come back.
-    const bool spec = run.allow_spec && !regroup && !sharded && c->speculate > 0;
-    const bool defer = run.defer && !sharded && c->speculate > 0;
-    if (c->top_gate && (regroup || !spec || !defer))               // (plan_locked's top_spec_fits rules these out)
+    // assume there are none and to look at flags[kFlagOrphans], flags[kFlagEvents] only when the pass's own flags come back.
+    spec = run.allow_spec && !regroup && !sharded && c->speculate > 0;
+    defer = run.defer && !sharded && c->speculate > 0;
+    if (c->top_gate && (regroup || !spec || !defer))               // (top_spec_fits rules these out)
         return fail(BLANCE_ERR_DEVICE, "a chain pass behind the top-state pass's verdict would read back");
     run.spec = spec;
-    run.pending = 0;
+    run.pending = Pending::kNone;
     run.redo = false;
-    auto gate_on = [&](uint32_t words) {               // (the words of scal + 4 a deferred verdict depends on)
-        Gate g;
-        g.flags = scal + 4;
-        g.mask = words | (1u << kFlagForced) | (spec ? (1u << 6) | (1u << 7) : 0u) | c->top_gate;
-        return g;
-    };
-    int32_t n_events = 0, cfl[8] = {0};
     if (!spec) {
-        HIPTRY(read_back(c, cfl, scal + 4, sizeof cfl));
+        HIPTRY(read_back(c, cfl, flags, sizeof cfl));
         if (regroup) {                                     // (always: the next sweep may reuse the grouping, the host's copy with it)
             c->h_reg_off.resize((size_t)B + 1);
             HIPTRY(read_back(c, c->h_reg_off.data(), c->reg_off.p, sizeof(int32_t) * ((size_t)B + 1)));
         }
         HIPTRY(stream_sync(c));
     }
-    // (speculate == 2, tests: every assumption is treated as refuted)
-    auto refuted = [&](const int32_t* f) { return spec && (f[6] || f[7] || c->speculate == 2); };
-    if (!cfl[0] && cfl[7]) {                            // rare: nodes outside their partition's region
+    return 0;
+}
+
+// The pass's events (nodes a partition holds in this state outside its region) counted and grouped by the region that owns
+// them; and the one launch every attempt starts with.
+int ChainPass::events() {
+    if (!cfl[kFlagNotLocal] && cfl[kFlagEvents]) {      // rare: nodes outside their partition's region
         SCANTRY(P + 1, c->n_ev.as<int32_t>());   // -> event slots
         HIPTRY(read_back(c, &n_events, c->n_ev.as<int32_t>() + P, sizeof n_events));
         HIPTRY(stream_sync(c));
     }
     if (c->trace)
         fprintf(stderr, spec ? "[blance] chain pass state %d: classification assumed clean (checked with the pass's flags)\n" :
-                               "[blance] chain pass state %d: %d events, not-local %d, orphans %d\n", m, n_events, cfl[0], cfl[6]);
-    const size_t cnt_words = (size_t)(M + 1) * NX;
+                               "[blance] chain pass state %d: %d events, not-local %d, orphans %d\n", m, n_events, cfl[kFlagNotLocal], cfl[kFlagOrphans]);
     {   // one launch: no events yet, the counters this pass starts from (what a redo restores), k_stay_by_top's flag
         FillCopyJob fj;
         fj.zero(c->ev_off.p, (int64_t)B + 1);
-        fj.zero(scal + 4 + kFlagStayMoved, 1);
+        fj.zero(flags + kFlagStayMoved, 1);
         fj.copy(c->cnt_save.p, c->cnt.p, (int64_t)cnt_words);
         if (run_fill_copy(c, fj)) return BLANCE_ERR_DEVICE;
     }
-    if (!cfl[0] && n_events > 0) {
-        const int nec = cdiv(n_events, kPartChunk);
+    if (!cfl[kFlagNotLocal] && n_events > 0) {
         BLANCE_LAUNCH_NOSYNC(k_chain_ev_fill, cdiv(P, 256), 256, 0, sm, d, m, h.top_state, a.order,
                              rr.node_region.as<int32_t>(), rr.reg_lo.as<int32_t>(), c->node_leaf_pos.as<int32_t>(),
                              c->regid.as<int32_t>(), c->n_ev.as<int32_t>(), c->ev_key.as<int32_t>(),
                              c->ev_oi.as<int32_t>(), c->ev_leaf.as<int32_t>(), c->ev_w.as<int32_t>());
-        BLANCE_LAUNCH(k_part_count, nec, 64, sizeof(int32_t) * B + 64, sm, n_events, c->ev_key.as<int32_t>(),
-                      (const uint8_t*)nullptr, (const int32_t*)nullptr, nec, B, c->ev_counts.as<int32_t>());
-        SCANTRY(B * nec, c->ev_counts.as<int32_t>());
-        BLANCE_LAUNCH_NOSYNC(k_region_offsets, cdiv(B + 1, 64), 64, 0, sm, B, nec, n_events,
-                             c->ev_counts.as<int32_t>(), c->ev_off.as<int32_t>());
-        BLANCE_LAUNCH(k_part_scatter, nec, 64, sizeof(int32_t) * B + 64, sm, n_events, c->ev_key.as<int32_t>(),
-                      (const uint8_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, nec, B, nbits,
-                      c->ev_counts.as<int32_t>(), c->ev_perm.as<int32_t>(), (int32_t*)nullptr);
-        launches += 5;
+        const int ge = group_by_key(c, sm, c->scan_sums, n_events, c->ev_key.as<int32_t>(), nullptr, B, c->ev_counts.as<int32_t>(),
+                                    c->ev_off.as<int32_t>(), c->ev_perm.as<int32_t>(), nullptr);
+        if (ge) return ge;
+        pr.launches += 5;
     }
+    return 0;
+}
+
+// steps grouped by the leaf of their top priority node, pass order inside a group (stable counting sort)
+int ChainPass::group_by_top(hipStream_t st, DevBuf& sums) {
+    const int ge = group_by_key(c, st, sums, P, c->topkey.as<int32_t>(), nullptr, rr.n_leaves, c->top_counts.as<int32_t>(),
+                                c->top_off.as<int32_t>(), c->top_order.as<int32_t>(), nullptr);
+    if (ge) return ge;
+    c->top_group_state = m;
+    c->top_group_epoch = c->group_epoch;
+    pr.launches += 5;
+    return 0;
+}
+
+// The compact records of the pass in chain order (k_gather_chain); whether k_stay_by_top is worth a try, and its work list
+// made on the second stream for the next sweep when it is not.
+int ChainPass::gather_records() {
     // A pass of stays only (the last sweep of every plan that converges)?  Worth a try when the state's pass of the
     // sweep before was one but for a few steps: k_stay_by_top checks every step in parallel.
-    const bool stay_fits = !sharded && !c->no_stay_top && NP > 0 && !cfl[0] && !cfl[6] && !cfl[7] && rr.max_size <= kStayMaxLeaves && rr.n_stay_wgs > 0;
-    const bool try_stay = stay_fits && !run.no_stay && (c->force_stay_top || c->last_stays[m] * 100 >= (int64_t)P * 99);
+    stay_fits = !sharded && !c->no_stay_top && a.NP > 0 && !cfl[kFlagNotLocal] && !cfl[kFlagOrphans] && !cfl[kFlagEvents] &&
+                rr.max_size <= kStayMaxLeaves && rr.n_stay_wgs > 0;
+    try_stay = stay_fits && !run.no_stay && (c->force_stay_top || c->last_stays[m] * 100 >= (int64_t)P * 99);
     // k_stay_by_top's work list (the steps grouped by the leaf of their top priority node: four launches over all steps)
     // depends on the grouping by region and on the top priority nodes only.  One made for this state at the same count of
     // regroupings still holds; and a pass that does NOT try k_stay_by_top makes it for the next sweep's on the second
     // stream, beside its own chain kernel.
-    const bool group_stands = c->top_group_state == m && c->top_group_epoch == c->group_epoch;
+    group_stands = c->top_group_state == m && c->top_group_epoch == c->group_epoch;
     // (The second stream is made when it is first wanted, and only in a process of one or two planners: a stream is a
     // hardware queue, and with many contexts planning at once on one GPU -- bench.py's replicas: 16 contexts, 32 queues -- the
     // planners' own streams end up sharing queues and their long kernels run one after the other.)
-    bool group_ahead = stay_fits && !try_stay && !group_stands && c->speculate > 0 && a.it + 1 < h.max_iterations &&
-                       (c->side || g_live_contexts.load() <= 2);
+    group_ahead = stay_fits && !try_stay && !group_stands && c->speculate > 0 && a.it + 1 < h.max_iterations &&
+                  (c->side || g_live_contexts.load() <= 2);
     if (group_ahead && !c->side && hipStreamCreate(&c->side) != hipSuccess) { c->side = nullptr; group_ahead = false; (void)hipGetLastError(); }
-    const int BL = rr.n_leaves;
     if (try_stay || group_ahead) {
         RESERVE(topkey, sizeof(int32_t) * ((size_t)P + 1));
         RESERVE(top_order, sizeof(int32_t) * ((size_t)P + 1));
@@ -1924,24 +2035,7 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
                          c->state_has_stick.as<uint8_t>(), c->node_leaf_pos.as<int32_t>(),
                          rr.node_region.as<int32_t>(), rr.reg_lo.as<int32_t>(), rr.leaf_cls.as<int32_t>(),
                          rr.cls_size.as<int32_t>(), 0,
-                         c->crec.as<int32_t>(), scal + 4, group_now ? c->topkey.as<int32_t>() : (int32_t*)nullptr, top_gate);
-    // steps grouped by the leaf of their top priority node, pass order inside a group (stable counting sort)
-    auto group_by_top = [&](hipStream_t st, DevBuf& sums) -> int {
-        int lbits = 1;
-        while ((1 << lbits) < BL) lbits++;
-        BLANCE_LAUNCH(k_part_count, nbc, 64, sizeof(int32_t) * BL + 64, st, P, c->topkey.as<int32_t>(),
-                      (const uint8_t*)nullptr, (const int32_t*)nullptr, nbc, BL, c->top_counts.as<int32_t>());
-        const int se = launch_scan_excl_on(c, st, sums, BL * nbc, c->top_counts.as<int32_t>());
-        if (se) return se;
-        BLANCE_LAUNCH_NOSYNC(k_region_offsets, cdiv(BL + 1, 64), 64, 0, st, BL, nbc, P, c->top_counts.as<int32_t>(), c->top_off.as<int32_t>());
-        BLANCE_LAUNCH(k_part_scatter, nbc, 64, sizeof(int32_t) * BL + 64, st, P, c->topkey.as<int32_t>(),
-                      (const uint8_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, nbc, BL, lbits,
-                      c->top_counts.as<int32_t>(), c->top_order.as<int32_t>(), (int32_t*)nullptr);
-        c->top_group_state = m;
-        c->top_group_epoch = c->group_epoch;
-        launches += 5;
-        return 0;
-    };
+                         c->crec.as<int32_t>(), flags, group_now ? c->topkey.as<int32_t>() : (int32_t*)nullptr, top_gate);
     if (group_ahead) {
         HIPTRY(hipEventRecord(c->side_go, sm));        // (the keys are written)
         HIPTRY(hipStreamWaitEvent(c->side, c->side_go, 0));
@@ -1951,10 +2045,13 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
         c->side_pending = true;
         if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps grouped by top priority node for the next sweep, on the second stream\n", m);
     }
-    ChainParams cq;
-    memset(&cq, 0, sizeof cq);
-    cq.N = N; cq.NX = NX; cq.M = M; cq.L = L; cq.s = m; cq.k = k;
-    cq.NP = NP; cq.OW = OW; cq.booster_kind = h.booster_kind;
+    return 0;
+}
+
+void ChainPass::fill_chain_params() {
+    fill_pass_common(c, cq, m, a.k, a.NP);
+    fill_region_tables(c, rr, cq);
+    cq.L = c->L;
     cq.n_regions = B;
     // (a plan's first sweep is where the moves are: a stay round of 512 steps that commits a short prefix costs more than one of
     // 256 -- the last wave looks its node up in seven tables; the rebalance of config 3 after a tenth of the nodes left: 59.5
@@ -1962,303 +2059,737 @@ static int run_chain_pass_once(blance_ctx* c, const ChainPassArgs& a, int64_t* l
     cq.waves = c->chain_waves ? c->chain_waves : (a.it == 0 ? 4 : 0);
     cq.cls_run = rr.cls_run;
     // a sharded plan: this rank walks the chains of its slice of the regions
-    auto slice_lo = [&](int r) { return (int)((int64_t)B * r / G); };
     cq.region_base = sharded ? slice_lo(rank) : 0;
     cq.n_launch = sharded ? slice_lo(rank + 1) - cq.region_base : B;
-    cq.reg_lo = rr.reg_lo.as<int32_t>(); cq.reg_hi = rr.reg_hi.as<int32_t>();
     cq.reg_off = c->reg_off.as<int32_t>();
-    cq.leaf_node = c->leaf_node.as<int32_t>();
-    cq.leaf_cls = rr.leaf_cls.as<int32_t>();
-    cq.cls_size = rr.cls_size.as<int32_t>();
-    cq.alive = c->alive.as<uint8_t>();
-    cq.node_weight = c->node_weight.as<int32_t>();
-    cq.node_has_weight = c->node_has_weight.as<uint8_t>();
-    cq.cnt = c->cnt.as<int32_t>(); cq.ntn = c->ntn.as<int32_t>();
+    cq.ntn = c->ntn.as<int32_t>();
     cq.crec = c->crec.as<int32_t>(); cq.out = c->out.as<int32_t>();
-    cq.flags = scal + 4;
+    cq.flags = flags;
     cq.gate = c->top_gate;
     cq.ev_off = c->ev_off.as<int32_t>(); cq.ev_perm = c->ev_perm.as<int32_t>();
     cq.ev_oi = c->ev_oi.as<int32_t>(); cq.ev_leaf = c->ev_leaf.as<int32_t>(); cq.ev_w = c->ev_w.as<int32_t>();
-    if (cfl[6])                                        // nodes of this state that lie in no region
-        BLANCE_LAUNCH_NOSYNC(k_chain_orphans, cdiv(P, 256), 256, 0, sm, d, m, h.top_state, a.order,
-                             rr.node_region.as<int32_t>(), c->cnt.as<int32_t>());
     cq.cnt_out = cq.cnt;
-    const bool gather_out = sharded && (c->comm.allgather_i32 || !c->comm.allreduce_sum_i32);
+}
+
+// the counters every walk of this pass starts from: the orphans' loads gone, and a sharded plan's copy of them
+int ChainPass::start_counters() {
+    if (cfl[kFlagOrphans]) uncount_orphans();
+    gather_out = sharded && (c->comm.allgather_i32 || !c->comm.allreduce_sum_i32);
     if (sharded) {                                     // the loads every rank starts this pass from (orphans included)
         RESERVE(cnt_base, sizeof(int32_t) * (cnt_words + 1));
         RESERVE(xbuf, sizeof(int32_t) * (kXHead + cnt_words + 1));
         HIPTRY(hipMemcpyAsync(c->cnt_base.p, c->cnt.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
         if (!gather_out) HIPTRY(hipMemsetAsync(c->out.p, 0, sizeof(int32_t) * (size_t)P * OW, sm));
     }
-    HIPTRY(hipEventRecord(c->pass_events[2 * n_pass], sm));
-    bool stayed = false;
-    if (try_stay) {
-        if (!group_stands) {
-            const int ge = group_by_top(sm, c->scan_sums);
-            if (ge) return ge;
-        } else if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps' grouping by top priority node stands\n", m);
-        StayParams sq;
-        memset(&sq, 0, sizeof sq);
-        sq.N = N; sq.NX = NX; sq.M = M; sq.s = m; sq.k = k; sq.NP = NP; sq.OW = OW; sq.booster_kind = h.booster_kind;
-        sq.wg_region = rr.wg_region.as<int32_t>(); sq.wg_chunk = rr.wg_chunk.as<int32_t>();
-        sq.reg_lo = rr.reg_lo.as<int32_t>(); sq.reg_hi = rr.reg_hi.as<int32_t>();
-        sq.leaf_node = c->leaf_node.as<int32_t>(); sq.leaf_cls = rr.leaf_cls.as<int32_t>(); sq.cls_size = rr.cls_size.as<int32_t>();
-        sq.alive = c->alive.as<uint8_t>(); sq.node_weight = c->node_weight.as<int32_t>(); sq.node_has_weight = c->node_has_weight.as<uint8_t>();
-        sq.cnt = c->cnt.as<int32_t>(); sq.crec = c->crec.as<int32_t>();
-        sq.top_off = c->top_off.as<int32_t>(); sq.top_order = c->top_order.as<int32_t>();
-        sq.out = c->out.as<int32_t>(); sq.flag = scal + 4 + kFlagStayMoved;
-        sq.gate = top_gate;
-        if (launch_stay_by_top(sm, sq, rr.n_stay_wgs, rr.max_size)) {
-            launches += 1;
-            if (defer) {
-                stayed = true;                          // (until the caller's readback says otherwise)
-                run.pending = 1;
-                run.gate = gate_on(1u | (1u << kFlagStayMoved));
-                if (c->trace) fprintf(stderr, "[blance] chain pass state %d: stays per top priority node, the verdict is read with the sweep's\n", m);
-            } else {
-                int32_t sf[8] = {0}, moved = 0;         // [0] a step is not region-local (k_gather_chain); moved: not all stays
-                HIPTRY(read_back(c, sf, scal + 4, sizeof sf));
-                HIPTRY(read_back(c, &moved, scal + 4 + kFlagStayMoved, sizeof moved));
-                HIPTRY(stream_sync(c));
-                if (refuted(sf)) {                      // (k_stay_by_top changes no counter)
-                    run.redo = true;
-                    *launches_io += launches;
-                    return 0;
-                }
-                stayed = !sf[0] && !moved;
-                if (c->trace) fprintf(stderr, "[blance] chain pass state %d: stays verified per top priority node: %s\n", m, stayed ? "all of them" : "no");
-            }
-        }
-    }
-    if (stayed) {
-        HIPTRY(hipEventRecord(c->pass_events[2 * n_pass + 1], sm));
-        c->pass_kind.resize(n_pass + 1);
-        c->pass_kind[n_pass] = 3;                      // 3: k_stay_by_top verified the pass
-        n_pass++;
-        c->last_stays[m] = P;
-        if (dump_pass(c, a.it, m, P, OW, c->chain_oi.as<int32_t>())) return BLANCE_ERR_DEVICE;
-        if (a.tail) {
-            *a.tail = SweepTail{true, true, m, OW, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>(),
-                                run.pending ? run.gate : kNoGate};
-        } else {
-            BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(),
-                                 run.pending ? run.gate : kNoGate);
-            launches++;
-        }
-        *batched_io += P;
-        *done = true;
-        *launches_io += launches;
-        return 0;
-    }
-    // a fresh plan's first sweep: every step blank -> the lean kernel; it either does this rank's
-    // whole slice or changes nothing that is not restored below (a rank-local decision: the full
-    // kernel makes the same choices)
-    bool lean = false;
-    if (NP == 0 && !run.no_lean && !c->any_node_weight && rr.max_size <= 256 && k <= 4 && !cfl[0]) {
-        bool walked = false;
-        if (c->periodic && !sharded && n_events == 0 && !cfl[6] && !cfl[7]) {
-            // k_period.h: regions whose records repeat are walked for two periods; the rest of the periodic stretch is
-            // copied, what lies behind it is walked -- all decided on the device, region by region
-            int max_len = 0;
-            for (int r = 0; r < B; r++) max_len = std::max(max_len, (int)(c->h_reg_off[r + 1] - c->h_reg_off[r]));
-            if (max_len >= kPeriodMinRounds * 2) {
-                RESERVE(period, sizeof(int32_t) * ((size_t)kPWords * B + 1));
-                RESERVE(cnt_p1, sizeof(int32_t) * (cnt_words + 1));
-                int32_t* pb = c->period.as<int32_t>();
-                const int gx = cdiv(max_len, 256), gl = cdiv(rr.max_size, 64);
-                BLANCE_LAUNCH_NOSYNC(k_period_init, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, pb);
-                const int gf = cdiv(std::min(max_len, kPeriodCap + 1), 256);
-                BLANCE_LAUNCH_NOSYNC(k_period_find, gf * B, 256, 0, sm, B, gf, cq.reg_off, cq.crec, pb);
-                const int gv = cdiv((long long)max_len * (kCW / 4), 256);
-                BLANCE_LAUNCH_NOSYNC(k_period_verify, gv * B, 256, 0, sm, B, gv, cq.reg_off, cq.crec, pb);
-                if (c->periodic_cut > 0) BLANCE_LAUNCH_NOSYNC(k_period_clamp, cdiv(B, 64), 64, 0, sm, B, c->periodic_cut, pb);
-                BLANCE_LAUNCH_NOSYNC(k_period_segments, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, pb);
-                ChainParams sq = cq;
-                sq.seg_beg = pb + (size_t)kPBeg1 * B; sq.seg_end = pb + (size_t)kPEnd1 * B;
-                // (the plane automaton for regions of up to 128 leaves, the lane-minimum kernel for wider ones)
-                auto walk = [&](const ChainParams& p) {
-                    if (c->no_planes || !launch_chain_planes(sm, p, rr.max_size)) launch_chain_blank(sm, p, rr.max_size);
-                };
-                {
-                    walk(sq);
-                    walked = true;
-                    HIPTRY(hipMemcpyAsync(c->cnt_p1.p, c->cnt.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
-                    sq.seg_beg = pb + (size_t)kPBeg2 * B; sq.seg_end = pb + (size_t)kPEnd2 * B;
-                    walk(sq);
-                    BLANCE_LAUNCH_NOSYNC(k_period_state_max, gl * B, 64, 0, sm, B, gl, m, N, NX, cq.reg_lo, cq.reg_hi, cq.leaf_node,
-                                         cq.alive, c->cnt_p1.as<int32_t>(), cq.cnt, pb);
-                    BLANCE_LAUNCH_NOSYNC(k_period_state_check, gl * B, 64, 0, sm, B, gl, m, N, NX, cq.reg_lo, cq.reg_hi, cq.leaf_node,
-                                         cq.alive, c->cnt_p1.as<int32_t>(), cq.cnt, pb);
-                    BLANCE_LAUNCH_NOSYNC(k_period_verdict, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, cq.flags, pb);
-                    BLANCE_LAUNCH_NOSYNC(k_period_replicate, gx * B, 256, 0, sm, B, gx, OW, cq.reg_off, pb, cq.out);
-                    BLANCE_LAUNCH(k_period_counts, B, 256, 0, sm, B, m, N, NX, OW, cq.reg_off, cq.reg_lo, cq.reg_hi, cq.leaf_node,
-                                  cq.alive, cq.crec, cq.out, pb, cq.cnt);
-                    sq.seg_beg = pb + (size_t)kPBeg3 * B; sq.seg_end = pb + (size_t)kPEnd3 * B;
-                    walk(sq);
-                    launches += 11;
-                    c->periodic_passes++;
-                    if (c->trace) {
-                        std::vector<int32_t> hp((size_t)kPWords * B);
-                        HIPTRY(hipMemcpyAsync(hp.data(), pb, sizeof(int32_t) * hp.size(), hipMemcpyDeviceToHost, sm));
-                        HIPTRY(stream_sync(c));
-                        int64_t copied = 0; int n_ok = 0;
-                        for (int r = 0; r < B; r++)
-                            if (hp[(size_t)kPOk * B + r]) { n_ok++; copied += hp[(size_t)kPLimit * B + r] - 2 * hp[(size_t)kPT * B + r]; }
-                        fprintf(stderr, "[blance] chain pass state %d: periodic records in %d of %d regions (period %d in the first), %lld of %d steps copied\n",
-                                m, n_ok, B, hp[(size_t)kPT * B], (long long)copied, P);
-                    }
-                }
-            }
-        }
-        if (!walked && (c->no_planes || !launch_chain_planes(sm, cq, rr.max_size))) launch_chain_blank(sm, cq, rr.max_size);
-        int32_t fl[8] = {0};
-        launches++;
-        if (defer) {                                    // (taken to have done the pass until the caller's readback says otherwise)
-            run.pending = 2;
-            run.gate = gate_on(1u | 2u);
-        } else {
-            HIPTRY(read_back(c, fl, scal + 4, sizeof fl));
-            HIPTRY(stream_sync(c));
-            if (refuted(fl)) {
-                HIPTRY(hipMemcpyAsync(c->cnt.p, c->cnt_save.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
-                run.redo = true;
-                *launches_io += launches;
-                return 0;
-            }
-        }
-        if (c->trace) fprintf(stderr, "[blance] chain pass state %d: all-blank kernel (%s) %s\n", m, c->no_planes ? "lanes" : "planes",
-                              run.pending ? "launched, its flags are read with the sweep's" : !fl[0] && !fl[1] ? "did the pass" : "escaped");
-        if (!fl[0] && !fl[1]) {
-            lean = true;
-        } else if (!fl[0]) {                            // not all blank: the full kernel, from the same state
-            HIPTRY(hipMemcpyAsync(c->cnt.p, sharded ? c->cnt_base.p : c->cnt_save.p, sizeof(int32_t) * cnt_words,
-                                  hipMemcpyDeviceToDevice, sm));
-            if (cfl[6] && !sharded)
-                BLANCE_LAUNCH_NOSYNC(k_chain_orphans, cdiv(P, 256), 256, 0, sm, d, m, h.top_state,
-                                     a.order, rr.node_region.as<int32_t>(), c->cnt.as<int32_t>());
-            HIPTRY(hipMemsetAsync(scal + 4, 0, 16, sm));
-        }
-    }
-    if (!lean) {
-        if (NP > 0 && !chain_rows_in_lds(cq, rr.max_size)) NTNTRY();      // (rows in LDS: the matrix in HBM is not touched)
-        if (!dispatch_chain(c, cq, rr.max_size)) return fail(BLANCE_ERR_UNSUPPORTED, "region chain shape");
-    }
-    HIPTRY(hipEventRecord(c->pass_events[2 * n_pass + 1], sm));
-    launches += 8;
-    c->pass_kind.resize(n_pass + 1);
-    c->pass_kind[n_pass] = lean ? 2 : 0;           // 2: the all-blank kernel did the pass
-    n_pass++;
-    int32_t fl[kXHead] = {0};
-    if (sharded) {
-        // collective A: [flags | this rank's change of the load vector]
-        int32_t* xb = c->xbuf.as<int32_t>();
-        HIPTRY(hipMemsetAsync(xb, 0, sizeof(int32_t) * kXHead, sm));
-        HIPTRY(hipMemcpyAsync(xb, scal + 4, 32, hipMemcpyDeviceToDevice, sm));
-        BLANCE_LAUNCH_NOSYNC(k_vec_sub, cdiv((int64_t)cnt_words, 256), 256, 0, sm, (int)cnt_words, c->cnt.as<int32_t>(),
-                             c->cnt_base.as<int32_t>(), xb + kXHead);
-        *a_done = true;
-        COMMTRY(comm_allreduce(c, xb, (int64_t)(kXHead + cnt_words)));
-        HIPTRY(read_back(c, fl, xb, sizeof fl));
-        launches++;
-    } else if (!lean) {                              // (the all-blank kernel's flags were read above: all clear)
-        if (defer) {
-            run.pending = 3;
-            run.gate = gate_on(1u | 2u);
-        } else {
-            HIPTRY(read_back(c, fl, scal + 4, 32));
-        }
-    }
-    if (!run.pending && (sharded || !lean)) HIPTRY(stream_sync(c));
-    if (fl[8]) return fail(BLANCE_ERR_COMM, "another rank of the sharded plan failed");
-    if (!run.pending && !lean && refuted(fl)) {      // (the all-blank kernel's words were checked above)
-        c->pass_ntn_ready = false;
-        HIPTRY(hipMemcpyAsync(c->cnt.p, c->cnt_save.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
-        n_pass--;
-        run.redo = true;
-        *launches_io += launches;
-        return 0;
-    }
-    if (c->trace && !run.pending)
-        fprintf(stderr, "[blance] chain pass state %d: %d of %d steps committed as verified stays in %d batches\n",
-                m, fl[2], P, fl[3]);
-    c->last_stays[m] = (!fl[0] && !fl[1]) ? fl[2] : 0;          // (a pending verdict: the caller fills this in)
-    if (!fl[0] && !fl[1]) {
-        if (sharded) {
-            // every rank's chains wrote their own regions' loads and their own steps' outputs
-            int32_t* xb = c->xbuf.as<int32_t>();
-            BLANCE_LAUNCH_NOSYNC(k_vec_add, cdiv((int64_t)cnt_words, 256), 256, 0, sm, (int)cnt_words, c->cnt_base.as<int32_t>(),
-                                 xb + kXHead, c->cnt.as<int32_t>());
-            launches++;
-            if (gather_out) {
-                // collective B: a rank's steps are contiguous in chain order
-                const int32_t* ro = c->h_reg_off.data();
-                int64_t per = 0;
-                for (int r = 0; r < G; r++) {
-                    const int64_t len = (int64_t)(ro[slice_lo(r + 1)] - ro[slice_lo(r)]) * OW;
-                    if (len > per) per = len;
-                }
-                if (per > 0) {
-                    RESERVE(gath, sizeof(int32_t) * ((size_t)per * G + 1));
-                    int32_t* gb = c->gath.as<int32_t>();
-                    const int64_t mine = (int64_t)(ro[slice_lo(rank + 1)] - ro[slice_lo(rank)]) * OW;
-                    if (mine > 0)
-                        HIPTRY(hipMemcpyAsync(gb + (size_t)rank * per, c->out.as<int32_t>() + (size_t)ro[slice_lo(rank)] * OW,
-                                              sizeof(int32_t) * (size_t)mine, hipMemcpyDeviceToDevice, sm));
-                    COMMTRY(comm_allgather(c, gb, per));
-                    for (int r = 0; r < G; r++) {
-                        const int64_t len = (int64_t)(ro[slice_lo(r + 1)] - ro[slice_lo(r)]) * OW;
-                        if (r != rank && len > 0)
-                            HIPTRY(hipMemcpyAsync(c->out.as<int32_t>() + (size_t)ro[slice_lo(r)] * OW, gb + (size_t)r * per,
-                                                  sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToDevice, sm));
-                    }
-                }
-            } else {
-                COMMTRY(comm_allreduce(c, c->out.as<int32_t>(), (int64_t)P * OW));
-            }
-        }
-        if (dump_pass(c, a.it, m, P, OW, c->chain_oi.as<int32_t>())) return BLANCE_ERR_DEVICE;
-        if (a.tail) {
-            *a.tail = SweepTail{true, true, m, OW, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>(),
-                                run.pending ? run.gate : kNoGate};
-        } else {
-            BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(),
-                                 run.pending ? run.gate : kNoGate);
-            launches++;
-        }
-        *batched_io += P;
-        *done = true;
-    } else {                                        // not region-local after all: redo in order
-        c->pass_ntn_ready = false;                  // (chains of big regions keep their rows in global memory: zeroed again on demand)
-        HIPTRY(hipMemcpyAsync(c->cnt.p, c->cnt_save.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
-    }
-    *launches_io += launches;
     return 0;
 }
 
-static int run_chain_pass(blance_ctx* c, const ChainPassArgs& a, int64_t* launches_io, int64_t* batched_io, int* n_pass_io,
-                          bool* done, bool* a_done, ChainRun& run) {
-    int e = run_chain_pass_once(c, a, launches_io, batched_io, n_pass_io, done, a_done, run);
+// k_stay_by_top: every step of the pass checked as a stay, one thread per top priority node.  *stayed: the pass is done
+// (or, its verdict deferred, taken to be).
+int ChainPass::stay_attempt(bool* stayed) {
+    *stayed = false;
+    if (!group_stands) {
+        const int ge = group_by_top(sm, c->scan_sums);
+        if (ge) return ge;
+    } else if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps' grouping by top priority node stands\n", m);
+    StayParams sq;
+    fill_pass_common(c, sq, m, a.k, a.NP);
+    fill_region_tables(c, rr, sq);
+    sq.wg_region = rr.wg_region.as<int32_t>(); sq.wg_chunk = rr.wg_chunk.as<int32_t>();
+    sq.crec = c->crec.as<int32_t>();
+    sq.top_off = c->top_off.as<int32_t>(); sq.top_order = c->top_order.as<int32_t>();
+    sq.out = c->out.as<int32_t>(); sq.flag = flags + kFlagStayMoved;
+    sq.gate = top_gate;
+    if (!launch_stay_by_top(sm, sq, rr.n_stay_wgs, rr.max_size)) return 0;
+    pr.launches += 1;
+    if (defer) {
+        *stayed = true;                                 // (until the caller's readback says otherwise)
+        run.pending = Pending::kStayTop;
+        run.gate = gate_on((1u << kFlagNotLocal) | (1u << kFlagStayMoved));
+        if (c->trace) fprintf(stderr, "[blance] chain pass state %d: stays per top priority node, the verdict is read with the sweep's\n", m);
+        return 0;
+    }
+    int32_t sf[kChainFlags] = {0}, moved = 0;           // sf[kFlagNotLocal]: k_gather_chain's; moved: not all stays
+    HIPTRY(read_back(c, sf, flags, sizeof sf));
+    HIPTRY(read_back(c, &moved, flags + kFlagStayMoved, sizeof moved));
+    HIPTRY(stream_sync(c));
+    if (refuted(sf)) {                                  // (k_stay_by_top changes no counter)
+        run.redo = true;
+        return 0;
+    }
+    *stayed = !sf[kFlagNotLocal] && !moved;
+    if (c->trace) fprintf(stderr, "[blance] chain pass state %d: stays verified per top priority node: %s\n", m, *stayed ? "all of them" : "no");
+    return 0;
+}
+
+// k_period.h: regions whose records repeat are walked for two periods; the rest of the periodic stretch is copied, what
+// lies behind it is walked -- all decided on the device, region by region.  *walked: the walk has been launched.
+int ChainPass::periodic_walk(bool* walked) {
+    const int N = h.n_nodes, NX = h.n_nodes_ext;
+    *walked = false;
+    int max_len = 0;
+    for (int r = 0; r < B; r++) max_len = std::max(max_len, (int)(c->h_reg_off[r + 1] - c->h_reg_off[r]));
+    if (max_len < kPeriodMinRounds * 2) return 0;
+    RESERVE(period, sizeof(int32_t) * ((size_t)kPWords * B + 1));
+    RESERVE(cnt_p1, sizeof(int32_t) * (cnt_words + 1));
+    int32_t* pb = c->period.as<int32_t>();
+    const int gx = cdiv(max_len, 256), gl = cdiv(rr.max_size, 64);
+    BLANCE_LAUNCH_NOSYNC(k_period_init, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, pb);
+    const int gf = cdiv(std::min(max_len, kPeriodCap + 1), 256);
+    BLANCE_LAUNCH_NOSYNC(k_period_find, gf * B, 256, 0, sm, B, gf, cq.reg_off, cq.crec, pb);
+    const int gv = cdiv((long long)max_len * (kCW / 4), 256);
+    BLANCE_LAUNCH_NOSYNC(k_period_verify, gv * B, 256, 0, sm, B, gv, cq.reg_off, cq.crec, pb);
+    if (c->periodic_cut > 0) BLANCE_LAUNCH_NOSYNC(k_period_clamp, cdiv(B, 64), 64, 0, sm, B, c->periodic_cut, pb);
+    BLANCE_LAUNCH_NOSYNC(k_period_segments, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, pb);
+    ChainParams sq = cq;
+    // (the plane automaton for regions of up to 128 leaves, the lane-minimum kernel for wider ones)
+    auto walk = [&](int beg_row, int end_row) {
+        sq.seg_beg = pb + (size_t)beg_row * B; sq.seg_end = pb + (size_t)end_row * B;
+        if (c->no_planes || !launch_chain_planes(sm, sq, rr.max_size)) launch_chain_blank(sm, sq, rr.max_size);
+    };
+    walk(kPBeg1, kPEnd1);
+    *walked = true;
+    HIPTRY(hipMemcpyAsync(c->cnt_p1.p, c->cnt.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
+    walk(kPBeg2, kPEnd2);
+    BLANCE_LAUNCH_NOSYNC(k_period_state_max, gl * B, 64, 0, sm, B, gl, m, N, NX, cq.reg_lo, cq.reg_hi, cq.leaf_node,
+                         cq.alive, c->cnt_p1.as<int32_t>(), cq.cnt, pb);
+    BLANCE_LAUNCH_NOSYNC(k_period_state_check, gl * B, 64, 0, sm, B, gl, m, N, NX, cq.reg_lo, cq.reg_hi, cq.leaf_node,
+                         cq.alive, c->cnt_p1.as<int32_t>(), cq.cnt, pb);
+    BLANCE_LAUNCH_NOSYNC(k_period_verdict, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, cq.flags, pb);
+    BLANCE_LAUNCH_NOSYNC(k_period_replicate, gx * B, 256, 0, sm, B, gx, OW, cq.reg_off, pb, cq.out);
+    BLANCE_LAUNCH(k_period_counts, B, 256, 0, sm, B, m, N, NX, OW, cq.reg_off, cq.reg_lo, cq.reg_hi, cq.leaf_node,
+                  cq.alive, cq.crec, cq.out, pb, cq.cnt);
+    walk(kPBeg3, kPEnd3);
+    pr.launches += 11;
+    if (c->trace) {
+        std::vector<int32_t> hp((size_t)kPWords * B);
+        HIPTRY(hipMemcpyAsync(hp.data(), pb, sizeof(int32_t) * hp.size(), hipMemcpyDeviceToHost, sm));
+        HIPTRY(stream_sync(c));
+        int64_t copied = 0; int n_ok = 0;
+        for (int r = 0; r < B; r++)
+            if (hp[(size_t)kPOk * B + r]) { n_ok++; copied += hp[(size_t)kPLimit * B + r] - 2 * hp[(size_t)kPT * B + r]; }
+        fprintf(stderr, "[blance] chain pass state %d: periodic records in %d of %d regions (period %d in the first), %lld of %d steps copied\n",
+                m, n_ok, B, hp[(size_t)kPT * B], (long long)copied, P);
+    }
+    return 0;
+}
+
+// a fresh plan's first sweep: every step blank -> the lean kernel; it either does this rank's
+// whole slice or changes nothing that is not restored below (a rank-local decision: the full
+// kernel makes the same choices).  *lean: it did the pass (or, its verdict deferred, is taken to have).
+int ChainPass::blank_walk(bool* lean) {
+    *lean = false;
+    if (!(a.NP == 0 && !run.no_lean && !c->any_node_weight && rr.max_size <= 256 && a.k <= 4 && !cfl[kFlagNotLocal])) return 0;
+    bool walked = false;
+    if (c->periodic && !sharded && n_events == 0 && !cfl[kFlagOrphans] && !cfl[kFlagEvents]) {
+        const int pe = periodic_walk(&walked);
+        if (pe) return pe;
+    }
+    if (!walked && (c->no_planes || !launch_chain_planes(sm, cq, rr.max_size))) launch_chain_blank(sm, cq, rr.max_size);
+    int32_t fl[kChainFlags] = {0};
+    pr.launches++;
+    if (defer) {                                        // (taken to have done the pass until the caller's readback says otherwise)
+        run.pending = Pending::kBlank;
+        run.gate = gate_on((1u << kFlagNotLocal) | (1u << kFlagEscaped));
+    } else {
+        HIPTRY(read_back(c, fl, flags, sizeof fl));
+        HIPTRY(stream_sync(c));
+        if (refuted(fl)) {
+            run.redo = true;
+            return restore_counters();
+        }
+    }
+    if (c->trace) fprintf(stderr, "[blance] chain pass state %d: all-blank kernel (%s) %s\n", m, c->no_planes ? "lanes" : "planes",
+                          run.pending != Pending::kNone ? "launched, its flags are read with the sweep's" :
+                          !fl[kFlagNotLocal] && !fl[kFlagEscaped] ? "did the pass" : "escaped");
+    if (!fl[kFlagNotLocal] && !fl[kFlagEscaped]) {
+        *lean = true;
+    } else if (!fl[kFlagNotLocal]) {                    // not all blank: the full kernel, from the same state
+        HIPTRY(hipMemcpyAsync(c->cnt.p, sharded ? c->cnt_base.p : c->cnt_save.p, sizeof(int32_t) * cnt_words,
+                              hipMemcpyDeviceToDevice, sm));
+        if (cfl[kFlagOrphans] && !sharded) uncount_orphans();
+        HIPTRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * (kFlagStayBatches + 1), sm));
+    }
+    return 0;
+}
+
+// collective A of a sharded pass: [flags | this rank's change of the load vector], summed over the ranks; fl: the header
+int ChainPass::collective_a(int32_t* fl) {
+    int32_t* xb = c->xbuf.as<int32_t>();
+    HIPTRY(hipMemsetAsync(xb, 0, sizeof(int32_t) * kXHead, sm));
+    HIPTRY(hipMemcpyAsync(xb, flags, sizeof(int32_t) * kChainFlags, hipMemcpyDeviceToDevice, sm));
+    BLANCE_LAUNCH_NOSYNC(k_vec_sub, cdiv((int64_t)cnt_words, 256), 256, 0, sm, (int)cnt_words, c->cnt.as<int32_t>(),
+                         c->cnt_base.as<int32_t>(), xb + kXHead);
+    run.a_done = true;
+    COMMTRY(comm_allreduce(c, xb, (int64_t)(kXHead + cnt_words)));
+    HIPTRY(read_back(c, fl, xb, sizeof(int32_t) * kXHead));
+    pr.launches++;
+    return 0;
+}
+
+// A sharded pass that stands: every rank's chains wrote their own regions' loads and their own steps' outputs.  The loads
+// are those of collective A; collective B brings the outputs together.
+int ChainPass::collective_b() {
+    int32_t* xb = c->xbuf.as<int32_t>();
+    BLANCE_LAUNCH_NOSYNC(k_vec_add, cdiv((int64_t)cnt_words, 256), 256, 0, sm, (int)cnt_words, c->cnt_base.as<int32_t>(),
+                         xb + kXHead, c->cnt.as<int32_t>());
+    pr.launches++;
+    if (!gather_out) {
+        COMMTRY(comm_allreduce(c, c->out.as<int32_t>(), (int64_t)P * OW));
+        return 0;
+    }
+    // a rank's steps are contiguous in chain order
+    const int32_t* ro = c->h_reg_off.data();
+    int64_t per = 0;
+    for (int r = 0; r < G; r++) {
+        const int64_t len = (int64_t)(ro[slice_lo(r + 1)] - ro[slice_lo(r)]) * OW;
+        if (len > per) per = len;
+    }
+    if (per <= 0) return 0;
+    RESERVE(gath, sizeof(int32_t) * ((size_t)per * G + 1));
+    int32_t* gb = c->gath.as<int32_t>();
+    const int64_t mine = (int64_t)(ro[slice_lo(rank + 1)] - ro[slice_lo(rank)]) * OW;
+    if (mine > 0)
+        HIPTRY(hipMemcpyAsync(gb + (size_t)rank * per, c->out.as<int32_t>() + (size_t)ro[slice_lo(rank)] * OW,
+                              sizeof(int32_t) * (size_t)mine, hipMemcpyDeviceToDevice, sm));
+    COMMTRY(comm_allgather(c, gb, per));
+    for (int r = 0; r < G; r++) {
+        const int64_t len = (int64_t)(ro[slice_lo(r + 1)] - ro[slice_lo(r)]) * OW;
+        if (r != rank && len > 0)
+            HIPTRY(hipMemcpyAsync(c->out.as<int32_t>() + (size_t)ro[slice_lo(r)] * OW, gb + (size_t)r * per,
+                                  sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToDevice, sm));
+    }
+    return 0;
+}
+
+// The pass stands (or is taken to): its list edits go to the sweep's tail or are launched, behind the pending verdict's gate.
+int ChainPass::commit() {
+    if (dump_pass(c, a.it, m, P, OW, c->chain_oi.as<int32_t>())) return BLANCE_ERR_DEVICE;
+    const Gate gate = run.pending != Pending::kNone ? run.gate : kNoGate;
+    if (a.tail) {
+        *a.tail = SweepTail{true, true, m, OW, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>(), gate};
+    } else {
+        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(), gate);
+        pr.launches++;
+    }
+    pr.at.batched += P;
+    run.done = true;
+    return 0;
+}
+
+// 0 = ok (run.done tells whether the pass was made; if not, the counters are as before and the caller
+// runs the pass in order), < 0 = error.
+int ChainPass::run_once() {
+    int e;
+    if ((e = classify_and_group()) || (e = events()) || (e = gather_records())) return e;
+    fill_chain_params();
+    if ((e = start_counters()) || (e = open_timing())) return e;
+    if (try_stay) {
+        bool stayed = false;
+        if ((e = stay_attempt(&stayed)) || run.redo) return e;
+        if (stayed) {
+            if ((e = close_timing(kPassStayTop))) return e;
+            c->last_stays[m] = P;
+            return commit();
+        }
+    }
+    bool lean = false;
+    if ((e = blank_walk(&lean)) || run.redo) return e;
+    if (!lean) {
+        if (a.NP > 0 && !chain_rows_in_lds(cq, rr.max_size)) NTNTRY();      // (rows in LDS: the matrix in HBM is not touched)
+        if (!dispatch_chain(c, cq, rr.max_size)) return fail(BLANCE_ERR_UNSUPPORTED, "region chain shape");
+    }
+    pr.launches += 8;
+    if ((e = close_timing(lean ? kPassBlank : kPassKernel))) return e;
+    int32_t fl[kXHead] = {0};
+    if (sharded) {
+        if ((e = collective_a(fl))) return e;
+    } else if (!lean) {                              // (the all-blank kernel's flags were read above: all clear)
+        if (defer) {
+            run.pending = Pending::kChain;
+            run.gate = gate_on((1u << kFlagNotLocal) | (1u << kFlagEscaped));
+        } else {
+            HIPTRY(read_back(c, fl, flags, sizeof(int32_t) * kChainFlags));
+        }
+    }
+    const bool pending = run.pending != Pending::kNone;
+    if (!pending && (sharded || !lean)) HIPTRY(stream_sync(c));
+    if (fl[kXPoison]) return fail(BLANCE_ERR_COMM, "another rank of the sharded plan failed");
+    if (!pending && !lean && refuted(fl)) {          // (the all-blank kernel's words were checked above)
+        c->pass_ntn_ready = false;
+        pr.at.n_pass--;
+        run.redo = true;
+        return restore_counters();
+    }
+    if (c->trace && !pending)
+        fprintf(stderr, "[blance] chain pass state %d: %d of %d steps committed as verified stays in %d batches\n",
+                m, fl[kFlagStaySteps], P, fl[kFlagStayBatches]);
+    const bool stands = !fl[kFlagNotLocal] && !fl[kFlagEscaped];
+    c->last_stays[m] = stands ? fl[kFlagStaySteps] : 0;         // (a pending verdict: the caller fills this in)
+    if (!stands) {                                  // not region-local after all: redo in order
+        c->pass_ntn_ready = false;                  // (chains of big regions keep their rows in global memory: zeroed again on demand)
+        return restore_counters();
+    }
+    if (sharded && (e = collective_b())) return e;
+    return commit();
+}
+
+static int run_chain_pass(blance_ctx* c, PlanRun& pr, const ChainPassArgs& a, ChainRun& run) {
+    int e = ChainPass(c, pr, a, run).run_once();
     if (e || !run.redo) return e;
-    c->spec_refuted++;
     if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the assumed classification did not hold, the pass runs again\n", a.m);
     run.allow_spec = false;
     run.defer = false;
-    return run_chain_pass_once(c, a, launches_io, batched_io, n_pass_io, done, a_done, run);
+    return ChainPass(c, pr, a, run).run_once();
+}
+
+// One sweep of the plan (plan.go:32's loop body), and what its retries need.
+struct Sweep {
+    int it = 0;
+    bool first = false;
+    int NP = 0, add_nil = 0, any_removed = 0;
+    bool opened = false;           // the last sweep's k_sweep_tail counted this sweep's prevMap into cnt_next and made every
+                                   // present list a non-nil slice
+    int known_passes = 0, known_state = -1, known_k = 0;        // run_flat_pass's `opening`
+    bool known_broken = false;
+    // The sweep's last pass, when it is a chain pass, leaves its verdict on the device (ChainRun::defer) and the words
+    // come back with the convergence word: one round trip for both.  A bad verdict brings the sweep back for that
+    // state alone (retry says how), with everything the pass enqueued behind its gate undone by never having run.
+    int m_from = 0;
+    ChainRun retry;
+    bool retrying = false, counted = false;
+    bool restore_counters = false;     // the pass that runs again starts from cnt_save
+    // The sweep's first pass, when it is `settled` (run_state_pass), need not be read back either: its stay test leaves a word
+    // on the device (kFlagTopMoved), everything behind it waits for that word, and the word comes back with the convergence
+    // word.  Set, the whole sweep runs again from its first pass with that pass read back (top_spec_off).  This holds only
+    // when every later pass of the sweep keeps its own verdict on the device as well (top_spec_fits), so that nothing of the
+    // sweep is read before its one readback.
+    bool top_spec_off = false;
+    Progress at_open, at_last_pass;    // the plan's progress when the sweep / its last state's pass began
+    std::vector<int64_t> last_stays_open;
+    // of the current round of passes:
+    ChainRun pend;                 // the last pass's deferred verdict
+    SweepTail tail;
+    bool tail_counts = false;      // (this round ended with a counting tail)
+};
+
+// run_chain_pass makes the pass of every state behind m0 from the grouping by region it made last sweep, assumes its
+// classification and defers its verdict: no readback inside
+static bool top_spec_fits(const blance_ctx* c, const PlanRun& pr, const Sweep& sw, int m0) {
+    const blance_problem& h = c->h;
+    if (sw.NP == 0 || !c->top_prio_strict || m0 != h.top_state) return false;
+    for (int t = m0 + 1; t < h.n_states; t++) {
+        const int kt = c->state_constraints[t];
+        if (kt <= 0) continue;
+        if (t != pr.m_last) return false;
+        const int q0 = c->rule_off[t], q1 = c->rule_off[t + 1];
+        if (c->engine == BLANCE_ENGINE_SEQUENTIAL || h.hierarchy_rules_nil || q1 - q0 != 1 || !c->rule_regions[q0].ok ||
+            h.n_parts < c->chain_min_parts || kt > 4)
+            return false;
+        const int B = c->rule_regions[q0].n_regions;
+        if (pass_sharded(c, B)) return false;
+        if (c->chain_group_state != t || !c->chain_group_static || c->h_reg_off.size() != (size_t)B + 1) return false;
+    }
+    return true;
+}
+
+// The sweep's working state as plan.go:53-55, :94 set it up: the live lists, stateNodeCounts = countStateNodes(prevMap).
+static int open_sweep(blance_ctx* c, PlanRun& pr, Sweep& sw) {
+    const blance_problem& h = c->h;
+    const int NX = h.n_nodes_ext, M = h.n_states;
+    const int64_t PM = (int64_t)h.n_parts * M;
+    hipStream_t sm = c->stream;
+    int32_t* scal = c->scalars.as<int32_t>();
+    DevProblem& d = pr.d;
+    d.node_removed = sw.first ? c->node_removed.as<uint8_t>() : c->zeros_nx.as<uint8_t>();   // plan.go:53-55
+    d.node_added = sw.first ? c->node_added.as<uint8_t>() : c->zeros_nx.as<uint8_t>();
+    c->tops_moved = true;                                       // until this sweep's top-state pass turns out to be one run of stays
+    sw.opened = c->tail_counted;
+    c->tail_counted = false;
+    if (sw.opened) std::swap(c->cnt, c->cnt_next);
+    {   // one launch: warn_count / not_match, the chain flags, stateNodeCounts (plan.go:94) unless counted already, the flat
+        // passes' row counts, and the counters this sweep's tail counts the next sweep's into
+        FillCopyJob fj;
+        fj.zero(scal + kScalWarnCount, 2);
+        fj.zero(scal + kScalFlags, kChainFlags);
+        if (!sw.opened) fj.zero(c->cnt.p, (int64_t)(M + 1) * (NX + 1));
+        if (sw.NP > 0 && c->f_row_count.p) fj.zero(c->f_row_count.p, (int64_t)NX + 1);
+        if (pr.fuse) fj.zero(c->cnt_next.p, (int64_t)(M + 1) * (NX + 1));
+        if (run_fill_copy(c, fj)) return BLANCE_ERR_DEVICE;
+        c->flags_clean = true;
+        c->rowcount_clean = sw.NP > 0 && c->f_row_count.p;
+    }
+    if (PM > 0 && !sw.opened) {
+        if (sw.first)
+            BLANCE_LAUNCH_NOSYNC(k_live_init, cdiv(PM, 256), 256, 0, sm, d, c->a_off.as<int32_t>(),
+                                 c->a_nodes.as<int32_t>(), c->a_kind.as<uint8_t>(), c->p_off.as<int32_t>(),
+                                 c->p_nodes.as<int32_t>(), c->p_kind.as<uint8_t>());
+        else
+            BLANCE_LAUNCH_NOSYNC(k_live_refresh, cdiv(PM, 256), 256, 0, sm, d);
+        pr.launches++;
+    }
+    // stateNodeCounts = countStateNodes(prevMap), plan.go:94 (zeroed above)
+    if (h.n_loads > 0) {
+        BLANCE_LAUNCH_NOSYNC(k_count_loads, cdiv(h.n_loads, 256), 256, 0, sm, h.n_loads, NX, sw.first ? 0 : 1,
+                             c->load_state.as<int32_t>(), c->load_node.as<int32_t>(),
+                             c->load_weight.as<int32_t>(), c->load_first.as<uint8_t>(), c->cnt.as<int32_t>());
+        pr.launches++;
+    }
+    if (PM > 0 && !sw.opened) {
+        BLANCE_LAUNCH_NOSYNC(k_count_prev, cdiv(PM, 256), 256, 0, sm, d, c->cnt.as<int32_t>());
+        pr.launches++;
+    }
+    return 0;
+}
+
+// The order of state m's pass (plan.go:542-561): the static order stably partitioned by category in sweep 1, the static
+// order itself wherever every partition has the same category.
+static int pass_order(blance_ctx* c, PlanRun& pr, const Sweep& sw, int m, const int32_t** order) {
+    const int P = c->h.n_parts, n_chunks = cdiv(P, kPartChunk);
+    hipStream_t sm = c->stream;
+    const bool sort_cat = sw.first && !(pr.at.passes_this_sweep == 0 ? c->uniform_first : c->uniform_all);
+    if (sort_cat) {
+        BLANCE_LAUNCH_NOSYNC(k_category, cdiv(P, 256), 256, 0, sm, pr.d, m, sw.any_removed, sw.add_nil, c->cat.as<uint8_t>());
+        BLANCE_LAUNCH(k_part_count, n_chunks, 64, 64, sm, P, (const int32_t*)nullptr, c->cat.as<uint8_t>(),
+                      c->part_order.as<int32_t>(), n_chunks, 3, c->chunk_counts.as<int32_t>());
+        SCANTRY(3 * n_chunks, c->chunk_counts.as<int32_t>());
+        BLANCE_LAUNCH(k_part_scatter, n_chunks, 64, 64, sm, P, (const int32_t*)nullptr, c->cat.as<uint8_t>(),
+                      c->part_order.as<int32_t>(), c->part_order.as<int32_t>(), n_chunks, 3, 2,
+                      c->chunk_counts.as<int32_t>(), c->order.as<int32_t>(), (int32_t*)nullptr);
+    } else {
+        // sweeps >= 2 run with nodesToRemove = nodesToAdd = [] (non-nil, plan.go:53-55): no partition's
+        // nodes are in either, so every category is "1" (plan.go:542-561) and the pass order is the
+        // static order itself
+    }
+    // (the same holds in sweep 1 when every partition has one category, known at upload: uniform_category)
+    *order = sort_cat ? c->order.as<int32_t>() : c->part_order.as<int32_t>();
+    return 0;
+}
+
+struct StatePass {                 // what the paths of one state's pass share
+    int m, k, higher_mask, r0, r1;
+    const int32_t* order;
+};
+
+// State m's pass without region chains: the flat bulk driver, the flat single chain, or the pass kernels in order.
+static int run_pass_in_order(blance_ctx* c, PlanRun& pr, Sweep& sw, const StatePass& sp) {
+    const blance_problem& h = c->h;
+    const int NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts, L = c->L;
+    const int RW = kRecHead + M * (1 + L);       // header + per-state lists
+    const int m = sp.m, k = sp.k;
+    hipStream_t sm = c->stream;
+    int32_t* scal = c->scalars.as<int32_t>();
+    const DevProblem& d = pr.d;
+    int& n_pass = pr.at.n_pass;
+    // (what kind of pass this will be, before its records are made: the flat bulk driver's row bound rides on the gather)
+    const bool flat_state = h.hierarchy_rules_nil || sp.r1 == sp.r0;
+    const bool bulk = c->engine != BLANCE_ENGINE_SEQUENTIAL && flat_state && (k == 1 || (k == 2 && sw.NP == 0)) &&
+                      P >= c->chain_min_parts;
+    const bool count_rows = bulk && sw.NP > 0 && c->f_row_count.p;
+    const bool settled = bulk && !sw.first && pr.at.passes_this_sweep == 1 && !sw.retrying && c->dump_sweep < 0 && c->speculate > 0;
+    const bool assume_stays = settled && pr.top_spec_plan && !sw.top_spec_off && k == 1 && top_spec_fits(c, pr, sw, m);
+    if (count_rows && !assume_stays && rowcount_reset(c)) return BLANCE_ERR_DEVICE;
+    if (!assume_stays)
+        BLANCE_LAUNCH(k_gather, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (RW | 1) + 64, sm, d, m, h.top_state, RW, sp.order,
+                             c->state_stick.as<int32_t>(), c->state_has_stick.as<uint8_t>(), c->rec.as<int32_t>(),
+                             count_rows ? c->f_row_count.as<int32_t>() : (int32_t*)nullptr, NX);
+    PassParams q;
+    fill_pass_common(c, q, m, k, sw.NP);
+    q.L = L; q.P = P; q.top_state = h.top_state;
+    q.RW = RW;
+    q.higher_mask = sp.higher_mask;
+    q.hier = !h.hierarchy_rules_nil;
+    q.rule_begin = sp.r0; q.rule_end = sp.r1;
+    q.n_alive = c->n_alive;
+    q.vertex_empty_anchor = NX;
+    q.node_leaf_pos = c->node_leaf_pos.as<int32_t>();
+    q.anchors = c->anchors.as<AnchorSet>();
+    q.ntn = c->ntn.as<int32_t>();
+    q.rec = c->rec.as<int32_t>();
+    q.out = c->out.as<int32_t>();
+    q.warn_part = c->warn_part.as<int32_t>();
+    q.warn_state = c->warn_state.as<int32_t>();
+    q.warn_count = scal + kScalWarnCount;
+    q.err = scal + kScalErr;
+    q.spec_count = (long long*)(scal + kScalSpecCount);
+    q.beg = 0; q.end = P;
+    // a flat pass (no rule for the state) of a small cluster can run on one wave64
+    bool flat_chain = c->engine != BLANCE_ENGINE_SEQUENTIAL && flat_state && c->flat_chain_ok && k <= 4 &&
+                      P >= c->chain_min_parts;
+    c->no_fast_keys = false;
+    FlatChainPrep fc;
+    fc.possible = flat_chain; fc.d = d; fc.m = m; fc.higher_mask = sp.higher_mask; fc.order = sp.order;
+    if (flat_chain && !bulk) {               // (the bulk driver asks for the records when a sub-range needs them)
+        const int pe = flat_chain_prepare(c, fc, &pr.launches);
+        if (pe) return pe;
+        flat_chain = fc.ok;
+    }
+    HIPTRY(hipEventRecord(c->pass_events[2 * n_pass], sm));
+    int e;
+    bool nothing_to_apply = false;               // (run_flat_pass: a pass of stays that leaves every list as it is)
+    c->pass_kind.resize(n_pass + 1);
+    // the flat bulk driver: k = 1, and the first sweep of a fresh plan (NumPartitions == 0) with k = 2
+    if (bulk) {
+        c->pass_kind[n_pass] = kPassFlatBulk;
+        // (what the sweep's passes so far have been: known_passes of them fresh runs known in advance, the last one
+        // of state known_state with known_k picks a step)
+        const bool opening = sw.first && !sw.retrying && !sw.known_broken &&
+                             (sw.known_passes == 0 || (sw.known_passes == 1 && sw.known_k == 1 && sw.NP == 0 && ((sp.higher_mask >> sw.known_state) & 1)));
+        bool whole_known = false;
+        if (assume_stays) sw.last_stays_open = c->last_stays;
+        e = run_flat_pass(c, q, scal, &pr.launches, &pr.at.batched, fc, opening, &whole_known, settled, assume_stays, &nothing_to_apply,
+                          count_rows);
+        if (assume_stays) {
+            c->top_gate = (1u << kFlagTopMoved) | (1u << kFlagForced);
+            if (c->trace) fprintf(stderr, "[blance] sweep %d: state %d's pass taken to be one run of stays, checked with the sweep's readback\n", sw.it, m);
+        }
+        if (whole_known) { sw.known_passes++; sw.known_state = m; sw.known_k = k; }
+        else sw.known_broken = true;
+    } else if (flat_chain) {
+        sw.known_broken = true;
+        c->pass_kind[n_pass] = kPassKernel;
+        const size_t rows = sizeof(int32_t) * (size_t)(NX + 1) * (NX + 1);
+        e = run_flat_chain(c, q, 0, P, sw.NP > 0 && rows <= 100 * 1024, scal, &pr.launches);
+        if (e > 0) e = fail(BLANCE_ERR_DEVICE, "flat chain refused a checked pass");
+        if (!e) pr.at.batched += P;
+    } else {
+        sw.known_broken = true;
+        c->pass_kind[n_pass] = kPassKernel;
+        e = dispatch_pass(c, q);
+    }
+    if (e) return e;
+    HIPTRY(hipEventRecord(c->pass_events[2 * n_pass + 1], sm));
+    n_pass++;
+    if (dump_pass(c, sw.it, m, P, q.OW, nullptr)) return BLANCE_ERR_DEVICE;
+    if (pr.fuse && m == pr.m_last)
+        sw.tail = SweepTail{true, !nothing_to_apply, m, q.OW, sp.order, nullptr, kNoGate};
+    else if (!nothing_to_apply)
+        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, q.OW, sp.order, c->out.as<int32_t>(), kNoGate);
+    return 0;
+}
+
+// State m's pass (assignStateToPartitions, plan.go:253-303): as region chains when the state's single hierarchy rule allows
+// them, else in order.
+static int run_state_pass(blance_ctx* c, PlanRun& pr, Sweep& sw, int m) {
+    const blance_problem& h = c->h;
+    const int M = h.n_states, P = h.n_parts;
+    StatePass sp;
+    sp.m = m;
+    sp.k = c->state_constraints[m];
+    if (sw.restore_counters) {                                  // (a pass whose deferred verdict came back bad)
+        HIPTRY(hipMemcpyAsync(c->cnt.p, c->cnt_save.p, sizeof(int32_t) * (size_t)(M + 1) * h.n_nodes_ext, hipMemcpyDeviceToDevice, c->stream));
+        sw.restore_counters = false;
+    }
+    const int oe = pass_order(c, pr, sw, m, &sp.order);
+    if (oe) return oe;
+    pr.at.passes_this_sweep++;
+    c->pass_ntn_ready = false;                              // nodeToNodeCounts := fresh (plan.go:266), zeroed when first needed
+    sp.higher_mask = 0;
+    for (int t = 0; t < M; t++)
+        if (c->state_priority[t] < c->state_priority[m]) sp.higher_mask |= 1 << t;
+    sp.r0 = c->rule_off[m]; sp.r1 = c->rule_off[m + 1];
+    while (c->pass_events.size() < 2 * (size_t)(pr.at.n_pass + 2)) {
+        hipEvent_t ev;
+        HIPTRY(hipEventCreate(&ev));
+        c->pass_events.push_back(ev);
+    }
+    // ---- region chains, when the state's single hierarchy rule allows them
+    bool done = false;
+    if (c->engine != BLANCE_ENGINE_SEQUENTIAL && !h.hierarchy_rules_nil && sp.r1 - sp.r0 == 1 &&
+        c->rule_regions[sp.r0].ok && P >= c->chain_min_parts && sp.k <= 4 && !(sw.retrying && sw.retry.skip)) {
+        // (same_tops: the top state's pass was one run of stays AND no other state can take a partition's top priority
+        // node away in between -- plan.go:146-154 keeps only nodes of STRICTLY higher priority states out of a pass)
+        ChainPassArgs ca{m, sp.k, sw.NP, sp.higher_mask, sp.r0, sw.it, sp.order,
+                         !sw.first && !c->tops_moved && m != h.top_state && c->top_prio_strict,
+                         pr.fuse && m == pr.m_last ? &sw.tail : nullptr};
+        ChainRun run;
+        if (sw.retrying) run = sw.retry;
+        run.defer = !sw.retrying && m == pr.m_last;
+        sw.known_broken = true;
+        const int e = run_chain_pass(c, pr, ca, run);
+        if (e) {
+            const bool sharded = pass_sharded(c, c->rule_regions[sp.r0].n_regions);
+            if (sharded && !run.a_done) comm_poison(c);       // the other ranks are (or will be) in collective A
+            if (sharded) comm_abort(c);
+            return e;
+        }
+        if (run.pending != Pending::kNone) sw.pend = run;
+        done = run.done;
+    }
+    if (!done) {
+        const int e = run_pass_in_order(c, pr, sw, sp);
+        if (e) return e;
+    }
+    pr.launches += 7;
+    pr.at.steps += P;
+    return 0;
+}
+
+// The sweep's end: convergence (plan.go:36-45) + write-back (plan.go:49-52), with the last pass's list edits when it left
+// them to the tail.
+static int close_sweep(blance_ctx* c, PlanRun& pr, Sweep& sw) {
+    const blance_problem& h = c->h;
+    const int P = h.n_parts;
+    if (P <= 0) return 0;
+    hipStream_t sm = c->stream;
+    int32_t* scal = c->scalars.as<int32_t>();
+    const DevProblem& d = pr.d;
+    SweepTail& tail = sw.tail;
+    const Gate cg = sw.pend.pending != Pending::kNone ? sw.pend.gate : c->top_gate ? Gate{scal + kScalFlags, c->top_gate} : kNoGate;
+    if (tail.set && tail.scatter && (!tail.inv || tail.gate.flags != cg.flags || tail.gate.mask != cg.mask)) {
+        // (no inverse of the pass order -- a flat pass --, or the list edits wait for other words than the convergence
+        // test: on their own, as before)
+        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.order, c->out.as<int32_t>(), tail.gate);
+        pr.launches++;
+        tail.scatter = false;
+    }
+    if (tail.set) {
+        // the sweep's tail: the list edits, the convergence test and write-back, and -- when another sweep may follow --
+        // that sweep's counters and kinds, in one pass over the partitions
+        int32_t* next = sw.it + 1 < h.max_iterations ? c->cnt_next.as<int32_t>() : nullptr;
+        BLANCE_LAUNCH(k_sweep_tail, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.scatter ? tail.inv : nullptr,
+                      tail.scatter ? c->out.as<int32_t>() : nullptr, scal + kScalNotMatch, next, cg);   // (uses a wave ballot)
+        sw.tail_counts = next != nullptr;
+    } else {
+        BLANCE_LAUNCH(k_converge, cdiv(P, 256), 256, 0, sm, d, scal + kScalNotMatch, cg);   // (uses a wave ballot)
+    }
+    pr.launches++;
+    return 0;
+}
+
+// What the sweep's one readback says about the verdicts the sweep left on the device.
+enum class Verdict {
+    kStands,
+    kSweepAgain,       // the top-state pass was not one run of stays: from the sweep's first pass, that pass read back
+    kPassAgain,        // the last pass's deferred verdict was bad: that state's pass alone, as sw.retry says
+};
+static Verdict sweep_verdict(blance_ctx* c, PlanRun& pr, Sweep& sw) {
+    const int32_t* f = pr.hs + kScalFlags;
+    if (c->top_gate) {
+        const bool moved = f[kFlagTopMoved] || c->speculate == 2;
+        c->top_gate = 0;
+        if (c->trace) fprintf(stderr, "[blance] sweep %d: the first pass %s\n", sw.it, moved ? "was not one run of stays: the sweep runs again" : "was one run of stays");
+        if (moved) {
+            // Nothing behind the gate ran: the live lists, prevMap, the counters and the flag words are as the sweep's
+            // first pass found them.  What the host assumed or cached along the way is dropped.
+            c->last_stays = sw.last_stays_open;
+            c->tops_moved = true;
+            c->chain_group_state = -1;                          // (a gated k_chain_classify wrote no region ids ...)
+            c->group_epoch++;
+            c->top_group_state = -1;                            // (... and a gated k_gather_chain no top priority keys)
+            c->pass_ntn_ready = false;
+            pr.at = sw.at_open;
+            sw.known_passes = 0; sw.known_state = -1; sw.known_k = 0; sw.known_broken = false;
+            sw.retry = ChainRun();
+            sw.retrying = false;
+            sw.top_spec_off = true;
+            pr.top_spec_plan = false;                           // (a plan whose top-state pass moves steps in one later
+                                                                // sweep tends to do so in the next: read them back)
+            sw.m_from = 0;
+            return Verdict::kSweepAgain;
+        }
+    }
+    const Pending pending = sw.pend.pending;
+    if (pending == Pending::kNone) return Verdict::kStands;
+    const bool refuted = (sw.pend.spec && (f[kFlagOrphans] || f[kFlagEvents])) || f[kFlagForced];
+    const bool bad = f[kFlagNotLocal] || (pending == Pending::kStayTop ? f[kFlagStayMoved] : f[kFlagEscaped]);
+    if (c->trace)
+        fprintf(stderr, "[blance] chain pass state %d: deferred verdict (%s): %s; %d verified stays in %d batches\n", pr.m_last,
+                pending == Pending::kStayTop ? "k_stay_by_top" : pending == Pending::kBlank ? "all-blank kernel" : "chain kernel",
+                refuted ? "assumption refuted" : bad ? "the pass did not stand" : "stands", f[kFlagStaySteps], f[kFlagStayBatches]);
+    if (!refuted && !bad) {
+        if (pending == Pending::kChain) c->last_stays[pr.m_last] = f[kFlagStaySteps];
+        return Verdict::kStands;
+    }
+    // nothing behind the gate ran: the live lists and prevMap are as the pass found them; the counters are not
+    sw.retry = ChainRun();
+    if (refuted) sw.retry.allow_spec = false;
+    else if (pending == Pending::kStayTop) sw.retry.no_stay = true;
+    else if (pending == Pending::kBlank) sw.retry.no_lean = true;
+    else sw.retry.skip = true;                                  // (straight to the pass in order)
+    if (pending != Pending::kStayTop || refuted) {              // (k_stay_by_top changes no counter)
+        c->pass_ntn_ready = false;
+        sw.restore_counters = true;
+    }
+    pr.at = sw.at_last_pass;
+    sw.retrying = true;
+    sw.m_from = pr.m_last;
+    return Verdict::kPassAgain;
+}
+
+static void fill_result(const PlanStats& s, blance_result* res) {
+    res->n_warnings = s.n_warnings;
+    res->iterations = s.iterations;
+    res->converged = s.converged;
+    res->device_ms = s.device_ms;
+    res->steps_total = s.steps_total;
+    res->steps_sequential = s.steps_total - s.steps_batched;
+    res->steps_batched = s.steps_batched;
+    res->kernel_launches = s.kernel_launches;
+    res->pass_kernel_ms = s.pass_ms;
+    res->pass_kernel_launches = s.pass_launches;
+    res->flat_pass_ms = s.flat_ms;
+    res->flat_passes = s.flat_passes;
+    res->blank_pass_ms = s.blank_ms;
+    res->blank_pass_launches = s.blank_launches;
+    res->stay_pass_ms = s.stay_ms;
+    res->stay_pass_launches = s.stay_launches;
+    res->host_syncs = s.host_syncs;
+}
+
+// The plan's end: event times and statistics into c->stats.
+static int finish_plan(blance_ctx* c, PlanRun& pr, int64_t syncs0) {
+    PlanStats& s = c->stats;
+    const int64_t n_warnings = pr.iterations == 0 ? 0 : s.n_warnings;     // (counted sweep by sweep)
+    s = PlanStats();
+    HIPTRY(hipEventRecord(c->ev1, c->stream));
+    long long spec = 0, qs[4] = {0, 0, 0, 0};
+    memcpy(&spec, pr.hs + kScalSpecCount, sizeof spec);
+    memcpy(qs, pr.hs + kScalQueueStats, sizeof qs);
+    HIPTRY(hipEventSynchronize(c->ev1));
+    comm_sum_up(c);
+    c->queue_moved = qs[0]; c->queue_exact = qs[1]; c->queue_rebuilds = qs[2]; c->queue_dense = qs[3];
+    if (c->trace || getenv("BLANCE_QUEUE_STATS"))
+        fprintf(stderr, "[blance] k_pass_queue: %lld launches, %lld stops, %lld moving steps (%lld with matrix reads, %lld scoring every node), %lld window rebuilds\n",
+                (long long)c->queue_launches, (long long)c->queue_stops, qs[0], qs[1], qs[3], qs[2]);
+    int64_t batched = pr.at.batched + spec;
+    if (batched > pr.at.steps) batched = pr.at.steps;     // the flat chain counts its whole pass already
+    if (c->trace) fprintf(stderr, "[blance] sequential passes: %lld verified stays\n", spec);
+    float ms = 0.f;
+    HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    for (int i = 0; i < pr.at.n_pass; i++) {
+        float pm = 0.f;
+        HIPTRY(hipEventElapsedTime(&pm, c->pass_events[2 * i], c->pass_events[2 * i + 1]));
+        const PassKind kind = c->pass_kind[i];
+        if (kind != kPassFlatBulk) { s.pass_ms += pm; s.pass_launches++; } else { s.flat_ms += pm; s.flat_passes++; }
+        if (kind == kPassBlank) { s.blank_ms += pm; s.blank_launches++; }
+        if (kind == kPassStayTop) { s.stay_ms += pm; s.stay_launches++; }
+        if (c->trace)
+            fprintf(stderr, "[blance] pass %d (%s): %.3f ms\n", i,
+                    kind == kPassFlatBulk ? "flat bulk driver" : kind == kPassBlank ? "all-blank chain kernel" :
+                    kind == kPassStayTop ? "k_stay_by_top" : "pass kernel", pm);
+    }
+    s.iterations = pr.iterations;
+    s.converged = pr.converged;
+    s.n_warnings = n_warnings;
+    s.device_ms = ms;
+    s.host_syncs = c->n_syncs - syncs0;
+    s.steps_total = pr.at.steps;
+    s.steps_batched = batched;
+    s.kernel_launches = pr.launches;
+    return 0;
 }
 
 static int plan_locked(blance_ctx* c, blance_result* res) {
     if (!c->uploaded) return fail(BLANCE_ERR_BAD_ARG, "no problem uploaded");
     HIPTRY(hipSetDevice(c->device));
     const blance_problem& h = c->h;
-    const int N = h.n_nodes, NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts, L = c->L;
-    const int64_t PM = (int64_t)P * M;
-    const int RW = kRecHead + M * (1 + L);       // header + per-state lists
+    const int M = h.n_states, P = h.n_parts;
     hipStream_t sm = c->stream;
     int32_t* scal = c->scalars.as<int32_t>();
-    int64_t launches = 0, steps = 0, batched = 0;
-    int n_pass = 0;
 
-    DevProblem d = dev_problem(c);
+    PlanRun pr;
+    pr.d = dev_problem(c);
     c->last_stays.assign((size_t)(M > 0 ? M : 1), 0);
     c->queue_launches = c->queue_stops = 0;
     c->comm_events_used = 0;
@@ -2268,423 +2799,65 @@ static int plan_locked(blance_ctx* c, blance_result* res) {
     c->tail_counted = false;
     if (c->side_pending) { HIPTRY(hipStreamSynchronize(c->side)); c->side_pending = false; }
     const int64_t syncs0 = c->n_syncs;
-    // Each sweep ends with k_sweep_tail (the last pass's list edits, the convergence test and write-back, and the next
-    // sweep's counters and kinds) -- not on a sharded plan, whose ranks scatter the pass's gathered outputs one by one.
-    const bool fuse = c->fused_tail && !(c->comm.n_ranks > 1 || c->shard_one_rank);
+    pr.fuse = c->fused_tail && !comm_active(c);
 
     HIPTRY(hipEventRecord(c->ev0, sm));
-    HIPTRY(hipMemsetAsync(scal, 0, 256, sm));
+    HIPTRY(hipMemsetAsync(scal, 0, sizeof(int32_t) * kScalWords, sm));
     if (c->speculate == 2) {                                         // (tests: every deferred verdict comes back bad, every gate is closed)
         static const int32_t one = 1;
-        HIPTRY(hipMemcpyAsync(scal + 4 + kFlagForced, &one, sizeof one, hipMemcpyHostToDevice, sm));
+        HIPTRY(hipMemcpyAsync(scal + kScalFlags + kFlagForced, &one, sizeof one, hipMemcpyHostToDevice, sm));
     }
     if (P > 0) {
         BLANCE_LAUNCH_NOSYNC(k_flags_init, cdiv(P, 256), 256, 0, sm, P, c->part_in_prev.as<uint8_t>(), c->part_never_equal.as<uint8_t>(),
-                             d.in_prev, d.never_equal);
+                             pr.d.in_prev, pr.d.never_equal);
     }
-    int iterations = 0, converged = 0;
-    int32_t hs[32] = {0};                                            // the scalar words read back after every sweep
-    int m_last = -1;                                                 // the last state a sweep makes a pass for
     for (int m = 0; m < M; m++)
-        if (c->state_constraints[m] > 0 && P > 0) m_last = m;
-    bool top_spec_plan = true;                                       // (no sweep of this plan has refuted it: see top_spec_off)
+        if (c->state_constraints[m] > 0 && P > 0) pr.m_last = m;
     for (int it = 0; it < h.max_iterations; it++) {                 // plan.go:32
-        const bool first = it == 0;
-        d.node_removed = first ? c->node_removed.as<uint8_t>() : c->zeros_nx.as<uint8_t>();   // plan.go:53-55
-        d.node_added = first ? c->node_added.as<uint8_t>() : c->zeros_nx.as<uint8_t>();
-        const int add_nil = first ? h.nodes_to_add_nil : 0;
-        const int any_removed = first ? c->any_removed : 0;
-        const int NP = first ? h.n_prev : c->np_later;
-        c->tops_moved = true;                                       // until this sweep's top-state pass turns out to be one run of stays
-        // the last sweep's k_sweep_tail counted this sweep's prevMap into cnt_next and made every present list a non-nil slice
-        const bool opened = c->tail_counted;
-        c->tail_counted = false;
-        if (opened) std::swap(c->cnt, c->cnt_next);
-        {   // one launch: warn_count / not_match, the chain flags, stateNodeCounts (plan.go:94) unless counted already, the flat
-            // passes' row counts, and the counters this sweep's tail counts the next sweep's into
-            FillCopyJob fj;
-            fj.zero(scal, 2);
-            fj.zero(scal + 4, 8);
-            if (!opened) fj.zero(c->cnt.p, (int64_t)(M + 1) * (NX + 1));
-            if (NP > 0 && c->f_row_count.p) fj.zero(c->f_row_count.p, (int64_t)NX + 1);
-            if (fuse) fj.zero(c->cnt_next.p, (int64_t)(M + 1) * (NX + 1));
-            if (run_fill_copy(c, fj)) return BLANCE_ERR_DEVICE;
-            c->flags_clean = true;
-            c->rowcount_clean = NP > 0 && c->f_row_count.p;
-        }
-        if (PM > 0 && !opened) {
-            if (first)
-                BLANCE_LAUNCH_NOSYNC(k_live_init, cdiv(PM, 256), 256, 0, sm, d, c->a_off.as<int32_t>(),
-                                     c->a_nodes.as<int32_t>(), c->a_kind.as<uint8_t>(), c->p_off.as<int32_t>(),
-                                     c->p_nodes.as<int32_t>(), c->p_kind.as<uint8_t>());
-            else
-                BLANCE_LAUNCH_NOSYNC(k_live_refresh, cdiv(PM, 256), 256, 0, sm, d);
-            launches++;
-        }
-        // stateNodeCounts = countStateNodes(prevMap), plan.go:94 (zeroed above)
-        if (h.n_loads > 0) {
-            BLANCE_LAUNCH_NOSYNC(k_count_loads, cdiv(h.n_loads, 256), 256, 0, sm, h.n_loads, NX, first ? 0 : 1,
-                                 c->load_state.as<int32_t>(), c->load_node.as<int32_t>(),
-                                 c->load_weight.as<int32_t>(), c->load_first.as<uint8_t>(), c->cnt.as<int32_t>());
-            launches++;
-        }
-        if (PM > 0 && !opened) {
-            BLANCE_LAUNCH_NOSYNC(k_count_prev, cdiv(PM, 256), 256, 0, sm, d, c->cnt.as<int32_t>());
-            launches++;
-        }
-        int passes_this_sweep = 0;
-        int known_passes = 0, known_state = -1, known_k = 0;        // run_flat_pass's `opening`
-        bool known_broken = false;
-        // The sweep's last pass, when it is a chain pass, leaves its verdict on the device (ChainRun::defer) and the words
-        // come back with the convergence word: one round trip for both.  A bad verdict brings the loop back for that
-        // state alone (retry says how), with everything the pass enqueued behind its gate undone by never having run.
-        int m_from = 0;
-        ChainRun retry;
-        bool retrying = false, counted = false;
-        // The sweep's first pass, when it is `settled` below, need not be read back either: its stay test leaves a word on the
-        // device (kFlagTopMoved), everything behind it waits for that word, and the word comes back with the convergence word.
-        // Set, the whole sweep runs again from its first pass with that pass read back (top_spec_off).  This holds only when
-        // every later pass of the sweep keeps its own verdict on the device as well (top_spec_fits), so that nothing of the
-        // sweep is read before its one readback.
-        bool top_spec_off = false;
-        bool tail_counts = false;                                    // (this round of the loop below ended with a counting tail)
-        const int64_t batched_sw = batched, steps_sw = steps;
-        const int n_pass_sw = n_pass;
-        std::vector<int64_t> last_stays_sw;
-        // run_chain_pass_once makes the pass of state t from the grouping by region it made last sweep, assumes its
-        // classification and defers its verdict: no readback inside
-        auto top_spec_fits = [&](int m0) {
-            if (NP == 0 || !c->top_prio_strict || m0 != h.top_state) return false;
-            for (int t = m0 + 1; t < M; t++) {
-                const int kt = c->state_constraints[t];
-                if (kt <= 0) continue;
-                if (t != m_last) return false;
-                const int q0 = c->rule_off[t], q1 = c->rule_off[t + 1];
-                if (c->engine == BLANCE_ENGINE_SEQUENTIAL || h.hierarchy_rules_nil || q1 - q0 != 1 || !c->rule_regions[q0].ok ||
-                    P < c->chain_min_parts || kt > 4)
-                    return false;
-                const int B = c->rule_regions[q0].n_regions;
-                if ((c->comm.n_ranks > 1 || c->shard_one_rank) && B >= c->comm.n_ranks) return false;
-                if (c->chain_group_state != t || !c->chain_group_static || c->h_reg_off.size() != (size_t)B + 1) return false;
-            }
-            return true;
-        };
-        for (;;) {
-        ChainRun pend;
-        SweepTail tail;
-        tail_counts = false;
-        c->top_gate = 0;
-        int64_t batched0 = batched, steps0 = steps;
-        int n_pass0 = n_pass, passes0 = passes_this_sweep;
-        for (int m = m_from; m < M; m++) {                          // plan.go:307-324
-            const int k = c->state_constraints[m];
-            if (k <= 0 || P == 0) continue;
-            if (m == m_last) { batched0 = batched; steps0 = steps; n_pass0 = n_pass; passes0 = passes_this_sweep; }
-            const int n_chunks = cdiv(P, kPartChunk);
-            const bool sort_cat = first && !(passes_this_sweep == 0 ? c->uniform_first : c->uniform_all);
-            passes_this_sweep++;
-            if (sort_cat) {
-                BLANCE_LAUNCH_NOSYNC(k_category, cdiv(P, 256), 256, 0, sm, d, m, any_removed, add_nil, c->cat.as<uint8_t>());
-                BLANCE_LAUNCH(k_part_count, n_chunks, 64, 64, sm, P, (const int32_t*)nullptr, c->cat.as<uint8_t>(),
-                              c->part_order.as<int32_t>(), n_chunks, 3, c->chunk_counts.as<int32_t>());
-                SCANTRY(3 * n_chunks, c->chunk_counts.as<int32_t>());
-                BLANCE_LAUNCH(k_part_scatter, n_chunks, 64, 64, sm, P, (const int32_t*)nullptr, c->cat.as<uint8_t>(),
-                              c->part_order.as<int32_t>(), c->part_order.as<int32_t>(), n_chunks, 3, 2,
-                              c->chunk_counts.as<int32_t>(), c->order.as<int32_t>(), (int32_t*)nullptr);
-            } else {
-                // sweeps >= 2 run with nodesToRemove = nodesToAdd = [] (non-nil, plan.go:53-55): no partition's
-                // nodes are in either, so every category is "1" (plan.go:542-561) and the pass order is the
-                // static order itself
-            }
-            // (the same holds in sweep 1 when every partition has one category, known at upload: uniform_category)
-            const int32_t* order = sort_cat ? c->order.as<int32_t>() : c->part_order.as<int32_t>();
-            c->pass_ntn_ready = false;                              // nodeToNodeCounts := fresh (plan.go:266), zeroed when first needed
-            const int OW = 1 + k;
-            int higher_mask = 0;
-            for (int t = 0; t < M; t++)
-                if (c->state_priority[t] < c->state_priority[m]) higher_mask |= 1 << t;
-            const int r0 = c->rule_off[m], r1 = c->rule_off[m + 1];
-            while (c->pass_events.size() < 2 * (size_t)(n_pass + 2)) {
-                hipEvent_t ev;
-                HIPTRY(hipEventCreate(&ev));
-                c->pass_events.push_back(ev);
-            }
-
-            // ---- region chains, when the state's single hierarchy rule allows them
-            bool done = false;
-            if (c->engine != BLANCE_ENGINE_SEQUENTIAL && !h.hierarchy_rules_nil && r1 - r0 == 1 &&
-                c->rule_regions[r0].ok && P >= c->chain_min_parts && k <= 4 && !(retrying && retry.skip)) {
-                // (same_tops: the top state's pass was one run of stays AND no other state can take a partition's top priority
-                // node away in between -- plan.go:146-154 keeps only nodes of STRICTLY higher priority states out of a pass)
-                ChainPassArgs ca{d, m, k, NP, OW, RW, higher_mask, r0, it, order,
-                                 !first && !c->tops_moved && m != h.top_state && c->top_prio_strict,
-                                 fuse && m == m_last ? &tail : nullptr};
-                bool a_done = false;
-                ChainRun run;
-                if (retrying) run = retry;
-                run.defer = !retrying && m == m_last;
-                known_broken = true;
-                const int e = run_chain_pass(c, ca, &launches, &batched, &n_pass, &done, &a_done, run);
-                if (!e && run.pending) pend = run;
-                if (e) {
-                    const bool sharded = (c->comm.n_ranks > 1 || c->shard_one_rank) && c->rule_regions[r0].n_regions >= c->comm.n_ranks;
-                    if (sharded && !a_done) comm_poison(c);       // the other ranks are (or will be) in collective A
-                    if (sharded) comm_abort(c);
-                    return e;
-                }
-            }
-            if (!done) {
-            // (what kind of pass this will be, before its records are made: the flat bulk driver's row bound rides on the gather)
-            const bool flat_state = h.hierarchy_rules_nil || r1 == r0;
-            const bool bulk = c->engine != BLANCE_ENGINE_SEQUENTIAL && flat_state && (k == 1 || (k == 2 && NP == 0)) &&
-                              P >= c->chain_min_parts;
-            const bool count_rows = bulk && NP > 0 && c->f_row_count.p;
-            const bool settled = bulk && !first && passes_this_sweep == 1 && !retrying && c->dump_sweep < 0 && c->speculate > 0;
-            const bool assume_stays = settled && top_spec_plan && !top_spec_off && k == 1 && top_spec_fits(m);
-            if (count_rows && !assume_stays) {
-                if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)NX + 1), sm));
-                c->rowcount_clean = false;
-            }
-            if (!assume_stays)
-                BLANCE_LAUNCH(k_gather, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (RW | 1) + 64, sm, d, m, h.top_state, RW, order,
-                                     c->state_stick.as<int32_t>(), c->state_has_stick.as<uint8_t>(), c->rec.as<int32_t>(),
-                                     count_rows ? c->f_row_count.as<int32_t>() : (int32_t*)nullptr, NX);
-            PassParams q;
-            memset(&q, 0, sizeof q);
-            q.N = N; q.NX = NX; q.M = M; q.L = L; q.P = P; q.s = m; q.k = k; q.top_state = h.top_state;
-            q.NP = NP; q.RW = RW; q.OW = OW;
-            q.higher_mask = higher_mask;
-            q.hier = !h.hierarchy_rules_nil;
-            q.rule_begin = r0; q.rule_end = r1;
-            q.booster_kind = h.booster_kind;
-            q.n_alive = c->n_alive;
-            q.vertex_empty_anchor = NX;
-            q.alive = c->alive.as<uint8_t>();
-            q.node_weight = c->node_weight.as<int32_t>();
-            q.node_has_weight = c->node_has_weight.as<uint8_t>();
-            q.node_leaf_pos = c->node_leaf_pos.as<int32_t>();
-            q.anchors = c->anchors.as<AnchorSet>();
-            q.cnt = c->cnt.as<int32_t>();
-            q.ntn = c->ntn.as<int32_t>();
-            q.rec = c->rec.as<int32_t>();
-            q.out = c->out.as<int32_t>();
-            q.warn_part = c->warn_part.as<int32_t>();
-            q.warn_state = c->warn_state.as<int32_t>();
-            q.warn_count = scal + 0;
-            q.err = scal + 2;
-            q.spec_count = (long long*)(scal + 12);
-            q.beg = 0; q.end = P;
-            // a flat pass (no rule for the state) of a small cluster can run on one wave64
-            bool flat_chain = c->engine != BLANCE_ENGINE_SEQUENTIAL && flat_state && c->flat_chain_ok && k <= 4 &&
-                              P >= c->chain_min_parts;
-            c->no_fast_keys = false;
-            FlatChainPrep fc;
-            fc.possible = flat_chain; fc.d = d; fc.m = m; fc.higher_mask = higher_mask; fc.order = order;
-            if (flat_chain && !bulk) {               // (the bulk driver asks for the records when a sub-range needs them)
-                const int pe = flat_chain_prepare(c, fc, &launches);
-                if (pe) return pe;
-                flat_chain = fc.ok;
-            }
-            HIPTRY(hipEventRecord(c->pass_events[2 * n_pass], sm));
-            int e;
-            bool nothing_to_apply = false;               // (run_flat_pass: a pass of stays that leaves every list as it is)
-            c->pass_kind.resize(n_pass + 1);
-            // the flat bulk driver: k = 1, and the first sweep of a fresh plan (NumPartitions == 0) with k = 2
-            if (bulk) {
-                c->pass_kind[n_pass] = 1;
-                // (what the sweep's passes so far have been: known_passes of them fresh runs known in advance, the last one
-                // of state known_state with known_k picks a step)
-                const bool opening = first && !retrying && !known_broken &&
-                                     (known_passes == 0 || (known_passes == 1 && known_k == 1 && NP == 0 && ((higher_mask >> known_state) & 1)));
-                bool whole_known = false;
-                if (assume_stays) last_stays_sw = c->last_stays;
-                e = run_flat_pass(c, q, scal, &launches, &batched, fc, opening, &whole_known, settled, assume_stays, &nothing_to_apply,
-                                  count_rows);
-                if (assume_stays) {
-                    c->top_gate = (1u << kFlagTopMoved) | (1u << kFlagForced);
-                    if (c->trace) fprintf(stderr, "[blance] sweep %d: state %d's pass taken to be one run of stays, checked with the sweep's readback\n", it, m);
-                }
-                if (whole_known) { known_passes++; known_state = m; known_k = k; }
-                else known_broken = true;
-            } else if (flat_chain) {
-                known_broken = true;
-                c->pass_kind[n_pass] = 0;
-                const size_t rows = sizeof(int32_t) * (size_t)(NX + 1) * (NX + 1);
-                e = run_flat_chain(c, q, 0, P, NP > 0 && rows <= 100 * 1024, scal, &launches);
-                if (e > 0) e = fail(BLANCE_ERR_DEVICE, "flat chain refused a checked pass");
-                if (!e) batched += P;
-            } else {
-                known_broken = true;
-                c->pass_kind[n_pass] = 0;
-                e = dispatch_pass(c, q);
-            }
-            if (e) return e;
-            HIPTRY(hipEventRecord(c->pass_events[2 * n_pass + 1], sm));
-            n_pass++;
-            if (dump_pass(c, it, m, P, q.OW, nullptr)) return BLANCE_ERR_DEVICE;
-            if (fuse && m == m_last)
-                tail = SweepTail{true, !nothing_to_apply, m, q.OW, order, nullptr, kNoGate};
-            else if (!nothing_to_apply)
-                BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, q.OW, order, c->out.as<int32_t>(), kNoGate);
-            }
-            launches += 7;
-            steps += P;
-        }
-        if (!counted) iterations++;
-        counted = true;
-        // convergence (plan.go:36-45) + write-back (plan.go:49-52)
-        if (P > 0) {
-            const Gate cg = pend.pending ? pend.gate : c->top_gate ? Gate{scal + 4, c->top_gate} : kNoGate;
-            if (tail.set && tail.scatter && (!tail.inv || tail.gate.flags != cg.flags || tail.gate.mask != cg.mask)) {
-                // (no inverse of the pass order -- a flat pass --, or the list edits wait for other words than the convergence
-                // test: on their own, as before)
-                BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.order, c->out.as<int32_t>(), tail.gate);
-                launches++;
-                tail.scatter = false;
-            }
-            if (tail.set) {
-                // the sweep's tail: the list edits, the convergence test and write-back, and -- when another sweep may follow --
-                // that sweep's counters and kinds, in one pass over the partitions
-                int32_t* next = it + 1 < h.max_iterations ? c->cnt_next.as<int32_t>() : nullptr;
-                BLANCE_LAUNCH(k_sweep_tail, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.scatter ? tail.inv : nullptr,
-                              tail.scatter ? c->out.as<int32_t>() : nullptr, scal + 1, next, cg);   // (uses a wave ballot)
-                tail_counts = next != nullptr;
-            } else {
-                BLANCE_LAUNCH(k_converge, cdiv(P, 256), 256, 0, sm, d, scal + 1, cg);   // (uses a wave ballot)
-            }
-            launches++;
-        }
-        // one readback per sweep: the convergence word with the warnings count, the chain flags (a deferred verdict) and --
-        // complete with the last sweep -- the statistics words behind them (steps k_pass_seq committed as verified stays,
-        // the queue kernel's counters)
-        HIPTRY(read_back(c, hs, scal, sizeof hs));
-        HIPTRY(stream_sync(c));
-        HIPTRY(hipGetLastError());
-        if (c->top_gate) {
-            const bool moved = hs[4 + kFlagTopMoved] || c->speculate == 2;
+        Sweep sw;
+        sw.it = it;
+        sw.first = it == 0;
+        sw.add_nil = sw.first ? h.nodes_to_add_nil : 0;
+        sw.any_removed = sw.first ? c->any_removed : 0;
+        sw.NP = sw.first ? h.n_prev : c->np_later;
+        int e = open_sweep(c, pr, sw);
+        if (e) return e;
+        pr.at.passes_this_sweep = 0;
+        sw.at_open = pr.at;
+        Verdict v;
+        do {
+            sw.pend = ChainRun();
+            sw.tail = SweepTail();
+            sw.tail_counts = false;
             c->top_gate = 0;
-            if (c->trace) fprintf(stderr, "[blance] sweep %d: the first pass %s\n", it, moved ? "was not one run of stays: the sweep runs again" : "was one run of stays");
-            if (moved) {
-                // Nothing behind the gate ran: the live lists, prevMap, the counters and the flag words are as the sweep's
-                // first pass found them.  What the host assumed or cached along the way is dropped.
-                c->spec_refuted++;
-                c->last_stays = last_stays_sw;
-                c->tops_moved = true;
-                c->chain_group_state = -1;                          // (a gated k_chain_classify wrote no region ids ...)
-                c->group_epoch++;
-                c->top_group_state = -1;                            // (... and a gated k_gather_chain no top priority keys)
-                c->pass_ntn_ready = false;
-                batched = batched_sw; steps = steps_sw; n_pass = n_pass_sw; passes_this_sweep = 0;
-                known_passes = 0; known_state = -1; known_k = 0; known_broken = false;
-                retry = ChainRun();
-                retrying = false;
-                top_spec_off = true;
-                top_spec_plan = false;                              // (a plan whose top-state pass moves steps in one later
-                                                                    // sweep tends to do so in the next: read them back)
-                m_from = 0;
-                continue;
+            sw.at_last_pass = pr.at;
+            for (int m = sw.m_from; m < M; m++) {                   // plan.go:307-324
+                if (c->state_constraints[m] <= 0 || P == 0) continue;
+                if (m == pr.m_last) sw.at_last_pass = pr.at;
+                if ((e = run_state_pass(c, pr, sw, m))) return e;
             }
-        }
-        if (!pend.pending) break;
-        {
-            const int32_t* f = hs + 4;
-            const bool refuted = (pend.spec && (f[6] || f[7])) || f[kFlagForced];
-            const bool bad = pend.pending == 1 ? (f[0] || f[kFlagStayMoved]) : (f[0] || f[1]);
-            if (c->trace)
-                fprintf(stderr, "[blance] chain pass state %d: deferred verdict (%s): %s; %d verified stays in %d batches\n", m_last,
-                        pend.pending == 1 ? "k_stay_by_top" : pend.pending == 2 ? "all-blank kernel" : "chain kernel",
-                        refuted ? "assumption refuted" : bad ? "the pass did not stand" : "stands", f[2], f[3]);
-            if (!refuted && !bad) {
-                if (pend.pending == 3) c->last_stays[m_last] = f[2];
-                break;
-            }
-            // nothing behind the gate ran: the live lists and prevMap are as the pass found them; the counters are not
-            c->spec_refuted++;
-            retry = ChainRun();
-            if (refuted) retry.allow_spec = false;
-            else if (pend.pending == 1) retry.no_stay = true;
-            else if (pend.pending == 2) retry.no_lean = true;
-            else retry.skip = true;                                 // (straight to the pass in order)
-            if (pend.pending != 1 || refuted) {
-                c->pass_ntn_ready = false;
-                HIPTRY(hipMemcpyAsync(c->cnt.p, c->cnt_save.p, sizeof(int32_t) * (size_t)(M + 1) * NX, hipMemcpyDeviceToDevice, sm));
-            }
-            batched = batched0; steps = steps0; n_pass = n_pass0; passes_this_sweep = passes0;
-            retrying = true;
-            m_from = m_last;
-        }
-        }
-        c->tail_counted = tail_counts;                              // (the tail that stood: a closed gate's wrote nothing)
-        if (hs[2]) return fail(BLANCE_ERR_UNSUPPORTED, "hierarchy fold overflowed the device's interval budget");
-        c->n_warnings = hs[0];
-        if (!hs[1]) { converged = 1; break; }
+            if (!sw.counted) pr.iterations++;
+            sw.counted = true;
+            if ((e = close_sweep(c, pr, sw))) return e;
+            // one readback per sweep: the convergence word with the warnings count, the chain flags (a deferred verdict) and --
+            // complete with the last sweep -- the statistics words behind them (steps k_pass_seq committed as verified stays,
+            // the queue kernel's counters)
+            HIPTRY(read_back(c, pr.hs, scal, sizeof pr.hs));
+            HIPTRY(stream_sync(c));
+            HIPTRY(hipGetLastError());
+            v = sweep_verdict(c, pr, sw);
+        } while (v != Verdict::kStands);
+        c->tail_counted = sw.tail_counts;                           // (the tail that stood: a closed gate's wrote nothing)
+        if (pr.hs[kScalErr]) return fail(BLANCE_ERR_UNSUPPORTED, "hierarchy fold overflowed the device's interval budget");
+        c->stats.n_warnings = pr.hs[kScalWarnCount];
+        if (!pr.hs[kScalNotMatch]) { pr.converged = 1; break; }
     }
-    HIPTRY(hipEventRecord(c->ev1, sm));
-    {
-        long long spec = 0, qs[4] = {0, 0, 0, 0};
-        memcpy(&spec, hs + 12, sizeof spec);
-        memcpy(qs, hs + 18, sizeof qs);
-        HIPTRY(hipEventSynchronize(c->ev1));
-        comm_sum_up(c);
-        c->queue_moved = qs[0]; c->queue_exact = qs[1]; c->queue_rebuilds = qs[2]; c->queue_dense = qs[3];
-        if (c->trace || getenv("BLANCE_QUEUE_STATS"))
-            fprintf(stderr, "[blance] k_pass_queue: %lld launches, %lld stops, %lld moving steps (%lld with matrix reads, %lld scoring every node), %lld window rebuilds\n",
-                    (long long)c->queue_launches, (long long)c->queue_stops, qs[0], qs[1], qs[3], qs[2]);
-        batched += spec;
-        if (batched > steps) batched = steps;     // the flat chain counts its whole pass already
-        if (c->trace) fprintf(stderr, "[blance] sequential passes: %lld verified stays\n", spec);
-    }
-    float ms = 0.f;
-    HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    double pass_ms = 0.0, flat_ms = 0.0, blank_ms = 0.0, stay_ms = 0.0;
-    int n_kernel_pass = 0, n_flat = 0, n_blank = 0, n_stay = 0;
-    for (int i = 0; i < n_pass; i++) {
-        float pm = 0.f;
-        HIPTRY(hipEventElapsedTime(&pm, c->pass_events[2 * i], c->pass_events[2 * i + 1]));
-        if (c->pass_kind[i] != 1) { pass_ms += pm; n_kernel_pass++; } else { flat_ms += pm; n_flat++; }
-        if (c->pass_kind[i] == 2) { blank_ms += pm; n_blank++; }
-        if (c->pass_kind[i] == 3) { stay_ms += pm; n_stay++; }
-        if (c->trace)
-            fprintf(stderr, "[blance] pass %d (%s): %.3f ms\n", i,
-                    c->pass_kind[i] == 1 ? "flat bulk driver" : c->pass_kind[i] == 2 ? "all-blank chain kernel" :
-                    c->pass_kind[i] == 3 ? "k_stay_by_top" : "pass kernel", pm);
-    }
-    c->pass_ms = pass_ms;
-    c->pass_launches = n_kernel_pass;
-    c->flat_ms = flat_ms;
-    c->flat_passes = n_flat;
-    c->blank_ms = blank_ms;
-    c->blank_launches = n_blank;
-    c->stay_ms = stay_ms;
-    c->stay_launches = n_stay;
-    c->iterations = iterations;
-    c->converged = converged;
-    c->device_ms = ms;
-    c->plan_syncs = c->n_syncs - syncs0;
-    c->steps_total = steps;
-    c->steps_batched = batched;
-    c->kernel_launches = launches;
+    const int fe = finish_plan(c, pr, syncs0);
+    if (fe) return fe;
     c->planned = true;
-    if (iterations == 0) c->n_warnings = 0;
     if (res) {
-        res->iterations = iterations;
-        res->converged = converged;
-        res->device_ms = ms;
-        res->total_ms = ms;
-        res->steps_total = steps;
-        res->steps_sequential = steps - batched;
-        res->steps_batched = batched;
-        res->kernel_launches = launches;
-        res->n_warnings = c->n_warnings;
-        res->pass_kernel_ms = pass_ms;
-        res->pass_kernel_launches = n_kernel_pass;
-        res->flat_pass_ms = flat_ms;
-        res->flat_passes = n_flat;
-        res->blank_pass_ms = blank_ms;
-        res->blank_pass_launches = n_blank;
-        res->stay_pass_ms = stay_ms;
-        res->stay_pass_launches = n_stay;
-        res->host_syncs = c->plan_syncs;
+        fill_result(c->stats, res);
+        res->total_ms = res->device_ms;
     }
     return BLANCE_OK;
 }
@@ -2697,8 +2870,8 @@ static int download_locked(blance_ctx* c, blance_result* res) {
     const blance_problem& h = c->h;
     const int M = h.n_states, P = h.n_parts, L = c->L;
     const size_t PM = (size_t)P * M;
-    if (c->n_warnings > res->warn_capacity) return fail(BLANCE_ERR_CAPACITY, "warn_capacity too small");
-    if (c->iterations == 0) {
+    if (c->stats.n_warnings > res->warn_capacity) return fail(BLANCE_ERR_CAPACITY, "warn_capacity too small");
+    if (c->stats.iterations == 0) {
         // MaxIterationsPerPlan <= 0: planNextMapEx returns (nil, nil) -- nothing to report (plan.go:32-58)
         for (size_t i = 0; i <= PM; i++) res->out_off[i] = 0;
         for (size_t i = 0; i < PM; i++) res->out_kind[i] = BLANCE_LIST_ABSENT;
@@ -2729,29 +2902,13 @@ static int download_locked(blance_ctx* c, blance_result* res) {
         if (total && (e = down.copy(res->out_nodes, c->dl_nodes.p, sizeof(int32_t) * (size_t)total))) return e;
         if ((e = down.copy(res->out_kind, c->prv_kind.p, PM))) return e;
     }
-    if (c->n_warnings) {
-        if ((e = down.copy(res->warn_part, c->warn_part.p, sizeof(int32_t) * (size_t)c->n_warnings))) return e;
-        if ((e = down.copy(res->warn_state, c->warn_state.p, sizeof(int32_t) * (size_t)c->n_warnings))) return e;
+    if (c->stats.n_warnings) {
+        if ((e = down.copy(res->warn_part, c->warn_part.p, sizeof(int32_t) * (size_t)c->stats.n_warnings))) return e;
+        if ((e = down.copy(res->warn_state, c->warn_state.p, sizeof(int32_t) * (size_t)c->stats.n_warnings))) return e;
     }
     if ((e = down.finish())) return e;
     HIPTRY(stream_sync(c));
-    res->n_warnings = c->n_warnings;
-    res->iterations = c->iterations;
-    res->converged = c->converged;
-    res->device_ms = c->device_ms;
-    res->steps_total = c->steps_total;
-    res->steps_sequential = c->steps_total - c->steps_batched;
-    res->steps_batched = c->steps_batched;
-    res->kernel_launches = c->kernel_launches;
-    res->pass_kernel_ms = c->pass_ms;
-    res->pass_kernel_launches = c->pass_launches;
-    res->flat_pass_ms = c->flat_ms;
-    res->flat_passes = c->flat_passes;
-    res->blank_pass_ms = c->blank_ms;
-    res->blank_pass_launches = c->blank_launches;
-    res->stay_pass_ms = c->stay_ms;
-    res->stay_pass_launches = c->stay_launches;
-    res->host_syncs = c->plan_syncs;
+    fill_result(c->stats, res);
     return BLANCE_OK;
 }
 
@@ -2861,14 +3018,13 @@ extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
     HIPTRY(hipSetDevice(c->device));
     hipStream_t sm = c->stream;
     DevBuf load, out, cons, unmet, roff;
-    struct Free { DevBuf* b[5]; ~Free() { for (DevBuf* x : b) x->release(); } } fr{{&load, &out, &cons, &unmet, &roff}};
     if (load.reserve(sizeof(int32_t) * ((size_t)M * (NX > 0 ? NX : 1) + 1)) || out.reserve(sizeof(long long) * ((size_t)M * 5 + 1)) ||
         cons.reserve(sizeof(int32_t) * ((size_t)M + 1)) || unmet.reserve(sizeof(long long) * (2 * (size_t)M + 1)) ||
         roff.reserve(sizeof(int32_t) * ((size_t)M + 2)))
         return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
     std::vector<long long> host((size_t)M * 5 + 1), hun(2 * (size_t)M + 1, 0);
     int n_next = 0;
-    if (c->iterations > 0 && M > 0) {
+    if (c->stats.iterations > 0 && M > 0) {
         HIPTRY(hipMemsetAsync(load.p, 0, sizeof(int32_t) * (size_t)M * (NX > 0 ? NX : 1), sm));
         HIPTRY(hipMemsetAsync(unmet.p, 0, sizeof(long long) * 2 * (size_t)M, sm));
         HIPTRY(hipMemcpyAsync(cons.p, c->state_constraints.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, sm));
@@ -2886,17 +3042,17 @@ extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
         HIPTRY(hipMemcpyAsync(hun.data(), unmet.p, sizeof(long long) * 2 * (size_t)M, hipMemcpyDeviceToHost, sm));
         HIPTRY(stream_sync(c));
     }
-    if (c->iterations > 0) n_next = c->n_alive;
+    if (c->stats.iterations > 0) n_next = c->n_alive;
     st->n_nodes_next = n_next;
     for (int m = 0; m < M; m++) {
-        const bool any = c->iterations > 0 && n_next > 0;
+        const bool any = c->stats.iterations > 0 && n_next > 0;
         st->load_min[m] = any ? host[(size_t)m * 5 + 0] : 0;
         st->load_max[m] = any ? host[(size_t)m * 5 + 1] : 0;
         st->load_sum[m] = any ? host[(size_t)m * 5 + 2] : 0;
         st->load_sumsq[m] = any ? host[(size_t)m * 5 + 3] : 0;
         st->nodes_used[m] = any ? (int32_t)host[(size_t)m * 5 + 4] : 0;
-        st->unmet_slots[m] = c->iterations > 0 ? hun[(size_t)m] : 0;
-        if (st->rule_violations) st->rule_violations[m] = c->iterations > 0 ? hun[(size_t)M + m] : 0;
+        st->unmet_slots[m] = c->stats.iterations > 0 ? hun[(size_t)m] : 0;
+        if (st->rule_violations) st->rule_violations[m] = c->stats.iterations > 0 ? hun[(size_t)M + m] : 0;
     }
     return BLANCE_OK;
     });
@@ -2911,29 +3067,31 @@ extern "C" int blance_download(blance_ctx* c, blance_result* res) {
     });
 }
 
+// upload, plan, download; total_ms is the device's time for all three
+static int plan_whole_locked(blance_ctx* c, const blance_problem* pb, blance_result* res) {
+    HIPTRY(hipSetDevice(c->device));
+    struct Ev { hipEvent_t a = nullptr, b = nullptr; ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
+    HIPTRY(hipEventCreate(&ev.a));
+    HIPTRY(hipEventCreate(&ev.b));
+    HIPTRY(hipEventRecord(ev.a, c->stream));
+    int st = upload_locked(c, pb);
+    if (!st) st = settle(c, plan_locked(c, res));
+    if (!st) st = settle(c, download_locked(c, res));
+    if (st) return st;
+    (void)hipEventRecord(ev.b, c->stream);
+    (void)hipEventSynchronize(ev.b);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+    res->total_ms = ms;
+    return BLANCE_OK;
+}
+
 extern "C" int blance_plan(blance_ctx* c, const blance_problem* pb, blance_result* res) {
     return guarded([&]() -> int {
     if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
     if (!res) return fail(BLANCE_ERR_BAD_ARG, "null result");
     std::lock_guard<std::mutex> g(c->mu);
-    hipEvent_t t0, t1;
-    HIPTRY(hipSetDevice(c->device));
-    HIPTRY(hipEventCreate(&t0));
-    HIPTRY(hipEventCreate(&t1));
-    HIPTRY(hipEventRecord(t0, c->stream));
-    int st = upload_locked(c, pb);
-    if (!st) st = settle(c, plan_locked(c, res));
-    if (!st) st = settle(c, download_locked(c, res));
-    if (!st) {
-        (void)hipEventRecord(t1, c->stream);
-        (void)hipEventSynchronize(t1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0, t1);
-        res->total_ms = ms;
-    }
-    (void)hipEventDestroy(t0);
-    (void)hipEventDestroy(t1);
-    return st;
+    return plan_whole_locked(c, pb, res);
     });
 }
 
@@ -3123,6 +3281,12 @@ extern "C" int64_t blance_batch_moves_capacity(const blance_problem* pb, const b
     return cap;
 }
 
+// the last error as that of problem i of a batch
+static int fail_problem(int st, int i) {
+    const std::string why = g_last_error;
+    return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
+}
+
 static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
                              blance_batch_moves* const* mvs, blance_batch_info* info) {
     const auto t_start = std::chrono::steady_clock::now();
@@ -3130,10 +3294,7 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
     for (int i = 0; i < n; i++) {
         int st = batch_check(pbs[i], res[i]);
         if (!st && mvs && mvs[i]) st = batch_moves_check(pbs[i], mvs[i]);
-        if (st) {
-            const std::string why = g_last_error;
-            return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
-        }
+        if (st) return fail_problem(st, i);
     }
     HIPTRY(hipSetDevice(c->device));
     c->uploaded = false;                                 // the context holds no problem after a batch
@@ -3289,33 +3450,15 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
     }
     const int n_fallback = (int)fallback.size();
     for (int i : fallback) {                             // the single-problem path: blance_plan
-        hipEvent_t t0, t1;
-        HIPTRY(hipEventCreate(&t0));
-        HIPTRY(hipEventCreate(&t1));
-        struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{t0, t1};
-        HIPTRY(hipEventRecord(t0, c->stream));
-        int st = upload_locked(c, pbs[i]);
-        if (!st) st = settle(c, plan_locked(c, res[i]));
-        if (!st) st = settle(c, download_locked(c, res[i]));
+        int st = plan_whole_locked(c, pbs[i], res[i]);
         c->uploaded = c->planned = false;
-        if (st) {
-            const std::string why = g_last_error;
-            return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
-        }
-        (void)hipEventRecord(t1, c->stream);
-        (void)hipEventSynchronize(t1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0, t1);
-        res[i]->total_ms = ms;
+        if (st) return fail_problem(st, i);
         launches += res[i]->kernel_launches;
         steps += res[i]->steps_total;
         device_ms += res[i]->device_ms;
         if (mvs && mvs[i]) {
             st = batch_moves_single(c, pbs[i], res[i], mvs[i], &launches);
-            if (st) {
-                const std::string why = g_last_error;
-                return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
-            }
+            if (st) return fail_problem(st, i);
             device_ms += mvs[i]->out.device_ms;
         }
     }
@@ -3334,13 +3477,7 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
 
 extern "C" int blance_plan_batch(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
                                  blance_batch_info* info) {
-    return guarded([&]() -> int {
-    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
-    if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, plan_batch_locked(c, n, pbs, res, nullptr, info));
-    });
+    return blance_plan_batch_moves(c, n, pbs, res, nullptr, info);
 }
 
 extern "C" int blance_plan_batch_moves(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,

@@ -82,6 +82,49 @@ struct Gate {
 };
 constexpr Gate kNoGate = {nullptr, 0u};
 
+// The int32 words of the context's `scalars` buffer (DESIGN.md 4.5 has the table).  The host hands the kernels pointers
+// into it; a Gate's flags is always scalars + kScalFlags.
+enum ScalarWord : int {
+    kScalWarnCount = 0,       // warnings so far
+    kScalNotMatch = 1,        // the sweep's convergence word: some partition's lists changed
+    kScalErr = 2,             // device error word (interval overflow ...)
+    kScalFlags = 4,           // the eight chain flags (ChainFlag), zeroed per sweep and per chain pass
+    kScalSpecCount = 12,      // int64: steps the sequential passes committed as verified stays
+    kScalSortVarying = 14,    // uint64: the key bits that vary (k_sort_varbits)
+    kScalQueueStop = 16,      // k_pass_queue's two stop words
+    kScalQueueStats = 18,     // k_pass_queue's four int64 statistics
+    kScalReadback = 32,       // the host copies words [0, kScalReadback) back once per sweep
+    kScalFlatScan = 36,       // the flat bulk driver's own: k_flat_scan_min's two results ...
+    kScalFlatBad = 38,        // ... and k_fresh_excl_apply's first bad step
+    kScalWords = 64,
+};
+// Words of a Gate's flags, i.e. relative to kScalFlags.  [0, kChainFlags): what the chain passes' kernels report --
+// k_chain_classify, k_gather_chain, k_pass_chain*, k_period_verdict.  Behind them, outside what a chain pass resets:
+// k_stay_by_top's "not all stays"; BLANCE_SPECULATE=fail; k_flat_stay_live's "the sweep's first pass is NOT one run of stays".
+enum ChainFlag : int {
+    kFlagNotLocal = 0,        // a step is not region-local / does not fit the compact record
+    kFlagEscaped = 1,         // a chain had to escape (flat mode: it stopped)
+    kFlagStaySteps = 2,       // steps committed as verified stays
+    kFlagStayBatches = 3,     // ... in this many batches
+    kFlagStopAt = 4,          // flat mode: first step not done
+    kFlagStopRange = 5,       // flat mode: stopped by the key range
+    kFlagOrphans = 6,         // nodes of the state that lie in no region
+    kFlagEvents = 7,          // nodes outside their partition's region
+    kChainFlags = 8,
+    kFlagStayMoved = 22, kFlagForced = 23, kFlagTopMoved = 24,
+};
+constexpr int kGateWords = 32;                   // a Gate's mask has one bit per word
+static_assert(kScalErr < kScalFlags && kScalFlags + kChainFlags <= kScalSpecCount && kScalSpecCount + 2 <= kScalSortVarying &&
+              kScalSortVarying + 2 <= kScalQueueStop && kScalQueueStop + 2 <= kScalQueueStats &&
+              kScalQueueStats + 8 <= kScalFlags + kFlagStayMoved && kFlagStayMoved < kFlagForced && kFlagForced < kFlagTopMoved,
+              "the scalar words overlap");
+static_assert(kScalSpecCount % 2 == 0 && kScalSortVarying % 2 == 0 && kScalQueueStats % 2 == 0, "a 64-bit scalar word is not 8-byte aligned");
+static_assert(kFlagTopMoved < kGateWords && kChainFlags <= kGateWords, "a Gate's mask cannot name the word");
+static_assert(kScalFlags + kFlagTopMoved < kScalReadback && kScalQueueStats + 8 <= kScalReadback,
+              "the per-sweep readback misses a word the host decides on");
+static_assert(kScalFlatScan >= kScalFlags + kGateWords && kScalFlatScan >= kScalReadback && kScalFlatScan + 2 <= kScalFlatBad &&
+              kScalFlatBad < kScalWords, "the flat driver's words must lie outside what a Gate can address");
+
 struct ChainParams {
     int32_t N, NX, M, L;
     int32_t s, k, NP, OW;
@@ -93,7 +136,7 @@ struct ChainParams {
                                    // leaves that all carry nodes (racks of equal size), else 0
     int32_t flat;                  // the whole cluster is ONE region and every node its own exclude class:
                                    // a state pass without hierarchy rules (leaf index = node id); a chain that
-                                   // cannot go on stops, keeps what it did and reports the step in flags[4]
+                                   // cannot go on stops, keeps what it did and reports the step in flags[kFlagStopAt]
     const int32_t* reg_lo;         // [n_regions] leaf interval of the region
     const int32_t* reg_hi;
     const int32_t* reg_off;        // [n_regions + 1] step range of the region in chain order
@@ -119,9 +162,7 @@ struct ChainParams {
     const int32_t* crec;           // [P * kCW] compact step records in chain order
     int32_t* out;                  // [P * OW]
     int32_t waves;                 // waves of a region's workgroup: 0 = the launcher decides (8 when the LDS is there), 4, 8
-    int32_t* flags;                // [0] a step is not region-local, [1] a chain had to escape,
-                                   // [2] steps committed as verified stays, [3] stay batches,
-                                   // [4] flat mode: first step not done, [5] stopped by the key range
+    int32_t* flags;                // the chain flags (ChainFlag, below Gate)
     uint32_t gate;                 // k_pass_chain: words of flags[] (a Gate's mask) that, any of them set, make the launch return
 };
 

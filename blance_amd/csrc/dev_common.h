@@ -1,5 +1,5 @@
 // Device helpers: nodeSorter.Score / Less, workgroup argmin, hierarchy masks as leaf-interval algebra.
-// Part of blance_hip.hip (one translation unit); see DESIGN.md section 4.
+// Included by every translation unit of libblance_hip.so; see DESIGN.md section 4.
 #pragma once
 
 namespace blance {

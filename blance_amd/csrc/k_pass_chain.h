@@ -1,5 +1,5 @@
 // k_pass_chain: region chains (one wave64 per hierarchy region), verified-stay speculation, integer-key mode.
-// Part of blance_hip.hip (one translation unit); see DESIGN.md section 4.
+// Compiled in tu_chain.hip (in blance_hip.hip by the emulator build, which is one translation unit); see DESIGN.md section 4.
 #pragma once
 
 namespace blance {
@@ -13,7 +13,7 @@ namespace blance {
 // lanes own the region's leaves, the region's slice of nodeToNodeCounts sits
 // in LDS, and the argmin is a DPP reduction -- no barrier, no global traffic
 // on the critical path.  A chain that would have to look outside its region
-// (fallback to candidateNodes[0], unmet constraints) raises flags[1] and the
+// (fallback to candidateNodes[0], unmet constraints) raises flags[kFlagEscaped] and the
 // host redoes the whole pass with k_pass_seq.
 // ============================================================================
 template <int CTRL>
@@ -157,7 +157,7 @@ constexpr int chain_waves_max() { return NPTC >= 8 ? 4 : kChainWaves; }
 template <int NPTC, int KM, bool FAST>
 __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(ChainParams q) {
     BLANCE_DYN_LDS(lds);
-    if (q.flags[0] || gate_closed(Gate{q.flags, q.gate})) return;
+    if (q.flags[kFlagNotLocal] || gate_closed(Gate{q.flags, q.gate})) return;
     const int lane = threadIdx.x & 63;
     const int wave = uni((int)(threadIdx.x >> 6)), NWv = uni((int)(blockDim.x >> 6));
     const int rg = q.region_base + blockIdx.x;
@@ -938,9 +938,9 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
     if (!escaped) while (ev_cur < ev_end) apply_event();      // nodes that leave after this region's last step
     if (__ballot(range_bad)) { escaped = true; stop_range = true; }
     PH_DUMP(cend - cbeg);
-    if (lane == 0 && spec_batches) { atomicAdd(&q.flags[2], spec_steps); atomicAdd(&q.flags[3], spec_batches); }
+    if (lane == 0 && spec_batches) { atomicAdd(&q.flags[kFlagStaySteps], spec_steps); atomicAdd(&q.flags[kFlagStayBatches], spec_batches); }
     if (escaped) {
-        if (lane == 0) { q.flags[1] = 1; q.flags[4] = stop_at; q.flags[5] = stop_range ? 1 : 0; }
+        if (lane == 0) { q.flags[kFlagEscaped] = 1; q.flags[kFlagStopAt] = stop_at; q.flags[kFlagStopRange] = stop_range ? 1 : 0; }
         if (!q.flat) return;
         // the rest of the pass continues from global memory: hand over the LDS rows
         if (!FAST && NP > 0 && q.ntn_in_lds) {
@@ -963,7 +963,7 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
 // in which EVERY step is blank (the replica pass of a fresh plan's first sweep:
 // NumPartitions == 0, no node weights, partitions that hold no node of this or a
 // lower priority state).  Few live values, no spills: one dependent step costs k
-// wave minima and little else.  Anything outside its envelope sets flags[1] and
+// wave minima and little else.  Anything outside its envelope sets flags[kFlagEscaped] and
 // changes nothing; the host then runs k_pass_chain from the same state.
 // ---------------------------------------------------------------------------
 template <int NPTC, int KM>
@@ -1106,7 +1106,7 @@ __global__ __launch_bounds__(64) void k_pass_chain_blank(ChainParams q) {
       __syncthreads();
     }
     if (failed) {
-        if (lane == 0) q.flags[1] = 1;
+        if (lane == 0) q.flags[kFlagEscaped] = 1;
         return;
     }
     // every region must succeed before any of them may publish its counters: publish to
@@ -1127,7 +1127,7 @@ __global__ __launch_bounds__(64) void k_pass_chain_blank(ChainParams q) {
 // the pick's exclude masks (v_readlane_b32).  The exclude masks of 64 steps are prepared lane
 // parallel (lane r: step r), the records of the next 64 steps are fetched while this batch is walked.
 // Envelope: <= 64 W leaves, every live leaf has an exclude class, counts within kPlanes levels of
-// each other at any time, one partition weight for the whole chain.  Outside it: flags[1], nothing
+// each other at any time, one partition weight for the whole chain.  Outside it: flags[kFlagEscaped], nothing
 // published (as k_pass_chain_blank).
 // ---------------------------------------------------------------------------
 constexpr int kPlanes = 4;
@@ -1411,7 +1411,7 @@ __global__ __launch_bounds__(64) void k_pass_chain_planes(ChainParams q) {
         }
     }
     if (__ballot(bad)) {
-        if (lane == 0) q.flags[1] = 1;
+        if (lane == 0) q.flags[kFlagEscaped] = 1;
         return;
     }
     // planes (wave-uniform: SGPRs), and for every leaf the mask of its exclude class
@@ -1445,7 +1445,7 @@ __global__ __launch_bounds__(64) void k_pass_chain_planes(ChainParams q) {
             }
         }
         if (__ballot(!okc)) {
-            if (lane == 0) q.flags[1] = 1;
+            if (lane == 0) q.flags[kFlagEscaped] = 1;
             return;
         }
     }
@@ -1557,7 +1557,7 @@ __global__ __launch_bounds__(64) void k_pass_chain_planes(ChainParams q) {
 #endif
     PH_DUMP(cend - cbeg);
     if (failed) {
-        if (lane == 0) q.flags[1] = 1;
+        if (lane == 0) q.flags[kFlagEscaped] = 1;
         return;
     }
     // every region must succeed before any of them may publish its counters: publish to

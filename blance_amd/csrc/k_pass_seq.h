@@ -1,5 +1,5 @@
 // k_pass_seq: the exact sequential state pass (always applicable).
-// Part of blance_hip.hip (one translation unit); see DESIGN.md section 4.
+// Compiled in tu_seq.hip (in blance_hip.hip by the emulator build, which is one translation unit); see DESIGN.md section 4.
 #pragma once
 
 namespace blance {

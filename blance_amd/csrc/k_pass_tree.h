@@ -1,6 +1,6 @@
 // k_pass_tree: the exact sequential state pass of a state WITHOUT hierarchy rules on one wave64,
 // with a bound-ordered candidate structure instead of a scan of every node per step.
-// Part of blance_hip.hip (one translation unit); see DESIGN.md section 4.
+// Compiled in tu_tree.hip (in blance_hip.hip by the emulator build, which is one translation unit); see DESIGN.md section 4.
 #pragma once
 
 namespace blance {

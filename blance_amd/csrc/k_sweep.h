@@ -254,10 +254,10 @@ __global__ __launch_bounds__(64) void k_part_scatter(int n, const int32_t* key32
 }
 
 // Region of every step of the pass (the region of its top priority node), or
-// flags[0] if a step has none.  Nodes the partition holds in this state outside
+// flags[kFlagNotLocal] if a step has none.  Nodes the partition holds in this state outside
 // that region leave the state whatever the step decides (plan.go:290-293): they
-// become events for the chains that own them (n_ev counts them per step; flags[7]
-// says there are any; flags[6] is raised if some lie in no region at all --
+// become events for the chains that own them (n_ev counts them per step; flags[kFlagEvents]
+// says there are any; flags[kFlagOrphans] is raised if some lie in no region at all --
 // k_chain_orphans un-counts those).
 __global__ void k_chain_classify(DevProblem d, int m, int top_state, const int32_t* order,
                                  const int32_t* node_region, int32_t* regid, int32_t* n_ev, int32_t* flags, Gate gate) {
@@ -276,11 +276,11 @@ __global__ void k_chain_classify(DevProblem d, int m, int top_state, const int32
             for (int i = 0; i < d.live_len[idx]; i++) {
                 int r2 = node_region[d.live[(size_t)idx * d.L + i]];
                 if (r2 == rg) continue;
-                if (r2 >= 0) ne++; else flags[6] = 1;
-                flags[7] = 1;                      // the pass has nodes outside their partition's region
+                if (r2 >= 0) ne++; else flags[kFlagOrphans] = 1;
+                flags[kFlagEvents] = 1;                      // the pass has nodes outside their partition's region
             }
     }
-    if (rg < 0) { flags[0] = 1; rg = 0; }
+    if (rg < 0) { flags[kFlagNotLocal] = 1; rg = 0; }
     regid[oi] = rg;
     n_ev[oi] = ne;
 }
@@ -320,9 +320,9 @@ __global__ void k_chain_orphans(DevProblem d, int m, int top_state, const int32_
 }
 
 // Compact chain records (layout: blance_kernels.h): the step's nodes as leaf
-// indices local to its region.  Steps the chain kernel cannot represent raise flags[0].
+// indices local to its region.  Steps the chain kernel cannot represent raise flags[kFlagNotLocal].
 // one step's compact record (24 words at r); returns the global leaf index of the step's top priority node (0 if it has
-// none inside a region: flags[0] is raised for such a step)
+// none inside a region: flags[kFlagNotLocal] is raised for such a step)
 __device__ __forceinline__ int gather_chain_record(const DevProblem& d, int m, int top_state, int higher_mask, int p, int oi,
                                                     const int32_t* state_stickiness, const uint8_t* state_has_stickiness,
                                                     const int32_t* node_leaf_pos, const int32_t* node_region,
@@ -339,7 +339,7 @@ __device__ __forceinline__ int gather_chain_record(const DevProblem& d, int m, i
     int idxT = p * d.M + top_state;
     int top = (d.live_kind[idxT] != kListAbsent && d.live_len[idxT] > 0) ? d.live[(size_t)idxT * d.L] : -1;
     int rg = flat ? 0 : (top >= 0 ? node_region[top] : -1);
-    if (rg < 0) { flags[0] = 1; r[4] = 0; r[5] = 0; r[6] = -1; return 0; }
+    if (rg < 0) { flags[kFlagNotLocal] = 1; r[4] = 0; r[5] = 0; r[6] = -1; return 0; }
     const int lo = reg_lo[rg];
     if (flat) {
         r[4] = top >= 0 ? top : d.NX;              // the "" row when there is no top priority node
@@ -387,7 +387,7 @@ __device__ __forceinline__ int gather_chain_record(const DevProblem& d, int m, i
         }
     }
     r[5] = n_own | (n_h << 8) | (n_low << 16) | (present << 24) | (remote << 25);
-    if (bad) flags[0] = 1;
+    if (bad) flags[kFlagNotLocal] = 1;
     return flat ? 0 : lo + r[4];
 }
 
