@@ -284,3 +284,12 @@ class PlanStats(C.Structure):
                 ("load_sum", C.POINTER(C.c_int64)), ("load_sumsq", C.POINTER(C.c_int64)),
                 ("nodes_used", C.POINTER(C.c_int32)), ("unmet_slots", C.POINTER(C.c_int64)),
                 ("rule_violations", C.POINTER(C.c_int64))]
+
+
+# blance_plan_stats as a numpy record (pointers as addresses): Planner.plan_batch_stats fills many at once
+PLAN_STATS_ARRAYS = ("load_min", "load_max", "load_sum", "load_sumsq", "nodes_used", "unmet_slots", "rule_violations")
+PLAN_STATS_DTYPE = np.dtype({
+    "names": ["n_states", "n_nodes_next"] + list(PLAN_STATS_ARRAYS),
+    "formats": [np.int32, np.int32] + [np.uint64] * len(PLAN_STATS_ARRAYS),
+    "offsets": [getattr(PlanStats, f).offset for f in ("n_states", "n_nodes_next") + PLAN_STATS_ARRAYS],
+    "itemsize": C.sizeof(PlanStats)})

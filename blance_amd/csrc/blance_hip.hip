@@ -3005,10 +3005,9 @@ extern "C" int blance_plan_resident(blance_ctx* c, blance_result* res) {
     });
 }
 
-extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
-    return guarded([&]() -> int {
-    if (!c || !st) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
+// the statistics of the map the context holds (blance_plan_stats_get; a batch's single-path problems); *launches grows by
+// the kernels launched
+static int plan_stats_locked(blance_ctx* c, blance_plan_stats* st, int64_t* launches = nullptr) {
     if (!c->planned) return fail(BLANCE_ERR_BAD_ARG, "nothing planned yet");
     const blance_problem& h = c->h;
     const int N = h.n_nodes, NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts;
@@ -3029,15 +3028,20 @@ extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
         HIPTRY(hipMemsetAsync(unmet.p, 0, sizeof(long long) * 2 * (size_t)M, sm));
         HIPTRY(hipMemcpyAsync(cons.p, c->state_constraints.data(), sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, sm));
         DevProblem d = result_problem(c);
-        if ((int64_t)P * M > 0)
+        int n_launched = 1;
+        if ((int64_t)P * M > 0) {
             BLANCE_LAUNCH_NOSYNC(k_stats_load, cdiv((int64_t)P * M, 256), 256, 0, sm, d, load.as<int32_t>(), cons.as<int32_t>(),
                                  unmet.as<unsigned long long>());
+            n_launched++;
+        }
         if (!h.hierarchy_rules_nil && h.n_rules > 0 && (int64_t)P * M > 0) {      // rule violations (words M .. 2M - 1 of `unmet`)
             HIPTRY(hipMemcpyAsync(roff.p, c->rule_off.data(), sizeof(int32_t) * ((size_t)M + 1), hipMemcpyHostToDevice, sm));
             BLANCE_LAUNCH_NOSYNC(k_stats_rules, cdiv((int64_t)P * M, 256), 256, 0, sm, d, h.top_state, roff.as<int32_t>(),
                                  c->anchors.as<AnchorSet>(), c->node_leaf_pos.as<int32_t>(), unmet.as<unsigned long long>() + M);
+            n_launched++;
         }
         BLANCE_LAUNCH(k_stats_reduce, M, 256, sizeof(long long) * 5 * 256 + 64, sm, N, NX, c->alive.as<uint8_t>(), load.as<int32_t>(), out.as<long long>());
+        if (launches) *launches += n_launched;
         HIPTRY(hipMemcpyAsync(host.data(), out.p, sizeof(long long) * (size_t)M * 5, hipMemcpyDeviceToHost, sm));
         HIPTRY(hipMemcpyAsync(hun.data(), unmet.p, sizeof(long long) * 2 * (size_t)M, hipMemcpyDeviceToHost, sm));
         HIPTRY(stream_sync(c));
@@ -3055,6 +3059,13 @@ extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
         if (st->rule_violations) st->rule_violations[m] = c->stats.iterations > 0 ? hun[(size_t)M + m] : 0;
     }
     return BLANCE_OK;
+}
+
+extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
+    return guarded([&]() -> int {
+    if (!c || !st) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    return plan_stats_locked(c, st);
     });
 }
 
@@ -3106,6 +3117,7 @@ struct BatchItem {
     BatchDesc d;
     int64_t in_words, sc_words, out_words;
     int mi = -1;        // its BatchMovesDesc, when the caller asks for its moves
+    int si = -1;        // its BatchStatsDesc, when the caller asks for its statistics
 };
 
 int batch_list_len(const blance_problem* pb) {
@@ -3227,6 +3239,14 @@ int batch_moves_check(const blance_problem* pb, const blance_batch_moves* mv) {
     return BLANCE_OK;
 }
 
+// the statistics request of one problem: the six mandatory arrays, their capacity (blance_plan_stats_get's own check)
+int batch_stats_check(const blance_problem* pb, const blance_plan_stats* st) {
+    if (st->n_states < pb->n_states || !st->load_min || !st->load_max || !st->load_sum || !st->load_sumsq || !st->nodes_used ||
+        !st->unmet_slots)
+        return fail(BLANCE_ERR_BAD_ARG, "stats arrays missing or shorter than n_states");
+    return BLANCE_OK;
+}
+
 // every check blance_plan would make before it writes a result, and the result buffers' capacities
 int batch_check(const blance_problem* pb, const blance_result* r) {
     int st = blance_validate(pb);
@@ -3288,12 +3308,13 @@ static int fail_problem(int st, int i) {
 }
 
 static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
-                             blance_batch_moves* const* mvs, blance_batch_info* info) {
+                             blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_info* info) {
     const auto t_start = std::chrono::steady_clock::now();
     if (c->comm.n_ranks > 1 || c->rccl_comm) return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_batch on a context with a communicator");
     for (int i = 0; i < n; i++) {
         int st = batch_check(pbs[i], res[i]);
         if (!st && mvs && mvs[i]) st = batch_moves_check(pbs[i], mvs[i]);
+        if (!st && sts && sts[i]) st = batch_stats_check(pbs[i], sts[i]);
         if (st) return fail_problem(st, i);
     }
     HIPTRY(hipSetDevice(c->device));
@@ -3336,6 +3357,21 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         mds.push_back(md);
     }
     const int nm = (int)mds.size();
+    // the statistics regions of the batched problems that ask for them, behind the moves: 1 + 7 M int64 values each
+    std::vector<BatchStatsDesc> sds;
+    size_t lds_stats = 0;
+    for (int j = 0; j < nb && sts; j++) {
+        BatchItem& it = items[j];
+        if (!sts[it.idx]) continue;
+        BatchStatsDesc sd;
+        sd.desc = j;
+        sd.o_stats = (int32_t)it.out_words;              // (a multiple of 4 words, as every region: 8-byte aligned)
+        it.out_words += (2 * (1 + (int64_t)kBatchStatsArrays * it.d.M) + 3) & ~3ll;
+        lds_stats = std::max(lds_stats, batch_stats_lds(it.d.M, it.d.NX));
+        it.si = (int)sds.size();
+        sds.push_back(sd);
+    }
+    const int ns = (int)sds.size();
     int64_t launches = 0, steps = 0;
     double device_ms = 0.0;
     if (nb > 0) {
@@ -3350,7 +3386,8 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             else if (lds > lds256) lds256 = lds;
         }
         const size_t desc_bytes = ((sizeof(BatchDesc) * (size_t)nb) + 255) & ~(size_t)255;
-        const size_t head_bytes = desc_bytes + (((sizeof(BatchMovesDesc) * (size_t)nm) + 255) & ~(size_t)255);
+        const size_t mdesc_bytes = ((sizeof(BatchMovesDesc) * (size_t)nm) + 255) & ~(size_t)255;
+        const size_t head_bytes = desc_bytes + mdesc_bytes + (((sizeof(BatchStatsDesc) * (size_t)ns) + 255) & ~(size_t)255);
         const size_t in_bytes = head_bytes + sizeof(int32_t) * (size_t)in_words, out_bytes = sizeof(int32_t) * (size_t)out_words;
         struct Pinned { void* p = nullptr; ~Pinned() { pin_free(p); } } host;
         host.p = pin_alloc(in_bytes + out_bytes);
@@ -3374,6 +3411,7 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             }
         }
         if (nm > 0) memcpy(h_in + desc_bytes, mds.data(), sizeof(BatchMovesDesc) * (size_t)nm);
+        if (ns > 0) memcpy(h_in + desc_bytes + mdesc_bytes, sds.data(), sizeof(BatchStatsDesc) * (size_t)ns);
         if (c->batch_in.reserve(in_bytes) || c->batch_sc.reserve(sizeof(int32_t) * (size_t)sc_words + 256) ||
             c->batch_out.reserve(out_bytes))
             return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
@@ -3394,6 +3432,14 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             qm.mdesc = (const BatchMovesDesc*)(c->batch_in.as<char>() + desc_bytes);
             qm.in = q.in; qm.sc = q.sc; qm.out = q.out;
             launch_batch_moves(c->stream, qm, nm);
+            launches++;
+        }
+        if (ns > 0) {
+            BatchStatsParams qs;
+            qs.desc = q.desc;
+            qs.sdesc = (const BatchStatsDesc*)(c->batch_in.as<char>() + desc_bytes + mdesc_bytes);
+            qs.in = q.in; qs.out = q.out;
+            launch_batch_stats(c->stream, qs, ns, lds_stats);
             launches++;
         }
         HIPTRY(hipGetLastError());
@@ -3446,11 +3492,28 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
                     mo.op_kind[j] = (w[j] >> 24) & 0xff;
                 }
             }
+            if (it.si >= 0) {                            // statistics: n_nodes_next, then seven arrays [M], all int64
+                blance_plan_stats* ps = sts[it.idx];
+                const int M = d.M;
+                std::vector<int64_t> v(1 + (size_t)kBatchStatsArrays * M);
+                memcpy(v.data(), o + sds[it.si].o_stats, sizeof(int64_t) * v.size());
+                ps->n_nodes_next = (int32_t)v[0];
+                for (int m = 0; m < M; m++) {
+                    ps->load_min[m] = v[1 + m];
+                    ps->load_max[m] = v[1 + M + m];
+                    ps->load_sum[m] = v[1 + 2 * M + m];
+                    ps->load_sumsq[m] = v[1 + 3 * M + m];
+                    ps->nodes_used[m] = (int32_t)v[1 + 4 * M + m];
+                    ps->unmet_slots[m] = v[1 + 5 * M + m];
+                    if (ps->rule_violations) ps->rule_violations[m] = v[1 + 6 * M + m];
+                }
+            }
         }
     }
     const int n_fallback = (int)fallback.size();
     for (int i : fallback) {                             // the single-problem path: blance_plan
         int st = plan_whole_locked(c, pbs[i], res[i]);
+        if (!st && sts && sts[i]) st = plan_stats_locked(c, sts[i], &launches);     // while the context still holds the plan
         c->uploaded = c->planned = false;
         if (st) return fail_problem(st, i);
         launches += res[i]->kernel_launches;
@@ -3477,16 +3540,21 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
 
 extern "C" int blance_plan_batch(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
                                  blance_batch_info* info) {
-    return blance_plan_batch_moves(c, n, pbs, res, nullptr, info);
+    return blance_plan_batch_stats(c, n, pbs, res, nullptr, nullptr, info);
 }
 
 extern "C" int blance_plan_batch_moves(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
                                        blance_batch_moves* const* mvs, blance_batch_info* info) {
+    return blance_plan_batch_stats(c, n, pbs, res, mvs, nullptr, info);
+}
+
+extern "C" int blance_plan_batch_stats(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                                       blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_info* info) {
     return guarded([&]() -> int {
     if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
     if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
     std::lock_guard<std::mutex> g(c->mu);
     rb_discard(c);
-    return settle(c, plan_batch_locked(c, n, pbs, res, mvs, info));
+    return settle(c, plan_batch_locked(c, n, pbs, res, mvs, sts, info));
     });
 }

@@ -270,4 +270,20 @@ struct BatchMovesParams {
     int32_t* out;
 };
 
+// The plan statistics of one batched problem (DESIGN.md §4.10 "k_batch_stats"): 1 + 7 M int64 values in its output slice,
+// n_nodes_next, then load_min / load_max / load_sum / load_sumsq / nodes_used / unmet_slots / rule_violations [M] each.
+constexpr int kBatchStatsThreads = 256;
+constexpr int kBatchStatsArrays = 7;
+struct BatchStatsDesc {
+    int32_t desc;                         // index of the problem's BatchDesc
+    int32_t o_stats;                      // output slice: first word of the values (a multiple of 4: 8-byte aligned)
+};
+
+struct BatchStatsParams {
+    const BatchDesc* desc;
+    const BatchStatsDesc* sdesc;          // one workgroup each
+    const int32_t* in;
+    int32_t* out;
+};
+
 }  // namespace blance

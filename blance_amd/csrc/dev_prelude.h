@@ -52,4 +52,7 @@ void launch_plan_batch(hipStream_t stream, const BatchParams& q, int threads, in
 size_t plan_batch_lds(int threads, int M, int NX);   // dynamic LDS of one such workgroup
 // k_batch_moves (tu_batch.hip): the partition moves of n batched problems, one workgroup each
 void launch_batch_moves(hipStream_t stream, const BatchMovesParams& q, int n);
+// k_batch_stats (tu_batch.hip): the plan statistics of n batched problems, one workgroup each
+void launch_batch_stats(hipStream_t stream, const BatchStatsParams& q, int n, size_t lds);
+size_t batch_stats_lds(int M, int NX);               // dynamic LDS of one such workgroup
 }  // namespace blance

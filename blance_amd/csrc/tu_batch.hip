@@ -1,7 +1,9 @@
-// Translation unit of k_plan_batch and k_batch_moves: many small problems in one launch, and their launch wrappers.
+// Translation unit of k_plan_batch, k_batch_moves and k_batch_stats: many small problems in one launch, and their launch
+// wrappers.
 #include "dev_prelude.h"
 #include "k_plan_batch.h"
 #include "k_batch_moves.h"
+#include "k_batch_stats.h"
 
 namespace blance {
 
@@ -19,6 +21,15 @@ void launch_plan_batch(hipStream_t stream, const BatchParams& q, int threads, in
 void launch_batch_moves(hipStream_t stream, const BatchMovesParams& q, int n) {
     if (n <= 0) return;
     BLANCE_LAUNCH(k_batch_moves, n, kBatchMovesThreads, sizeof(int) * kBatchMovesThreads, stream, q);
+}
+
+size_t batch_stats_lds(int M, int NX) {
+    return sizeof(long long) * (size_t)M * (2 + 5 * (kBatchStatsThreads / 64)) + sizeof(int) * (size_t)M * NX;
+}
+
+void launch_batch_stats(hipStream_t stream, const BatchStatsParams& q, int n, size_t lds) {
+    if (n <= 0) return;
+    BLANCE_LAUNCH(k_batch_stats, n, kBatchStatsThreads, lds, stream, q);
 }
 
 }  // namespace blance

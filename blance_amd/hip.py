@@ -90,6 +90,11 @@ def load_library(path=None):
                                                 C.POINTER(abi.BatchInfo)]
         lib.blance_batch_moves_capacity.restype = C.c_int64
         lib.blance_batch_moves_capacity.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.BatchMoves)]
+    if hasattr(lib, "blance_plan_batch_stats"):
+        lib.blance_plan_batch_stats.restype = C.c_int
+        lib.blance_plan_batch_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
+                                                C.POINTER(C.POINTER(abi.Result)), C.POINTER(C.POINTER(abi.BatchMoves)),
+                                                C.POINTER(C.POINTER(abi.PlanStats)), C.POINTER(abi.BatchInfo)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
@@ -283,23 +288,15 @@ class Planner:
         self._check(self.lib.blance_plan_batch(self._h, n, pbs, rss, C.byref(info)))
         return results, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
-    def plan_batch_moves(self, fps, favor_min_nodes, beg_other=None):
-        """blance_plan_batch_moves(): plan_batch, and for each problem CalcPartitionMoves from its prevMap as passed to its
-        plan for every partition in partition id order.  favor_min_nodes: one bool, or one per problem where None asks for
-        no moves; beg_other: None, or per problem None or (offsets [P + 1], node ids) of prevMap's keys outside the model.
-        Returns ([FlatResult], [(op_off, op_node, op_state, op_kind) or None], info dict)."""
+    def _moves_requests(self, fps, results, favor_min_nodes, beg_other):
+        """The moves requests of a batch as one numpy block viewed as blance_batch_moves[], the moves of all problems in one
+        block: per problem op_off [P + 1], then op_node, op_state, op_kind [capacity] (no per-array ctypes conversions).
+        Returns (the pointer array of the call, what _moves_unpack needs -- it also keeps the buffers alive)."""
         import numpy as np
-        if not hasattr(self.lib, "blance_plan_batch_moves"):
-            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_moves (build the current sources)")
-        fps = list(fps)
         n = len(fps)
         favor = list(favor_min_nodes) if isinstance(favor_min_nodes, (list, tuple)) else [favor_min_nodes] * n
         other = list(beg_other) if beg_other is not None else [None] * n
-        results = [abi.FlatResult(fp) for fp in fps]
-        structs = [fp.as_struct() for fp in fps]
         ask = [i for i in range(n) if favor[i] is not None]
-        # the requests as one numpy block viewed as blance_batch_moves[], the moves of all problems in one block:
-        # per problem op_off [P + 1], then op_node, op_state, op_kind [capacity] (no per-array ctypes conversions)
         req = np.zeros(max(len(ask), 1), dtype=abi.BATCH_MOVES_DTYPE)
         keep = []
         P = np.array([fps[i].scalars["n_parts"] for i in ask], dtype=np.int64)
@@ -326,19 +323,88 @@ class Planner:
         req["capacity"][:len(ask)] = cap
         ptrs = np.zeros(max(n, 1), dtype=np.uint64)
         ptrs[ask] = req.ctypes.data + req.itemsize * np.arange(len(ask), dtype=np.uint64)
-        pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
-        rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
-        info = abi.BatchInfo()
-        self._check(self.lib.blance_plan_batch_moves(self._h, n, pbs, rss,
-                                                     ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
-                                                     C.byref(info)))
+        return ptrs, (n, ask, P, cap, base, block, req, keep)
+
+    @staticmethod
+    def _moves_unpack(state):
+        n, ask, P, cap, base, block, _, _ = state
         moves = [None] * n
         ends = (base[:-1] + P).tolist()
         totals = block[base[:-1] + P].tolist() if ask else []
         for j, i in enumerate(ask):
             e, t, c = ends[j] + 1, totals[j], max(int(cap[j]), 1)
             moves[i] = (block[e - int(P[j]) - 1:e], block[e:e + t], block[e + c:e + c + t], block[e + 2 * c:e + 2 * c + t])
-        return results, moves, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
+        return moves
+
+    def plan_batch_moves(self, fps, favor_min_nodes, beg_other=None):
+        """blance_plan_batch_moves(): plan_batch, and for each problem CalcPartitionMoves from its prevMap as passed to its
+        plan for every partition in partition id order.  favor_min_nodes: one bool, or one per problem where None asks for
+        no moves; beg_other: None, or per problem None or (offsets [P + 1], node ids) of prevMap's keys outside the model.
+        Returns ([FlatResult], [(op_off, op_node, op_state, op_kind) or None], info dict)."""
+        if not hasattr(self.lib, "blance_plan_batch_moves"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_moves (build the current sources)")
+        fps = list(fps)
+        n = len(fps)
+        results = [abi.FlatResult(fp) for fp in fps]
+        structs = [fp.as_struct() for fp in fps]
+        ptrs, state = self._moves_requests(fps, results, favor_min_nodes, beg_other)
+        pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
+        rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
+        info = abi.BatchInfo()
+        self._check(self.lib.blance_plan_batch_moves(self._h, n, pbs, rss,
+                                                     ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
+                                                     C.byref(info)))
+        return results, self._moves_unpack(state), {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
+
+    def plan_batch_stats(self, fps, stats=True, favor_min_nodes=None, beg_other=None):
+        """blance_plan_batch_stats(): plan_batch, and for each problem that asks the plan statistics of Planner.plan_stats
+        from the same device call.  stats: one bool or one per problem; favor_min_nodes / beg_other as in plan_batch_moves,
+        None: no moves at all.  Returns ([FlatResult], [moves or None], [stats dict or None], info dict); a stats dict has
+        the keys of Planner.plan_stats."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_batch_stats"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_stats (build the current sources)")
+        fps = list(fps)
+        n = len(fps)
+        results = [abi.FlatResult(fp) for fp in fps]
+        structs = [fp.as_struct() for fp in fps]
+        want = list(stats) if isinstance(stats, (list, tuple)) else [stats] * n
+        if len(want) != n:
+            raise ValueError("stats: one bool or one per problem")
+        mv_ptrs, mv_state = self._moves_requests(fps, results, favor_min_nodes, beg_other)
+        # the requests as one numpy block viewed as blance_plan_stats[], the arrays of all problems in one int64 block: per
+        # problem seven slots of max(M, 1) values in the order of abi.PLAN_STATS_ARRAYS (nodes_used: int32 in its slot)
+        ask = [i for i in range(n) if want[i]]
+        M = np.array([fps[i].scalars["n_states"] for i in ask], dtype=np.int64)
+        slot = np.maximum(M, 1)
+        base = np.zeros(len(ask) + 1, np.int64)
+        base[1:] = np.cumsum(len(abi.PLAN_STATS_ARRAYS) * slot)
+        block = np.zeros(max(int(base[-1]), 1), dtype=np.int64)
+        req = np.zeros(max(len(ask), 1), dtype=abi.PLAN_STATS_DTYPE)
+        req["n_states"][:len(ask)] = M
+        for k, name in enumerate(abi.PLAN_STATS_ARRAYS):
+            req[name][:len(ask)] = block.ctypes.data + 8 * (base[:-1] + k * slot)
+        st_ptrs = np.zeros(max(n, 1), dtype=np.uint64)
+        st_ptrs[ask] = req.ctypes.data + req.itemsize * np.arange(len(ask), dtype=np.uint64)
+        pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
+        rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
+        info = abi.BatchInfo()
+        self._check(self.lib.blance_plan_batch_stats(self._h, n, pbs, rss,
+                                                     mv_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
+                                                     st_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.PlanStats))),
+                                                     C.byref(info)))
+        out = [None] * n
+        block32 = block.view(np.int32)
+        n_next = req["n_nodes_next"].tolist()
+        starts, slots, ms = base.tolist(), slot.tolist(), M.tolist()
+        for j, i in enumerate(ask):
+            d = {}
+            for k, name in enumerate(abi.PLAN_STATS_ARRAYS):
+                at = starts[j] + k * slots[j]
+                d[name] = block32[2 * at:2 * at + ms[j]] if name == "nodes_used" else block[at:at + ms[j]]
+            d["n_nodes_next"] = n_next[j]
+            out[i] = d
+        return results, self._moves_unpack(mv_state), out, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
     def plan_stats(self, n_states):
         """Per-state load statistics of the map the last plan produced (blance_plan_stats_get):

@@ -164,6 +164,27 @@ def PlanNextMapExBatchMoves(calls, favorMinNodes=False, planner=None):
     return out
 
 
+def PlanNextMapExBatchStats(calls, planner=None):
+    """PlanNextMapExBatch, and each plan's quality numbers from the same device call (blance_plan_batch_stats): per state
+    the load over nodesNext (min, max, sum, sum of squares; a node's load is the summed weight of the partitions it holds
+    in that state), the nodes in use, the constraint slots left unmet and the (partition, slot) pairs that break a hierarchy
+    rule of the state.  Returns [(nextMap, warnings, {state name: {load_min, load_max, load_sum, load_sumsq, nodes_used,
+    unmet_slots, rule_violations}}, n_nodes_next)] in call order, with every call's write-back done as PlanNextMapEx does;
+    a call whose plan returns no map (MaxIterationsPerPlan <= 0) gets (None, None) with every number 0."""
+    from . import abi
+    names = ("prevMap", "partitionsToAssign", "nodesAll", "nodesToRemove", "nodesToAdd", "model", "options", "booster")
+    args = [dict(c) if isinstance(c, dict) else dict(zip(names, c)) for c in calls]
+    fps = [_build_call(**a) for a in args]
+    results, _, stats, _ = (planner or default_planner()).plan_batch_stats(fps, True)
+    out = []
+    for fp, res, a, st in zip(fps, results, args, stats):
+        nextMap, warnings = _finish_call(fp, res, a["prevMap"], a["partitionsToAssign"])
+        cols = {k: st[k].tolist() for k in abi.PLAN_STATS_ARRAYS}
+        bystate = {name: {k: cols[k][m] for k in abi.PLAN_STATS_ARRAYS} for m, name in enumerate(fp.state_names)}
+        out.append((nextMap, warnings, bystate, st["n_nodes_next"]))
+    return out
+
+
 def _beg_other(fp, prevMap):
     """prevMap's nodes under state keys outside the model, CSR over fp's partitions in its node id space (None if none)."""
     import numpy as np

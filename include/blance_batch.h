@@ -67,6 +67,24 @@ int blance_plan_batch_moves(blance_ctx* ctx, int32_t n, const blance_problem* co
                             blance_batch_moves* const* mvs /* mvs[i] may be NULL: no moves for problem i */,
                             blance_batch_info* info /* may be NULL */);
 
+/* ---- the same batch, and the plan statistics of each plan -------------------
+ * For every problem i with sts[i] != NULL, sts[i] receives exactly what blance_plan(ctx, pbs[i], res[i]) followed
+ * by blance_plan_stats_get(ctx, sts[i]) would write: n_nodes_next, per state load_min / load_max / load_sum /
+ * load_sumsq / nodes_used / unmet_slots, and rule_violations when that pointer is not NULL; all zeros with
+ * n_nodes_next = 0 for a plan with iterations == 0.  The caller owns the arrays; n_states is their capacity.
+ * Batched problems get theirs from k_batch_stats in the same call (one launch after the plan launches whenever at
+ * least one batched problem asks, the numbers in the same download: with moves and statistics a fully batched
+ * call is at most 4 launches); every other problem from the path of blance_plan_stats_get right after its plan.
+ * Every request is checked with its problem before anything runs (n_states below the problem's, one of the six
+ * mandatory arrays NULL): a refusal returns BLANCE_ERR_BAD_ARG, names the problem's index and writes no result, no
+ * moves and no statistics.  mvs follows blance_plan_batch_moves.  sts == NULL is exactly blance_plan_batch_moves;
+ * sts == NULL and mvs == NULL is exactly blance_plan_batch.  Afterwards the context holds no problem, as after every
+ * batch: blance_plan_stats_get answers BLANCE_ERR_BAD_ARG. */
+int blance_plan_batch_stats(blance_ctx* ctx, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                            blance_batch_moves* const* mvs /* may be NULL; mvs[i] may be NULL */,
+                            blance_plan_stats* const* sts /* may be NULL; sts[i] may be NULL: no statistics for problem i */,
+                            blance_batch_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
