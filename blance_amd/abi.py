@@ -286,6 +286,12 @@ class PlanStats(C.Structure):
                 ("rule_violations", C.POINTER(C.c_int64))]
 
 
+class PlanMoves(C.Structure):
+    """blance_plan_moves of include/blance_hip.h (blance_plan_moves_get): the moves request of the plan a context holds."""
+    _fields_ = [("favor_min_nodes", C.c_int32), ("beg_other_off", _i32p), ("beg_other_nodes", _i32p),
+                ("out", MovesResult), ("n_moves", C.c_int64), ("n_by_kind", C.c_int64 * 4), ("n_parts_moved", C.c_int64)]
+
+
 # blance_plan_stats as a numpy record (pointers as addresses): Planner.plan_batch_stats fills many at once
 PLAN_STATS_ARRAYS = ("load_min", "load_max", "load_sum", "load_sumsq", "nodes_used", "unmet_slots", "rule_violations")
 PLAN_STATS_DTYPE = np.dtype({

@@ -21,6 +21,7 @@
 #include "k_sweep.h"
 #include "k_flat.h"
 #include "k_period.h"
+#include "k_plan_moves.h"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
 #include "tu_seq.hip"
 #include "tu_tree.hip"
@@ -3066,6 +3067,126 @@ extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
     if (!c || !st) return fail(BLANCE_ERR_BAD_ARG, "null argument");
     std::lock_guard<std::mutex> g(c->mu);
     return plan_stats_locked(c, st);
+    });
+}
+
+// the partition moves of the map the context holds (blance_plan_moves_get): both maps are read where the
+// plan left them, k_plan_moves counts, the counts are scanned, k_plan_moves writes every move at its final place
+static int plan_moves_locked(blance_ctx* c, blance_plan_moves* mv) {
+    if (!c->planned) return fail(BLANCE_ERR_BAD_ARG, "nothing planned yet");
+    if (c->stats.iterations == 0) return fail(BLANCE_ERR_BAD_ARG, "the plan made no sweep (max_iterations <= 0): there is no map to move to");
+    blance_moves_result& o = mv->out;
+    const bool count_only = !o.op_node && !o.op_state && !o.op_kind && o.capacity == 0;
+    if (!count_only && (!o.op_node || !o.op_state || !o.op_kind || o.capacity < 0))
+        return fail(BLANCE_ERR_BAD_ARG, "null moves buffers (count only: all three NULL and capacity 0)");
+    if (!count_only && !o.op_off) return fail(BLANCE_ERR_BAD_ARG, "op_off is NULL but the move arrays are given");
+    if (!mv->beg_other_off != !mv->beg_other_nodes)
+        return fail(BLANCE_ERR_BAD_ARG, "beg_other_off and beg_other_nodes: both or neither");
+    const blance_problem& h = c->h;
+    const int P = h.n_parts, M = h.n_states;
+    int64_t n_other = 0;
+    if (mv->beg_other_off) {
+        const int32_t* off = mv->beg_other_off;
+        if (off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets must start at 0");
+        for (int p = 0; p < P; p++)
+            if (off[p + 1] < off[p]) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets not monotone");
+        n_other = off[P];
+        for (int64_t j = 0; j < n_other; j++)
+            if (mv->beg_other_nodes[j] < 0 || mv->beg_other_nodes[j] >= h.n_nodes_ext)
+                return fail(BLANCE_ERR_BAD_ARG, "beg_other node id outside [0, n_nodes_ext)");
+    }
+    HIPTRY(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
+    float ms = 0.f;
+    if (P > 0) {
+        constexpr size_t kHead = 1024;             // the six counter words, a cache line each, in front of n_moves [P + 1]
+        static_assert(6 * kPlanMovesCounterStride * sizeof(unsigned long long) <= kHead, "counters outgrew their block");
+        DevBuf &ooff = c->mv[0], &onod = c->mv[1], &nmov = c->mv[7], &cnode = c->mv[8], &cstate = c->mv[9], &ckind = c->mv[10];
+        if (nmov.reserve(kHead + sizeof(int32_t) * ((size_t)P + 2)) || ooff.reserve(sizeof(int32_t) * ((size_t)P + 2)) ||
+            onod.reserve(sizeof(int32_t) * ((size_t)n_other + 1)))
+            return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        int e = 0;
+        if (mv->beg_other_off) {                   // the call's only upload
+            Mover up(c, true);
+            c->stage.used = 0;                     // (the stream is idle between calls)
+            if ((e = up.copy(ooff.p, mv->beg_other_off, sizeof(int32_t) * ((size_t)P + 1)))) return e;
+            if ((e = up.copy(onod.p, mv->beg_other_nodes, sizeof(int32_t) * (size_t)n_other))) return e;
+            if ((e = up.flush())) return e;
+        }
+        const DevProblem d = result_problem(c);
+        PlanMovesParams q;
+        memset(&q, 0, sizeof q);
+        q.P = P; q.M = M; q.L = d.L; q.favor_min_nodes = mv->favor_min_nodes ? 1 : 0;
+        q.beg_off = c->p_off.as<int32_t>(); q.beg_nodes = c->p_nodes.as<int32_t>(); q.in_prev = c->part_in_prev.as<uint8_t>();
+        if (mv->beg_other_off) { q.other_off = ooff.as<int32_t>(); q.other_nodes = onod.as<int32_t>(); }
+        q.end = d.live; q.end_len = d.live_len; q.end_kind = d.live_kind;
+        q.counters = nmov.as<unsigned long long>();
+        q.n_moves = (int32_t*)((char*)nmov.p + kHead);
+        HIPTRY(hipMemsetAsync(nmov.p, 0, kHead, sm));
+        HIPTRY(hipEventRecord(c->ev0, sm));
+        const int wgs1 = cdiv((int64_t)P + 1, 256);
+        BLANCE_LAUNCH(k_plan_moves<false>, wgs1 < kPlanMovesMaxWgs ? wgs1 : kPlanMovesMaxWgs, 256, sizeof(int) * 5 * 4, sm, q);
+        const bool scanned = !count_only || o.op_off;
+        if (scanned) SCANTRY(P + 1, q.n_moves);
+        if (count_only) HIPTRY(hipEventRecord(c->ev1, sm));
+        // the one host round trip: the total sizes the download, the six counter words come with it
+        int32_t total = 0;
+        unsigned long long lines[6 * kPlanMovesCounterStride];
+        HIPTRY(read_back(c, lines, q.counters, sizeof lines));
+        if (scanned) HIPTRY(read_back(c, &total, q.n_moves + P, sizeof total));
+        HIPTRY(stream_sync(c));
+        HIPTRY(hipGetLastError());
+        for (int k = 0; k < 6; k++) cnt[k] = lines[k * kPlanMovesCounterStride];
+        if (cnt[0] > (unsigned long long)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "more than 2^31 moves");
+        if (scanned && (unsigned long long)total != cnt[0]) return fail(BLANCE_ERR_DEVICE, "k_plan_moves: the counts and the counters disagree");
+        if (!count_only && (int64_t)cnt[0] > o.capacity) {
+            mv->n_moves = (int64_t)cnt[0];
+            for (int k = 0; k < 4; k++) mv->n_by_kind[k] = (int64_t)cnt[1 + k];
+            mv->n_parts_moved = (int64_t)cnt[5];
+            return fail(BLANCE_ERR_CAPACITY, "moves capacity too small");
+        }
+        Mover down(c, false);
+        c->stage.used = 0;
+        if (!count_only) {
+            const size_t n = (size_t)cnt[0];
+            if (cnode.reserve(sizeof(int32_t) * (n + 1)) || cstate.reserve(sizeof(int32_t) * (n + 1)) || ckind.reserve(sizeof(int32_t) * (n + 1)))
+                return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+            q.op_node = cnode.as<int32_t>(); q.op_state = cstate.as<int32_t>(); q.op_kind = ckind.as<int32_t>();
+            if (n) BLANCE_LAUNCH_NOSYNC(k_plan_moves<true>, cdiv(P, 256), 256, 0, sm, q);
+            HIPTRY(hipEventRecord(c->ev1, sm));
+            if (n && ((e = down.copy(o.op_node, cnode.p, sizeof(int32_t) * n)) || (e = down.copy(o.op_state, cstate.p, sizeof(int32_t) * n)) ||
+                      (e = down.copy(o.op_kind, ckind.p, sizeof(int32_t) * n))))
+                return e;
+        }
+        if (o.op_off && (e = down.copy(o.op_off, q.n_moves, sizeof(int32_t) * ((size_t)P + 1)))) return e;
+        if ((e = down.finish())) return e;
+        HIPTRY(stream_sync(c));
+        HIPTRY(hipGetLastError());
+        HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    } else if (o.op_off) {
+        o.op_off[0] = 0;
+    }
+    o.device_ms = ms;
+    mv->n_moves = (int64_t)cnt[0];
+    for (int k = 0; k < 4; k++) mv->n_by_kind[k] = (int64_t)cnt[1 + k];
+    mv->n_parts_moved = (int64_t)cnt[5];
+    return BLANCE_OK;
+}
+
+extern "C" int64_t blance_plan_moves_capacity(const blance_problem* pb, const blance_plan_moves* mv) {
+    if (!pb || !pb->prev_off || pb->n_parts < 0 || pb->n_states < 0) return 0;
+    int64_t cap = pb->prev_off[(size_t)pb->n_parts * pb->n_states] + blance_result_capacity(pb);
+    if (mv && mv->beg_other_off) cap += mv->beg_other_off[pb->n_parts];
+    return cap;
+}
+
+extern "C" int blance_plan_moves_get(blance_ctx* c, blance_plan_moves* mv) {
+    return guarded([&]() -> int {
+    if (!c || !mv) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    rb_discard(c);
+    return settle(c, plan_moves_locked(c, mv));
     });
 }
 

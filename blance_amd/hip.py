@@ -18,7 +18,8 @@ EXPORTS = ["blance_abi_version", "blance_last_error", "blance_result_capacity", 
            "blance_ctx_create", "blance_ctx_destroy", "blance_plan", "blance_upload",
            "blance_plan_resident", "blance_download", "blance_calc_moves", "blance_plan_stats_get",
            "blance_comm_unique_id", "blance_comm_init_rccl", "blance_comm_set", "blance_comm_stats",
-           "blance_is_emulated", "blance_host_alloc", "blance_host_free", "blance_comm_time_ms", "blance_host_trim"]
+           "blance_is_emulated", "blance_host_alloc", "blance_host_free", "blance_comm_time_ms", "blance_host_trim",
+           "blance_plan_moves_capacity", "blance_plan_moves_get"]
 
 _libs = {}
 
@@ -95,10 +96,48 @@ def load_library(path=None):
         lib.blance_plan_batch_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
                                                 C.POINTER(C.POINTER(abi.Result)), C.POINTER(C.POINTER(abi.BatchMoves)),
                                                 C.POINTER(C.POINTER(abi.PlanStats)), C.POINTER(abi.BatchInfo)]
+    # declared in blance_hip.h, additive to ABI 6: an older library of the same version loads, Planner.plan_moves refuses
+    if hasattr(lib, "blance_plan_moves_get"):
+        lib.blance_plan_moves_get.restype = C.c_int
+        lib.blance_plan_moves_get.argtypes = [C.c_void_p, C.POINTER(abi.PlanMoves)]
+        lib.blance_plan_moves_capacity.restype = C.c_int64
+        lib.blance_plan_moves_capacity.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.PlanMoves)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
     return lib
+
+
+def moves_problem_of(fp, res, beg_other=None):
+    """The arguments of Planner.calc_moves for "from fp's prevMap to the plan `res`": both maps as CSRs over
+    p * (M + 1) + state (pseudo state M: beg_other, the (offsets [P + 1], node ids) of prevMap's keys outside the model).
+    The host route to a plan's moves, which Planner.plan_moves replaces.  Returns (beg_off, beg_nodes, end_off, end_nodes)."""
+    import numpy as np
+    P, M = fp.scalars["n_parts"], fp.scalars["n_states"]
+
+    def widen(off, nodes, other):
+        off = np.asarray(off[:P * M + 1], dtype=np.int64)
+        lens = np.zeros((P, M + 1), dtype=np.int64)
+        lens[:, :M] = np.diff(off).reshape(P, M)
+        total = int(off[-1])
+        if other is None:
+            out_nodes = np.asarray(nodes[:total], dtype=np.int32)
+        else:
+            ooff, onodes = np.asarray(other[0][:P + 1], dtype=np.int64), np.asarray(other[1], dtype=np.int32)
+            lens[:, M] = np.diff(ooff)
+            out_nodes = np.empty(total + int(ooff[-1]), dtype=np.int32)
+            per_part = off[::M][:P + 1] if M else np.zeros(P + 1, dtype=np.int64)     # model entries in front of partition p
+            part_of = np.repeat(np.arange(P), np.diff(per_part))
+            out_nodes[np.arange(total) + ooff[part_of]] = nodes[:total]
+            part_of = np.repeat(np.arange(P), np.diff(ooff))
+            out_nodes[np.arange(int(ooff[-1])) + per_part[part_of + 1]] = onodes[:int(ooff[-1])]
+        wide = np.zeros(P * (M + 1) + 1, dtype=np.int32)
+        wide[1:] = np.cumsum(lens.reshape(-1))
+        return wide, out_nodes
+
+    beg_off, beg_nodes = widen(fp.arrays["prev_off"], fp.arrays["prev_nodes"], beg_other)
+    end_off, end_nodes = widen(res.out_off, res.out_nodes, None)
+    return beg_off, beg_nodes, end_off, end_nodes
 
 
 class _PinnedBlock:
@@ -270,6 +309,7 @@ class Planner:
     def plan(self, fp):
         """blance_plan(): host buffers in, host buffers out."""
         res = abi.FlatResult(fp)
+        self._fp = fp
         self._check(self.lib.blance_plan(self._h, C.byref(fp.as_struct()), C.byref(res.struct)))
         return res
 
@@ -423,6 +463,47 @@ class Planner:
         out["nodes_used"] = used[:n_states]
         out["n_nodes_next"] = int(st.n_nodes_next)
         return out
+
+    def plan_moves(self, favor_min_nodes, beg_other=None, count_only=False, capacity=None, arena=None):
+        """blance_plan_moves_get(): CalcPartitionMoves from prevMap as uploaded to the map the last plan / plan_resident of
+        this planner produced, for every partition in partition id order, computed from the maps on the device.
+        beg_other: None or (offsets [P + 1], node ids) of prevMap's keys outside the model; capacity: entries of the three
+        move arrays (None: blance_plan_moves_capacity, which always suffices); arena: a HostArena for the output arrays.
+        Returns ((op_off, op_node, op_state, op_kind), info) -- the arrays cut to the moves made -- or (None, info) when
+        count_only; info: n_moves, n_by_kind {"add", "del", "promote", "demote"}, n_parts_moved, device_ms.  A capacity
+        that is too small raises BlanceError(ERR_CAPACITY) with the counters in its `info`."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_moves_get"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_moves_get (build the current sources)")
+        mv = abi.PlanMoves()
+        mv.favor_min_nodes = int(bool(favor_min_nodes))
+        keep = []
+        if beg_other is not None:
+            off, nodes = [np.ascontiguousarray(a, dtype=np.int32) for a in beg_other]
+            keep = [off, nodes if nodes.size else np.zeros(1, dtype=np.int32)]
+            mv.beg_other_off, mv.beg_other_nodes = [a.ctypes.data_as(C.POINTER(C.c_int32)) for a in keep]
+        out = None
+        if not count_only:
+            fp = getattr(self, "_fp", None)
+            if fp is None:
+                raise BlanceError(abi.ERR_BAD_ARG, "nothing planned yet")
+            if capacity is None:
+                capacity = int(self.lib.blance_plan_moves_capacity(C.byref(fp.as_struct()), C.byref(mv)))
+            new = (lambda n, dt: np.empty(n, dtype=dt)) if arena is None else arena.empty
+            out = [new(fp.scalars["n_parts"] + 1, np.int32)] + [new(max(int(capacity), 1), np.int32) for _ in range(3)]
+            mv.out.op_off, mv.out.op_node, mv.out.op_state, mv.out.op_kind = [a.ctypes.data_as(C.POINTER(C.c_int32)) for a in out]
+            mv.out.capacity = int(capacity)
+        st = self.lib.blance_plan_moves_get(self._h, C.byref(mv))
+        info = {"n_moves": int(mv.n_moves), "n_by_kind": {k: int(mv.n_by_kind[i]) for i, k in enumerate(abi.OP_NAMES)},
+                "n_parts_moved": int(mv.n_parts_moved), "device_ms": float(mv.out.device_ms)}
+        if st != abi.OK:
+            err = BlanceError(st, (self.lib.blance_last_error() or b"").decode())
+            err.info = info if st == abi.ERR_CAPACITY else None
+            raise err
+        if count_only:
+            return None, info
+        n = info["n_moves"]
+        return (out[0], out[1][:n], out[2][:n], out[3][:n]), info
 
     def calc_moves(self, n_states, favor_min_nodes, beg_off, beg_nodes, end_off, end_nodes):
         """blance_calc_moves(): CalcPartitionMoves for every partition (CSR over

@@ -298,6 +298,41 @@ typedef struct blance_plan_stats {
 
 int blance_plan_stats_get(blance_ctx* ctx, blance_plan_stats* stats);
 
+/* ---- the partition moves of the plan the context holds (additive to ABI 6: look the symbols up before use) --------
+ * What the orchestrator needs next (orchestrate.go:273-287), from the maps where they lie on the device: for the map
+ * the last blance_plan / blance_plan_resident of this context produced (the precondition of blance_plan_stats_get),
+ * out receives exactly what blance_calc_moves would return for
+ *   CalcPartitionMoves(sortStateNames(model), prevMap[name].NodesByState, nextMap[name].NodesByState, favor_min_nodes)
+ * over every partition of partitionsToAssign in partition id order: prevMap as it was uploaded (before the write-back
+ * of plan.go:49-52, however many plans ran since), node ids in the problem's own id space, an absent list counts as
+ * empty on either side, a partition with !part_in_prev has an empty begin map.  beg_other: prevMap[name]'s nodes under
+ * state keys that are not in the model, with the meaning blance_batch.h documents for blance_batch_moves; they only
+ * feed flattenNodesByState (moves.go:60-64).
+ * Count only: op_node, op_state and op_kind all NULL and capacity 0 -- the three counters are written and nothing else
+ * is downloaded (op_off may then be NULL too; it is filled when given).  The counters are written on every successful
+ * call.  Capacity: blance_plan_moves_capacity() always suffices; a smaller one is accepted when the plan's moves fit.
+ * When they do not, the call returns BLANCE_ERR_CAPACITY with the counters written (size a retry by n_moves) and no
+ * array touched.
+ * BLANCE_ERR_BAD_ARG, nothing launched and nothing written: a NULL argument; nothing planned yet, or the context holds
+ * no problem (as after any blance_plan_batch*); a plan with iterations == 0 (PlanNextMapEx returned no map); op_off
+ * NULL while the move arrays are given, or only some of the three given; beg_other with one pointer NULL, offsets that
+ * do not start at 0 or are not monotone, an id outside [0, n_nodes_ext).
+ * The call does not disturb the context: blance_download, blance_plan_stats_get and blance_plan_resident behave after
+ * it as without it.  On a context with a communicator it makes no collective (every rank holds the whole map). */
+typedef struct blance_plan_moves {
+    int32_t favor_min_nodes;          /* in */
+    const int32_t* beg_other_off;     /* in, may both be NULL: CSR over partitions, [P + 1], ids < n_nodes_ext */
+    const int32_t* beg_other_nodes;
+    blance_moves_result out;          /* op_off [P + 1]; op_node / op_state / op_kind [capacity]; device_ms */
+    int64_t n_moves;                  /* out: all moves */
+    int64_t n_by_kind[4];             /* out: moves per BLANCE_OP_* */
+    int64_t n_parts_moved;            /* out: partitions with at least one move */
+} blance_plan_moves;
+
+/* prev_off[P*M] + beg_other_off[P] + blance_result_capacity(pb): the bound of blance_batch_moves_capacity */
+int64_t blance_plan_moves_capacity(const blance_problem* pb, const blance_plan_moves* mv);
+int blance_plan_moves_get(blance_ctx* ctx, blance_plan_moves* mv);
+
 /* ---- one plan on several GPUs (BASELINE.json config 4) ------------------------------------
  * The steps of a state pass that runs as region chains (one chain per hierarchy region)
  * shard over the ranks by region: every rank holds the whole problem (upload the same problem on
