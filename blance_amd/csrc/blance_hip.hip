@@ -260,7 +260,7 @@ struct blance_ctx : CtxHandles {
     bool no_stay_top = false;       // test knob (& 64): never k_stay_by_top
     bool force_stay_top = false;    // test knob (& 128): try k_stay_by_top in every chain pass with NumPartitions > 0
     bool periodic = true;           // an all-blank chain pass with periodic records walks two periods (k_period.h); off: & 256, or BLANCE_PERIODIC=0
-    int periodic_cut = 0;           // test knob BLANCE_PERIODIC_CUT (k_period_clamp)
+    int periodic_cut = 0;           // test knob BLANCE_PERIODIC_CUT (k_period_segments)
     DevBuf cnt_base, xbuf, gath;    // sharded pass: loads at pass start, [flags | load change], gathered output slices
     std::vector<int32_t> h_reg_off; // host copy of the chain offsets (slice sizes of the all-gather)
     int chain_group_state = -1;     // the state whose chain pass last grouped the steps by region (chain_order, chain_oi, reg_off) ...
@@ -1319,7 +1319,7 @@ static int flat_chain_prepare(blance_ctx* c, FlatChainPrep& fc, int64_t* launche
                          fc.order, (const int32_t*)nullptr, c->state_stick.as<int32_t>(),
                          c->state_has_stick.as<uint8_t>(), c->fl_iota.as<int32_t>(),
                          c->fl_zero.as<int32_t>(), c->fl_reglo.as<int32_t>(), c->fl_iota.as<int32_t>(),
-                         c->fl_one.as<int32_t>(), 1,
+                         c->fl_one.as<int32_t>(), 1, 0,
                          c->crec.as<int32_t>(), flags, (int32_t*)nullptr, kNoGate);
     int32_t bad = 0;
     HIPTRY(read_back(c, &bad, flags + kFlagNotLocal, sizeof bad));
@@ -1327,6 +1327,16 @@ static int flat_chain_prepare(blance_ctx* c, FlatChainPrep& fc, int64_t* launche
     *launches += 1;
     fc.ok = !bad;                                  // (bad: some step does not fit the compact record)
     return 0;
+}
+
+// The opening pass of a plan from nothing that run_flat_pass settles as one fresh run in (key, node) order without looking at
+// a step record: every partition to assign holds no node and has no weight of its own, so no step is a stay and every step
+// is fresh with weight 1 (known_run); integer keys from counters that all start at zero make the run a round robin over
+// nodesNext (k_fresh_cycle); and no step excludes a node.  Asked by run_pass_in_order before it gathers, and by run_flat_pass.
+// (NumPartitions == 0 here: the stay test's row bound, which would ride on the gather, is not wanted.)
+static bool fresh_cycle_whole(const blance_ctx* c, bool opening, int NP, int k, int higher_mask) {
+    return opening && c->assign_empty && c->h.partition_weights_nil && c->speculate > 0 && NP == 0 && !c->any_node_weight &&
+           c->counts_start_zero && higher_mask == 0 && k == 1 && c->n_alive > 0 && c->h.n_parts > 0;
 }
 
 // A flat pass (no hierarchy rule for the state): runs of certain stays and of
@@ -1366,24 +1376,35 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
         // The stay test of the whole pass on the live lists (no step records: k_gather is not run), its row bound counted
         // from them as well; the verdict stays on the device.  What the pass would then do -- nothing, see `settled` below --
         // is done: no output, no k_scatter, and the top priority nodes are where they were.
+        // One launch for what the test reads (the row bound only when NP > 0), one for the test, which leaves its verdict
+        // word itself: open_sweep's fill zeroes kFlagTopMoved with the chain flags, nothing between that fill and this pass
+        // writes it, and nobody needs the first step that moved.
         if (q.NP > 0) {
             if (rowcount_reset(c)) return BLANCE_ERR_DEVICE;
-            BLANCE_LAUNCH(k_flat_row_count_live, cdiv(P, 256), 256, 0, sm, fc.d, q.top_state, c->f_row_count.as<int32_t>(), q.NX);
-            *launches += 1;
+            BLANCE_LAUNCH(k_flat_prepare_count_live, 1 + cdiv(P, 1024), 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
+                          c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>(), fc.d, c->f_row_count.as<int32_t>());
+            if (c->trace) fprintf(stderr, "[blance] flat pass state %d: the row count rides on k_flat_prepare's launch\n", q.s);
+        } else {
+            prepare();
         }
-        prepare();
-        const int scan_blocks = cdiv(P, 256);
-        fq.scan_waves = scan_blocks * 4;
-        if (c->scan_part.reserve(sizeof(int32_t) * 2 * ((size_t)fq.scan_waves + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-        fq.scan_part = c->scan_part.as<int32_t>();
-        BLANCE_LAUNCH(k_flat_stay_live, scan_blocks, 256, 0, sm, fq, fc.d, fc.order, c->state_stick.as<int32_t>(),
-                      c->state_has_stick.as<uint8_t>());
-        BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, (int32_t*)nullptr,
-                      scal + kScalFlags + kFlagTopMoved, P);
-        *launches += 3;
+        BLANCE_LAUNCH(k_flat_stay_live, cdiv(P, 256), 256, 0, sm, fq, fc.d, fc.order, c->state_stick.as<int32_t>(),
+                      c->state_has_stick.as<uint8_t>(), scal + kScalFlags + kFlagTopMoved);   // (uses a wave ballot)
+        if (c->trace) fprintf(stderr, "[blance] flat pass state %d: k_flat_stay_live leaves the verdict word, no k_flat_scan_min\n", q.s);
+        // (kernel_launches is the driver's own tally, pinned mode by mode in tests/test_driver_decisions_emulated.py; the steps
+        // folded away here and in the other shortcuts still count in it.  What runs on the stream is in profiles/.)
+        *launches += q.NP > 0 ? 4 : 3;
         if (q.s == q.top_state) c->tops_moved = false;
         *nothing_to_apply = true;
         *batched += P;
+        return 0;
+    }
+    if (fresh_cycle_whole(c, opening, q.NP, q.k, q.higher_mask)) {       // (q.rec has NOT been gathered)
+        BLANCE_LAUNCH_NOSYNC(k_fresh_cycle_commit, cdiv(P > q.N ? P : q.N, 256), 256, 0, sm, fq, P, c->n_alive,
+                             c->alive_ids.as<int32_t>(), c->alive_rank.as<int32_t>(), q.cnt);
+        if (c->trace) fprintf(stderr, "[blance] flat pass state %d: a plan from nothing, the pass committed as a round robin without its records\n", q.s);
+        *launches += 5;                            // (the tally of the path it replaces, see assume_stays above)
+        *batched += P;
+        *whole_known = true;
         return 0;
     }
     if (q.NP > 0 && !rows_counted) {                // only read by the stay test when NP > 0; (else: k_gather has counted)
@@ -1917,15 +1938,25 @@ int ChainPass::classify_and_group() {
     // (c->top_gate: the sweep's first pass is taken to be one run of stays -- plan_locked -- and every launch of this pass
     // waits for that verdict: closed, it returns at once)
     top_gate = Gate{flags, c->top_gate};
-    BLANCE_LAUNCH_NOSYNC(k_chain_classify, cdiv(P + 1, 256), 256, 0, sm, d, m, h.top_state,
-                         a.order, rr.node_region.as<int32_t>(), c->regid.as<int32_t>(),
-                         c->n_ev.as<int32_t>(), flags, top_gate);
     // The steps grouped by the region of their top priority node (a stable counting sort of the pass order).  A sweep whose
     // top-state pass was one run of stays has moved no top priority node, and from sweep 2 on the pass order is the static
     // order: the grouping of this state's last chain pass -- chain_order, chain_oi, reg_off -- still stands (config 3's
     // third sweep: six launches less).
     regroup = !(a.same_tops && c->chain_group_state == m && c->chain_group_static && a.order == c->part_order.as<int32_t>() &&
                 c->h_reg_off.size() == (size_t)B + 1);
+    // A pass that reuses its grouping has nothing else to learn from the classification's round trip: with the top priority
+    // nodes where they were, events and orphans come from this state's own nodes having left their partition's region since --
+    // rare enough to assume there are none and to look at flags[kFlagOrphans], flags[kFlagEvents] only when the pass's own
+    // flags come back.  Such a pass reads neither the region ids nor the event counts, and k_gather_chain, which walks the
+    // same lists right behind, raises the two words itself (gather_chain_record's `classify`): no k_chain_classify.
+    spec = run.allow_spec && !regroup && !sharded && c->speculate > 0;
+    if (!spec) {
+        BLANCE_LAUNCH_NOSYNC(k_chain_classify, cdiv(P + 1, 256), 256, 0, sm, d, m, h.top_state,
+                             a.order, rr.node_region.as<int32_t>(), c->regid.as<int32_t>(),
+                             c->n_ev.as<int32_t>(), flags, top_gate);
+    } else {
+        if (c->trace) fprintf(stderr, "[blance] chain pass state %d: no k_chain_classify, k_gather_chain raises its flag words\n", m);
+    }
     if (regroup) {
         const int ge = group_by_key(c, sm, c->scan_sums, P, c->regid.as<int32_t>(), a.order, B, c->bucket_counts.as<int32_t>(),
                                     c->reg_off.as<int32_t>(), c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>());
@@ -1938,10 +1969,6 @@ int ChainPass::classify_and_group() {
     } else if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the grouping by region of the last sweep stands\n", m);
     // events: how many?  (also: is every step region-local at all, are there orphan nodes); a sharded
     // plan reads the chain offsets in the same round trip (the slice sizes of collective B)
-    // A pass that reuses its grouping has nothing else to learn from this round trip: with the top priority nodes where they
-    // were, events and orphans come from this state's own nodes having left their partition's region since -- rare enough to
-    // assume there are none and to look at flags[kFlagOrphans], flags[kFlagEvents] only when the pass's own flags come back.
-    spec = run.allow_spec && !regroup && !sharded && c->speculate > 0;
     defer = run.defer && !sharded && c->speculate > 0;
     if (c->top_gate && (regroup || !spec || !defer))               // (top_spec_fits rules these out)
         return fail(BLANCE_ERR_DEVICE, "a chain pass behind the top-state pass's verdict would read back");
@@ -2035,7 +2062,7 @@ int ChainPass::gather_records() {
                          c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>(), c->state_stick.as<int32_t>(),
                          c->state_has_stick.as<uint8_t>(), c->node_leaf_pos.as<int32_t>(),
                          rr.node_region.as<int32_t>(), rr.reg_lo.as<int32_t>(), rr.leaf_cls.as<int32_t>(),
-                         rr.cls_size.as<int32_t>(), 0,
+                         rr.cls_size.as<int32_t>(), 0, spec ? 1 : 0,
                          c->crec.as<int32_t>(), flags, group_now ? c->topkey.as<int32_t>() : (int32_t*)nullptr, top_gate);
     if (group_ahead) {
         HIPTRY(hipEventRecord(c->side_go, sm));        // (the keys are written)
@@ -2134,14 +2161,11 @@ int ChainPass::periodic_walk(bool* walked) {
     RESERVE(period, sizeof(int32_t) * ((size_t)kPWords * B + 1));
     RESERVE(cnt_p1, sizeof(int32_t) * (cnt_words + 1));
     int32_t* pb = c->period.as<int32_t>();
-    const int gx = cdiv(max_len, 256), gl = cdiv(rr.max_size, 64);
-    BLANCE_LAUNCH_NOSYNC(k_period_init, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, pb);
-    const int gf = cdiv(std::min(max_len, kPeriodCap + 1), 256);
-    BLANCE_LAUNCH_NOSYNC(k_period_find, gf * B, 256, 0, sm, B, gf, cq.reg_off, cq.crec, pb);
+    const int gx = cdiv(max_len, 256);
+    BLANCE_LAUNCH(k_period_find, B, 1024, 64, sm, B, cq.reg_off, cq.crec, pb);
     const int gv = cdiv((long long)max_len * (kCW / 4), 256);
     BLANCE_LAUNCH_NOSYNC(k_period_verify, gv * B, 256, 0, sm, B, gv, cq.reg_off, cq.crec, pb);
-    if (c->periodic_cut > 0) BLANCE_LAUNCH_NOSYNC(k_period_clamp, cdiv(B, 64), 64, 0, sm, B, c->periodic_cut, pb);
-    BLANCE_LAUNCH_NOSYNC(k_period_segments, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, pb);
+    BLANCE_LAUNCH_NOSYNC(k_period_segments, cdiv(B, 64), 64, 0, sm, B, c->periodic_cut > 0 ? c->periodic_cut : 0, cq.reg_off, pb);
     ChainParams sq = cq;
     // (the plane automaton for regions of up to 128 leaves, the lane-minimum kernel for wider ones)
     auto walk = [&](int beg_row, int end_row) {
@@ -2152,25 +2176,25 @@ int ChainPass::periodic_walk(bool* walked) {
     *walked = true;
     HIPTRY(hipMemcpyAsync(c->cnt_p1.p, c->cnt.p, sizeof(int32_t) * cnt_words, hipMemcpyDeviceToDevice, sm));
     walk(kPBeg2, kPEnd2);
-    BLANCE_LAUNCH_NOSYNC(k_period_state_max, gl * B, 64, 0, sm, B, gl, m, N, NX, cq.reg_lo, cq.reg_hi, cq.leaf_node,
-                         cq.alive, c->cnt_p1.as<int32_t>(), cq.cnt, pb);
-    BLANCE_LAUNCH_NOSYNC(k_period_state_check, gl * B, 64, 0, sm, B, gl, m, N, NX, cq.reg_lo, cq.reg_hi, cq.leaf_node,
-                         cq.alive, c->cnt_p1.as<int32_t>(), cq.cnt, pb);
-    BLANCE_LAUNCH_NOSYNC(k_period_verdict, cdiv(B, 64), 64, 0, sm, B, cq.reg_off, cq.flags, pb);
+    // (128 threads: a trip over the leaves of config 3's regions; wider regions take two)
+    BLANCE_LAUNCH(k_period_judge, B, 128, 64, sm, B, m, N, NX, OW, cq.reg_off, cq.reg_lo, cq.reg_hi, cq.leaf_node, cq.alive,
+                  cq.crec, cq.out, cq.flags, c->cnt_p1.as<int32_t>(), cq.cnt, pb);
     BLANCE_LAUNCH_NOSYNC(k_period_replicate, gx * B, 256, 0, sm, B, gx, OW, cq.reg_off, pb, cq.out);
-    BLANCE_LAUNCH(k_period_counts, B, 256, 0, sm, B, m, N, NX, OW, cq.reg_off, cq.reg_lo, cq.reg_hi, cq.leaf_node,
-                  cq.alive, cq.crec, cq.out, pb, cq.cnt);
+    if (c->trace) fprintf(stderr, "[blance] chain pass state %d: periodic walk, the regions set up by k_period_find and judged by k_period_judge\n", m);
     walk(kPBeg3, kPEnd3);
     pr.launches += 11;
     if (c->trace) {
         std::vector<int32_t> hp((size_t)kPWords * B);
         HIPTRY(hipMemcpyAsync(hp.data(), pb, sizeof(int32_t) * hp.size(), hipMemcpyDeviceToHost, sm));
         HIPTRY(stream_sync(c));
-        int64_t copied = 0; int n_ok = 0;
-        for (int r = 0; r < B; r++)
-            if (hp[(size_t)kPOk * B + r]) { n_ok++; copied += hp[(size_t)kPLimit * B + r] - 2 * hp[(size_t)kPT * B + r]; }
-        fprintf(stderr, "[blance] chain pass state %d: periodic records in %d of %d regions (period %d in the first), %lld of %d steps copied\n",
-                m, n_ok, B, hp[(size_t)kPT * B], (long long)copied, P);
+        int64_t copied = 0; int n_ok = 0, n_refused = 0;     // refused: joined, then failed k_period_judge -- walked on behind 2T
+        for (int r = 0; r < B; r++) {
+            const int32_t T = hp[(size_t)kPT * B + r], limit = hp[(size_t)kPLimit * B + r];
+            if (hp[(size_t)kPOk * B + r]) { n_ok++; copied += limit - 2 * T; }
+            else if (T >= 1 && T <= kPeriodCap && (long long)limit >= (long long)kPeriodMinRounds * T) n_refused++;
+        }
+        fprintf(stderr, "[blance] chain pass state %d: periodic records in %d of %d regions (period %d in the first), %lld of %d steps copied, "
+                        "%d joined and were refused\n", m, n_ok, B, hp[(size_t)kPT * B], (long long)copied, P, n_refused);
     }
     return 0;
 }
@@ -2408,11 +2432,12 @@ static int open_sweep(blance_ctx* c, PlanRun& pr, Sweep& sw) {
     sw.opened = c->tail_counted;
     c->tail_counted = false;
     if (sw.opened) std::swap(c->cnt, c->cnt_next);
-    {   // one launch: warn_count / not_match, the chain flags, stateNodeCounts (plan.go:94) unless counted already, the flat
+    {   // one launch: warn_count / not_match, the chain flags, the settled pass's verdict word, stateNodeCounts (plan.go:94) unless counted already, the flat
         // passes' row counts, and the counters this sweep's tail counts the next sweep's into
         FillCopyJob fj;
         fj.zero(scal + kScalWarnCount, 2);
         fj.zero(scal + kScalFlags, kChainFlags);
+        fj.zero(scal + kScalFlags + kFlagTopMoved, 1);      // (k_flat_stay_live only ever stores a 1 there)
         if (!sw.opened) fj.zero(c->cnt.p, (int64_t)(M + 1) * (NX + 1));
         if (sw.NP > 0 && c->f_row_count.p) fj.zero(c->f_row_count.p, (int64_t)NX + 1);
         if (pr.fuse) fj.zero(c->cnt_next.p, (int64_t)(M + 1) * (NX + 1));
@@ -2489,8 +2514,13 @@ static int run_pass_in_order(blance_ctx* c, PlanRun& pr, Sweep& sw, const StateP
     const bool count_rows = bulk && sw.NP > 0 && c->f_row_count.p;
     const bool settled = bulk && !sw.first && pr.at.passes_this_sweep == 1 && !sw.retrying && c->dump_sweep < 0 && c->speculate > 0;
     const bool assume_stays = settled && pr.top_spec_plan && !sw.top_spec_off && k == 1 && top_spec_fits(c, pr, sw, m);
+    // (what the sweep's passes so far have been: known_passes of them fresh runs known in advance, the last one
+    // of state known_state with known_k picks a step)
+    const bool opening = bulk && sw.first && !sw.retrying && !sw.known_broken &&
+                         (sw.known_passes == 0 || (sw.known_passes == 1 && sw.known_k == 1 && sw.NP == 0 && ((sp.higher_mask >> sw.known_state) & 1)));
+    const bool ungathered = assume_stays || fresh_cycle_whole(c, opening, sw.NP, k, sp.higher_mask);   // (no step record is read)
     if (count_rows && !assume_stays && rowcount_reset(c)) return BLANCE_ERR_DEVICE;
-    if (!assume_stays)
+    if (!ungathered)
         BLANCE_LAUNCH(k_gather, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (RW | 1) + 64, sm, d, m, h.top_state, RW, sp.order,
                              c->state_stick.as<int32_t>(), c->state_has_stick.as<uint8_t>(), c->rec.as<int32_t>(),
                              count_rows ? c->f_row_count.as<int32_t>() : (int32_t*)nullptr, NX);
@@ -2532,10 +2562,6 @@ static int run_pass_in_order(blance_ctx* c, PlanRun& pr, Sweep& sw, const StateP
     // the flat bulk driver: k = 1, and the first sweep of a fresh plan (NumPartitions == 0) with k = 2
     if (bulk) {
         c->pass_kind[n_pass] = kPassFlatBulk;
-        // (what the sweep's passes so far have been: known_passes of them fresh runs known in advance, the last one
-        // of state known_state with known_k picks a step)
-        const bool opening = sw.first && !sw.retrying && !sw.known_broken &&
-                             (sw.known_passes == 0 || (sw.known_passes == 1 && sw.known_k == 1 && sw.NP == 0 && ((sp.higher_mask >> sw.known_state) & 1)));
         bool whole_known = false;
         if (assume_stays) sw.last_stays_open = c->last_stays;
         e = run_flat_pass(c, q, scal, &pr.launches, &pr.at.batched, fc, opening, &whole_known, settled, assume_stays, &nothing_to_apply,

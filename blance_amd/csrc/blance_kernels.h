@@ -99,7 +99,7 @@ enum ScalarWord : int {
     kScalWords = 64,
 };
 // Words of a Gate's flags, i.e. relative to kScalFlags.  [0, kChainFlags): what the chain passes' kernels report --
-// k_chain_classify, k_gather_chain, k_pass_chain*, k_period_verdict.  Behind them, outside what a chain pass resets:
+// k_chain_classify, k_gather_chain, k_pass_chain*, k_period_judge.  Behind them, outside what a chain pass resets:
 // k_stay_by_top's "not all stays"; BLANCE_SPECULATE=fail; k_flat_stay_live's "the sweep's first pass is NOT one run of stays".
 enum ChainFlag : int {
     kFlagNotLocal = 0,        // a step is not region-local / does not fit the compact record

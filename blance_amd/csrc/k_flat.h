@@ -31,10 +31,8 @@ __device__ __forceinline__ unsigned long long sortable_key(double v) {
 }
 
 // tot[n], g[n] and the kTopList smallest (g, n) over nodesNext.  One workgroup.
-__global__ __launch_bounds__(1024) void k_flat_prepare(FlatParams q, int32_t* tot, double* g, double* top_g,
-                                                       int32_t* top_n) {
-    BLANCE_DYN_LDS(lds);
-    RedSlot* red = (RedSlot*)lds;
+__device__ __forceinline__ void flat_prepare(const FlatParams& q, int32_t* tot, double* g, double* top_g, int32_t* top_n,
+                                             RedSlot* red) {
     int round = 0;
     const int tid = threadIdx.x;
     for (int n = tid; n < q.NX; n += 1024) {
@@ -65,6 +63,12 @@ __global__ __launch_bounds__(1024) void k_flat_prepare(FlatParams q, int32_t* to
             if (tid == 0) { top_g[r] = last_s; top_n[r] = best; }
         }
     }
+}
+
+__global__ __launch_bounds__(1024) void k_flat_prepare(FlatParams q, int32_t* tot, double* g, double* top_g,
+                                                       int32_t* top_n) {
+    BLANCE_DYN_LDS(lds);
+    flat_prepare(q, tot, g, top_g, top_n, (RedSlot*)lds);
 }
 
 // steps of the pass per nodeToNodeCounts row: an upper bound of any entry of that row
@@ -209,10 +213,11 @@ __global__ void k_flat_scan(FlatParams q, int beg, int end) {
 }
 
 // The stay test of a whole pass that is expected to be one run of stays (the first pass of a sweep >= 2), on the live lists
-// themselves: no step records.  Row [0] of scan_part only, as k_flat_scan leaves it; k_flat_scan_min turns it into a
-// verdict word.  The partitions' weights and stickiness as k_gather puts them into a record.
+// themselves: no step records.  The verdict word *moved -- zeroed by open_sweep's fill, word by name -- is set to 1 by any wave that holds
+// a step that is not a certain stay: no first such step, nobody reads one on this path.  The partitions' weights and
+// stickiness as k_gather puts them into a record.
 __global__ void k_flat_stay_live(FlatParams q, DevProblem d, const int32_t* order, const int32_t* state_stickiness,
-                                 const uint8_t* state_has_stickiness) {
+                                 const uint8_t* state_has_stickiness, int32_t* moved) {
     int oi = blockIdx.x * blockDim.x + threadIdx.x;
     const bool in_range = oi < q.P;
     if (!in_range) oi = q.P - 1;                     // keep the wave whole for the ballot below
@@ -225,12 +230,13 @@ __global__ void k_flat_stay_live(FlatParams q, DevProblem d, const int32_t* orde
     const int idxT = p * d.M + q.top_state;
     const int top = (d.live_kind[idxT] != kListAbsent && d.live_len[idxT] > 0) ? d.live[(size_t)idxT * d.L] : -1;
     const bool stay = flat_certain_stay(q, FlatLiveView{&d, p}, top, stick);
-    scan_note_first(in_range && !stay, oi, q.scan_part);
+    // (in the expected case nobody stores; else one lane of every wave that holds such a step stores the same 1)
+    const unsigned long long m = __ballot(in_range && !stay);
+    if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) *moved = 1;
 }
 
 // k_flat_stay_live's row bound (k_flat_row_count) from the live lists: the steps of the pass per top priority node
-__global__ void k_flat_row_count_live(DevProblem d, int top_state, int32_t* row_count, int NX) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void flat_row_count_live(const DevProblem& d, int top_state, int32_t* row_count, int NX, int p) {
     int top = -1;
     if (p < d.P) {
         const int idxT = p * d.M + top_state;
@@ -239,6 +245,16 @@ __global__ void k_flat_row_count_live(DevProblem d, int top_state, int32_t* row_
     }
     const unsigned long long none = __ballot(p < d.P && top < 0);      // the "" row: one atomic per wave
     if (none && (int)(threadIdx.x & 63) == __ffsll((long long)none) - 1) atomicAdd(&row_count[NX], __popcll(none));
+}
+
+// What k_flat_stay_live tests against, in one launch: workgroup 0 is k_flat_prepare (it reads the counters), the others
+// count the rows, 1024 partitions each (they read the live lists) -- two jobs that share nothing, and the count ends
+// long before the one workgroup's reduction does.
+__global__ __launch_bounds__(1024) void k_flat_prepare_count_live(FlatParams q, int32_t* tot, double* g, double* top_g,
+                                                                  int32_t* top_n, DevProblem d, int32_t* row_count) {
+    BLANCE_DYN_LDS(lds);
+    if (blockIdx.x == 0) flat_prepare(q, tot, g, top_g, top_n, (RedSlot*)lds);
+    else flat_row_count_live(d, q.top_state, row_count, q.NX, (int)(blockIdx.x - 1) * 1024 + (int)threadIdx.x);
 }
 
 // commit a run of certain stays: the lists do not change; nodeToNodeCounts does (plan.go:238-245)
@@ -485,6 +501,23 @@ __global__ void k_fresh_cycle(int RS, int A, int N, const int32_t* alive_ids, co
     if (e < N) {
         const int r = alive_rank[e];
         m[e] = r < 0 ? 0 : RS / A + (r < RS % A ? 1 : 0);
+    }
+}
+
+// A plan from nothing, its opening pass (k = 1, no exclusion, step weight 1, run_flat_pass's `fresh_cycle_whole`): k_fresh_cycle,
+// k_fresh_commit_steps and k_fresh_commit_nodes in one launch and without the sequence in memory -- step j takes
+// alive_ids[j % A], node n's counter grows by its share of the R steps.  No step record is read: the pass runs ungathered.
+__global__ void k_fresh_cycle_commit(FlatParams q, int R, int A, const int32_t* alive_ids, const int32_t* alive_rank, int32_t* cnt) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < R) {
+        int* out = q.out + (size_t)e * q.OW;
+        out[0] = 1;
+        out[1] = alive_ids[e % A];
+    }
+    if (e < q.N) {
+        const int r = alive_rank[e];
+        const int m = r < 0 ? 0 : R / A + (r < R % A ? 1 : 0);
+        if (m != 0) cnt[q.s * q.NX + e] += m;        // plan.go:299-301, weight 1
     }
 }
 

@@ -37,13 +37,32 @@ __device__ __forceinline__ bool period_same_input(const int32_t* a, const int32_
     return same;
 }
 
-// grid: gx workgroups per region over its steps: T[rg] = smallest t > 0 whose record equals the first step's
-__global__ void k_period_find(int B, int gx, const int32_t* reg_off, const int32_t* crec, int32_t* pb) {
-    const int rg = blockIdx.x / gx;
+// One workgroup per region: T[rg] = smallest t > 0 (t <= kPeriodCap) whose record equals the first step's, INT_MAX if
+// none.  The workgroup looks at blockDim.x candidates per trip in rising order and stops after the first trip with a
+// match (config 3: T = 128, one trip); then it sets up the region's other words, which once took a launch of their own:
+// limit = the chain's length (k_period_verify narrows it behind the kernel boundary), not ok, no d yet.
+__global__ __launch_bounds__(1024) void k_period_find(int B, const int32_t* reg_off, const int32_t* crec, int32_t* pb) {
+    BLANCE_DYN_LDS(lds);
+    int* best = (int*)lds;
+    const int rg = blockIdx.x, tid = threadIdx.x;
     const int cbeg = reg_off[rg], len = reg_off[rg + 1] - cbeg;
-    const int t = (blockIdx.x % gx) * blockDim.x + threadIdx.x;
-    if (t < 1 || t >= len || t > kPeriodCap) return;
-    if (period_same_input(crec + (size_t)cbeg * kCW, crec + (size_t)(cbeg + t) * kCW)) atomicMin(pb + kPT * B + rg, t);
+    const int last = len - 1 < kPeriodCap ? len - 1 : kPeriodCap;       // candidates: t in [1, last]
+    if (tid == 0) *best = INT_MAX;
+    __syncthreads();
+    int found = INT_MAX;
+    for (int base = 1; base <= last && found == INT_MAX; base += (int)blockDim.x) {
+        const int t = base + tid;
+        if (t <= last && period_same_input(crec + (size_t)cbeg * kCW, crec + (size_t)(cbeg + t) * kCW)) atomicMin(best, t);
+        __syncthreads();
+        found = *best;
+        __syncthreads();                            // (everyone has read it before the next trip's matches land)
+    }
+    if (tid == 0) {
+        pb[kPT * B + rg] = found;
+        pb[kPLimit * B + rg] = len;
+        pb[kPOk * B + rg] = 0;
+        pb[kPD * B + rg] = INT_MIN;
+    }
 }
 
 // limit[rg] = first step t >= T whose record differs from step t - T's (the chain's length if none).  One thread per 16 bytes
@@ -65,28 +84,16 @@ __global__ void k_period_verify(int B, int gx, const int32_t* reg_off, const int
     if (!same) atomicMin(pb + kPLimit * B + rg, (int)t);
 }
 
-// test knob (BLANCE_PERIODIC_CUT=n): the periodic stretch ends after n steps at the latest -- any prefix of a periodic
-// stretch is one; what lies behind is walked by the chain kernel (the path a chain with a non-periodic tail takes)
-__global__ void k_period_clamp(int B, int n, int32_t* pb) {
-    const int rg = blockIdx.x * blockDim.x + threadIdx.x;
-    if (rg < B && pb[kPLimit * B + rg] > n) pb[kPLimit * B + rg] = n;
-}
-
-__global__ void k_period_init(int B, const int32_t* reg_off, int32_t* pb) {
-    const int rg = blockIdx.x * blockDim.x + threadIdx.x;
-    if (rg >= B) return;
-    pb[kPT * B + rg] = INT_MAX;
-    pb[kPLimit * B + rg] = reg_off[rg + 1] - reg_off[rg];
-    pb[kPOk * B + rg] = 0;
-    pb[kPD * B + rg] = INT_MIN;
-}
-
 // the first two segments: [0, T) and [T, 2T) of a region that joins, the whole chain and nothing of one that does not
-__global__ void k_period_segments(int B, const int32_t* reg_off, int32_t* pb) {
+// cut > 0, a test knob (BLANCE_PERIODIC_CUT=n): the periodic stretch ends after n steps at the latest -- any prefix of a
+// periodic stretch is one; what lies behind is walked by the chain kernel (the path a chain with a non-periodic tail takes)
+__global__ void k_period_segments(int B, int cut, const int32_t* reg_off, int32_t* pb) {
     const int rg = blockIdx.x * blockDim.x + threadIdx.x;
     if (rg >= B) return;
     const int cbeg = reg_off[rg], cend = reg_off[rg + 1];
-    const int T = pb[kPT * B + rg], limit = pb[kPLimit * B + rg];
+    int limit = pb[kPLimit * B + rg];
+    if (cut > 0 && limit > cut) pb[kPLimit * B + rg] = limit = cut;
+    const int T = pb[kPT * B + rg];
     const bool joins = T >= 1 && T <= kPeriodCap && (long long)limit >= (long long)kPeriodMinRounds * T;
     pb[kPOk * B + rg] = joins ? 1 : 0;
     pb[kPBeg1 * B + rg] = cbeg;
@@ -97,49 +104,68 @@ __global__ void k_period_segments(int B, const int32_t* reg_off, int32_t* pb) {
     pb[kPEnd3 * B + rg] = cend;
 }
 
-// are the counters after 2T steps those after T steps plus the same d on every live leaf?  Three small launches over
-// the leaves (gx workgroups per region over its leaves): the largest difference, every difference against it, and
-// per region the verdict with the third segment: behind `limit` if so, behind 2T if not.
-__global__ void k_period_state_max(int B, int gx, int s, int N, int NX, const int32_t* reg_lo, const int32_t* reg_hi,
-                                   const int32_t* leaf_node, const uint8_t* alive, const int32_t* cnt1, const int32_t* cnt2,
-                                   int32_t* pb) {
-    const int rg = blockIdx.x / gx;
-    if (!pb[kPOk * B + rg]) return;
-    const int pos = reg_lo[rg] + (blockIdx.x % gx) * blockDim.x + threadIdx.x;
-    if (pos >= reg_hi[rg]) return;
-    const int n = leaf_node[pos];
-    if (n < 0) return;
-    const int d = cnt2[s * NX + n] - cnt1[s * NX + n];
-    if (n < N && alive[n]) atomicMax(pb + kPD * B + rg, d);
-    else if (d != 0) atomicMin(pb + kPOk * B + rg, 0);      // (a leaf that is no candidate never moves)
-}
-
-__global__ void k_period_state_check(int B, int gx, int s, int N, int NX, const int32_t* reg_lo, const int32_t* reg_hi,
-                                     const int32_t* leaf_node, const uint8_t* alive, const int32_t* cnt1, const int32_t* cnt2,
-                                     int32_t* pb) {
-    const int rg = blockIdx.x / gx;
-    if (!pb[kPOk * B + rg]) return;
-    const int pos = reg_lo[rg] + (blockIdx.x % gx) * blockDim.x + threadIdx.x;
-    if (pos >= reg_hi[rg]) return;
-    const int n = leaf_node[pos];
-    if (n >= 0 && n < N && alive[n] && cnt2[s * NX + n] - cnt1[s * NX + n] != pb[kPD * B + rg]) atomicMin(pb + kPOk * B + rg, 0);
-}
-
-// (flags[kFlagEscaped]: a chain of the walks so far had to escape -- it published nothing, the host will redo the whole pass with
-// k_pass_chain from the saved counters: then nothing is copied either.  Without this a walk that escaped in its second
-// period left the counters where the first period had put them, "the same d = 0 on every leaf" passed for a verdict, and
-// the outputs of steps nobody had written were replicated and counted -- node ids out of whatever the buffer held.)
-__global__ void k_period_verdict(int B, const int32_t* reg_off, const int32_t* flags, int32_t* pb) {
-    const int rg = blockIdx.x * blockDim.x + threadIdx.x;
-    if (rg >= B) return;
+// One workgroup per region, behind the second walk: are the counters after 2T steps (cnt) those after T steps (cnt1) plus
+// the same d on every live leaf?  The largest difference over the region's live leaves, every difference against it, the
+// verdict with the third segment -- behind `limit` if so, behind 2T if not -- and, if so, the counters behind the copied
+// stretch: d per full period on every live leaf, and the picks of the stretch's last, partial period one by one.  Those
+// are read from `out` of steps [T, 2T), which the second walk wrote and k_period_replicate leaves alone: this kernel may
+// run before it.  Everything here belongs to the region -- its leaves' counters, its chain's outputs, its words of pb --
+// and the workgroup is the only one that touches it.  The workgroup loops over the leaves when there are more than threads.
+// (A leaf that is no candidate never moves: one that did refutes the region.  flags[kFlagEscaped]: a chain of the walks so
+// far had to escape -- it published nothing, the host will redo the whole pass with k_pass_chain from the saved counters:
+// then nothing is copied either.  Without this a walk that escaped in its second period left the counters where the first
+// period had put them, "the same d = 0 on every leaf" passed for a verdict, and the outputs of steps nobody had written
+// were replicated and counted -- node ids out of whatever the buffer held.)
+__global__ void k_period_judge(int B, int s, int N, int NX, int OW, const int32_t* reg_off, const int32_t* reg_lo,
+                               const int32_t* reg_hi, const int32_t* leaf_node, const uint8_t* alive, const int32_t* crec,
+                               const int32_t* out, const int32_t* flags, const int32_t* cnt1, int32_t* cnt, int32_t* pb) {
+    BLANCE_DYN_LDS(lds);
+    int* red = (int*)lds;                            // [0] the largest difference, [1] refuted
+    const int rg = blockIdx.x, tid = threadIdx.x;
     const int cbeg = reg_off[rg], cend = reg_off[rg + 1];
-    const int T = pb[kPT * B + rg], limit = pb[kPLimit * B + rg], d = pb[kPD * B + rg];
-    const bool joined = T >= 1 && T <= kPeriodCap && (long long)limit >= (long long)kPeriodMinRounds * T;
-    if (!joined) return;                            // (segment 1 was the whole chain, segments 2 and 3 are empty)
-    const bool ok = pb[kPOk * B + rg] != 0 && d != INT_MIN && d >= 0 && flags[kFlagEscaped] == 0;
-    pb[kPOk * B + rg] = ok ? 1 : 0;
-    pb[kPBeg3 * B + rg] = ok ? cbeg + limit : cbeg + 2 * T;
-    pb[kPEnd3 * B + rg] = cend;
+    const int T = pb[kPT * B + rg], limit = pb[kPLimit * B + rg];
+    // (k_period_segments left ok = joins; of a region that does not join segment 1 was the whole chain, 2 and 3 are empty)
+    if (!(T >= 1 && T <= kPeriodCap && (long long)limit >= (long long)kPeriodMinRounds * T)) return;
+    const int lo = reg_lo[rg], hi = reg_hi[rg];
+    if (tid == 0) { red[0] = INT_MIN; red[1] = 0; }
+    __syncthreads();
+    for (int pos = lo + tid; pos < hi; pos += (int)blockDim.x) {
+        const int n = leaf_node[pos];
+        if (n < 0) continue;
+        const int diff = cnt[s * NX + n] - cnt1[s * NX + n];
+        if (n < N && alive[n]) atomicMax(&red[0], diff);
+        else if (diff != 0) atomicOr(&red[1], 1);
+    }
+    __syncthreads();
+    const int d = red[0];
+    for (int pos = lo + tid; pos < hi; pos += (int)blockDim.x) {
+        const int n = leaf_node[pos];
+        if (n >= 0 && n < N && alive[n] && cnt[s * NX + n] - cnt1[s * NX + n] != d) atomicOr(&red[1], 1);
+    }
+    __syncthreads();
+    const bool ok = red[1] == 0 && d != INT_MIN && d >= 0 && flags[kFlagEscaped] == 0;
+    if (tid == 0) {
+        pb[kPD * B + rg] = d;
+        pb[kPOk * B + rg] = ok ? 1 : 0;
+        pb[kPBeg3 * B + rg] = ok ? cbeg + limit : cbeg + 2 * T;
+        pb[kPEnd3 * B + rg] = cend;
+    }
+    if (!ok) return;
+    const int copied = limit - 2 * T, full = copied / T, rest = copied % T;
+    for (int pos = lo + tid; pos < hi; pos += (int)blockDim.x) {
+        const int n = leaf_node[pos];
+        if (n >= 0 && n < N && alive[n]) cnt[s * NX + n] += d * full;
+    }
+    __syncthreads();
+    const int w0 = crec[(size_t)cbeg * kCW + 1];
+    for (int j = tid; j < rest; j += (int)blockDim.x) {
+        const int32_t* o = out + (size_t)(cbeg + T + j) * OW;
+        const int n_out = o[0] & 0xffff;
+        for (int c = 0; c < n_out; c++) {
+            const int n = o[1 + c];
+            if (n >= 0 && n < NX) atomicAdd(cnt + s * NX + n, w0);
+        }
+    }
 }
 
 // grid: gx workgroups per region over its steps: step t in [2T, limit) emits what step T + (t - T) % T emitted
@@ -153,33 +179,6 @@ __global__ void k_period_replicate(int B, int gx, int OW, const int32_t* reg_off
     const int32_t* src = out + (size_t)(cbeg + T + (t - T) % T) * OW;
     int32_t* dst = out + (size_t)(cbeg + t) * OW;
     for (int j = 0; j < OW; j++) dst[j] = src[j];
-}
-
-// one workgroup per region: the counters behind the copied stretch -- d per full period on every live leaf,
-// and the picks of the stretch's last, partial period one by one
-__global__ void k_period_counts(int B, int s, int N, int NX, int OW, const int32_t* reg_off, const int32_t* reg_lo,
-                                const int32_t* reg_hi, const int32_t* leaf_node, const uint8_t* alive, const int32_t* crec,
-                                const int32_t* out, const int32_t* pb, int32_t* cnt) {
-    const int rg = blockIdx.x;
-    if (!pb[kPOk * B + rg]) return;
-    const int cbeg = reg_off[rg];
-    const int T = pb[kPT * B + rg], limit = pb[kPLimit * B + rg], d = pb[kPD * B + rg];
-    const int copied = limit - 2 * T, full = copied / T, rest = copied % T;
-    const int lo = reg_lo[rg], hi = reg_hi[rg];
-    for (int pos = lo + (int)threadIdx.x; pos < hi; pos += blockDim.x) {
-        const int n = leaf_node[pos];
-        if (n >= 0 && n < N && alive[n]) cnt[s * NX + n] += d * full;
-    }
-    __syncthreads();
-    const int w0 = crec[(size_t)cbeg * kCW + 1];
-    for (int j = threadIdx.x; j < rest; j += blockDim.x) {
-        const int32_t* o = out + (size_t)(cbeg + T + j) * OW;
-        const int n_out = o[0] & 0xffff;
-        for (int c = 0; c < n_out; c++) {
-            const int n = o[1 + c];
-            if (n >= 0 && n < NX) atomicAdd(cnt + s * NX + n, w0);
-        }
-    }
 }
 
 }  // namespace blance

@@ -323,11 +323,14 @@ __global__ void k_chain_orphans(DevProblem d, int m, int top_state, const int32_
 // indices local to its region.  Steps the chain kernel cannot represent raise flags[kFlagNotLocal].
 // one step's compact record (24 words at r); returns the global leaf index of the step's top priority node (0 if it has
 // none inside a region: flags[kFlagNotLocal] is raised for such a step)
+// classify: the pass assumed its classification and did not launch k_chain_classify -- the two words of it that such a pass
+// waits for are raised here, for the same nodes: flags[kFlagEvents] for a node of state m outside the step's region,
+// flags[kFlagOrphans] when it lies in no region at all (a step without a region has neither, there as here)
 __device__ __forceinline__ int gather_chain_record(const DevProblem& d, int m, int top_state, int higher_mask, int p, int oi,
                                                     const int32_t* state_stickiness, const uint8_t* state_has_stickiness,
                                                     const int32_t* node_leaf_pos, const int32_t* node_region,
                                                     const int32_t* reg_lo, const int32_t* leaf_cls, const int32_t* cls_size,
-                                                    int flat, int32_t* r, int32_t* flags) {
+                                                    int flat, int classify, int32_t* r, int32_t* flags) {
     for (int j = 0; j < kCW; j++) r[j] = -1;
     int w = 1;
     double stick = 1.5;
@@ -358,7 +361,11 @@ __device__ __forceinline__ int gather_chain_record(const DevProblem& d, int m, i
         present = 1;
         for (int j = 0; j < d.live_len[idx]; j++) {
             int x = d.live[(size_t)idx * d.L + j];
-            if (n_all >= kChainOwn) { bad = true; break; }
+            if (classify && node_region[x] != rg) {                 // (k_chain_classify's two words: every node of the list)
+                flags[kFlagEvents] = 1;
+                if (node_region[x] < 0) flags[kFlagOrphans] = 1;
+            }
+            if (n_all >= kChainOwn) { bad = true; if (classify) continue; break; }
             own_nodes[n_all++] = x;
             if (node_region[x] != rg) { remote = 1; continue; }     // leaves by an event (or as an orphan)
             r[kCOwn + n_own++] = node_leaf_pos[x] - lo;
@@ -395,7 +402,7 @@ __global__ void k_gather_chain(DevProblem d, int m, int top_state, int higher_ma
                                const int32_t* chain_oi,
                                const int32_t* state_stickiness, const uint8_t* state_has_stickiness,
                                const int32_t* node_leaf_pos, const int32_t* node_region, const int32_t* reg_lo,
-                               const int32_t* leaf_cls, const int32_t* cls_size, int flat, int32_t* crec,
+                               const int32_t* leaf_cls, const int32_t* cls_size, int flat, int classify, int32_t* crec,
                                int32_t* flags, int32_t* topkey /* or null: global leaf of the step's top priority node */, Gate gate) {
     if (gate_closed(gate)) {
         // (the host runs the sweep again from its first pass; the second stream may already be grouping the steps by these
@@ -413,7 +420,7 @@ __global__ void k_gather_chain(DevProblem d, int m, int top_state, int higher_ma
     int32_t* r = (int32_t*)lds + tid * (kCW + 1);
     if (i < d.P) {
         const int tl = gather_chain_record(d, m, top_state, higher_mask, chain_order[i], chain_oi ? chain_oi[i] : i, state_stickiness,
-                                           state_has_stickiness, node_leaf_pos, node_region, reg_lo, leaf_cls, cls_size, flat, r, flags);
+                                           state_has_stickiness, node_leaf_pos, node_region, reg_lo, leaf_cls, cls_size, flat, classify, r, flags);
         if (topkey) topkey[i] = tl;
     }
     __syncthreads();
@@ -500,7 +507,7 @@ __global__ void k_vec_add(int n, const int32_t* a, const int32_t* b, int32_t* ou
 
 // Several small fills and one copy in ONE launch: the driver used to enqueue each as a hipMemsetAsync / hipMemcpyAsync of its
 // own (a fill kernel of the runtime per call, 25 of them per PlanNextMap at config 3).  All int32 words.
-constexpr int kFillZeros = 5;
+constexpr int kFillZeros = 6;
 struct FillCopy {
     int32_t* z[kFillZeros]; // zero z[i][0 .. zn[i])
     int32_t zn[kFillZeros];
