@@ -234,6 +234,10 @@ struct CtxHandles {
     }
 };
 
+// The fewest remaining steps a region's chain hands off by default (profiles/chain_handoff_ab.txt).  Chains shorter than
+// this plus a stage never hand off: the driver then plans the pass as before.
+constexpr int kChainHandoffMin = 8192;
+
 enum PassKind { kPassKernel = 0, kPassFlatBulk = 1, kPassBlank = 2, kPassStayTop = 3 };   // what ran a state pass (statistics)
 
 struct blance_ctx : CtxHandles {
@@ -257,6 +261,10 @@ struct blance_ctx : CtxHandles {
     int top_group_state = -1;       // top_off / top_order are those of this state's chain order ...
     int64_t top_group_epoch = -1, group_epoch = 0;   // ... as grouped at this count of regroupings
     std::vector<int64_t> last_stays; // [state] steps the last chain pass of that state committed as verified stays
+    // The chain kernel's hand-off: a region's walk ends at the first stage boundary behind a stage of stay
+    // rounds only, when at least this many steps remain; k_stay_by_top checks the rest.  0: off (BLANCE_CHAIN_HANDOFF=0|<n>).
+    int chain_handoff = kChainHandoffMin;
+    DevBuf handoff;                 // [regions] chain index of the first step a region's walk did not do
     bool no_stay_top = false;       // test knob (& 64): never k_stay_by_top
     bool force_stay_top = false;    // test knob (& 128): try k_stay_by_top in every chain pass with NumPartitions > 0
     bool periodic = true;           // an all-blank chain pass with periodic records walks two periods (k_period.h); off: & 256, or BLANCE_PERIODIC=0
@@ -553,6 +561,7 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     if (const char* pc = getenv("BLANCE_PERIODIC_CUT")) c->periodic_cut = atoi(pc);
     c->trace = getenv("BLANCE_TRACE") != nullptr;
     if (const char* cw = getenv("BLANCE_CHAIN_WAVES")) c->chain_waves = atoi(cw);
+    if (const char* ho = getenv("BLANCE_CHAIN_HANDOFF")) c->chain_handoff = atoi(ho) > 0 ? atoi(ho) : 0;   // 0: the way out; n: hand off n steps or more
     if (const char* sp = getenv("BLANCE_SPECULATE")) c->speculate = !strcmp(sp, "fail") ? 2 : atoi(sp) != 0;   // 0: every decision read back first
     if (const char* ft = getenv("BLANCE_FUSED_TAIL")) c->fused_tail = atoi(ft) != 0;      // BLANCE_FUSED_TAIL=0: the unfused tail
     if (const char* ds = getenv("BLANCE_DUMP_SWEEP")) c->dump_sweep = atoi(ds);
@@ -1250,7 +1259,7 @@ static int radix_sort_pairs(blance_ctx* c, int n, int64_t* launches, int32_t** s
     return 0;
 }
 
-static bool dispatch_chain(blance_ctx* c, ChainParams& q, int max_size);
+static bool dispatch_chain(blance_ctx* c, ChainParams& q, int max_size, const ChainHandoff& ho = ChainHandoff{nullptr, 0});
 
 // Steps [beg, end) of a flat pass on ONE wave64 (clusters of <= 256 node names): the
 // chain kernel with the whole cluster as its region and every node its own exclude
@@ -1545,9 +1554,9 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
     return 0;
 }
 
-static bool dispatch_chain(blance_ctx* c, ChainParams& q, int max_size) {
+static bool dispatch_chain(blance_ctx* c, ChainParams& q, int max_size, const ChainHandoff& ho) {
     const bool fast = q.NP == 0 && !c->any_node_weight && !c->no_fast_keys;
-    return launch_chain(c->stream, q, max_size, fast);
+    return launch_chain(c->stream, q, max_size, fast, ho);
 }
 
 // developer aid: BLANCE_DUMP_SWEEP=<i> prints every step's choice of sweep i (pass order)
@@ -1840,6 +1849,7 @@ struct PlanRun {
     // sweep's counters and kinds) -- not on a sharded plan, whose ranks scatter the pass's gathered outputs one by one.
     bool fuse = false;
     bool top_spec_plan = true;     // (no sweep of this plan has refuted it: see Sweep::top_spec_off)
+    bool handoff_plan = true;      // (no chain pass of this plan has had its hand-off refuted: ChainPass::handoff)
     int iterations = 0, converged = 0;
 };
 
@@ -1855,6 +1865,9 @@ struct PlanRun {
 enum class Pending { kNone, kStayTop, kBlank, kChain };   // whose verdict is still on the device
 struct ChainRun {
     bool allow_spec = true, defer = false, no_stay = false, no_lean = false, skip = false;
+    bool no_handoff = false;       // the chain kernel walks every region to its end (a pass that runs again always does)
+    bool handoff = false;          // the pass was launched with the hand-off: kFlagStayMoved is part of its verdict
+    bool redo_handoff = false;     // (with redo: it was the hand-off that did not hold, not the classification)
     bool redo = false;
     Pending pending = Pending::kNone;
     bool spec = false;             // the classification was assumed
@@ -1884,6 +1897,7 @@ struct ChainPass {
     int32_t cfl[kChainFlags] = {0};          // the classification's flags (all zero when they were assumed)
     int32_t n_events = 0;
     bool stay_fits = false, try_stay = false, group_stands = false, group_ahead = false;
+    bool handoff = false;                    // k_pass_chain may hand a calm region's remaining steps to k_stay_by_top
     ChainParams cq;
 
     ChainPass(blance_ctx* c_, PlanRun& pr_, const ChainPassArgs& a_, ChainRun& run_)
@@ -1921,7 +1935,16 @@ struct ChainPass {
     int group_by_top(hipStream_t st, DevBuf& sums);
     void fill_chain_params();
     int start_counters();
+    void fill_stay_params(StayParams& sq);
     int stay_attempt(bool* stayed);
+    int stay_behind_handoff();
+    int trace_handoff();
+    int longest_chain() const {
+        int mx = 0;
+        if (c->h_reg_off.size() == (size_t)B + 1)
+            for (int r = 0; r < B; r++) mx = std::max(mx, (int)(c->h_reg_off[r + 1] - c->h_reg_off[r]));
+        return mx;
+    }
     int blank_walk(bool* lean);
     int periodic_walk(bool* walked);
     int collective_a(int32_t* fl);
@@ -2001,6 +2024,7 @@ int ChainPass::events() {
         FillCopyJob fj;
         fj.zero(c->ev_off.p, (int64_t)B + 1);
         fj.zero(flags + kFlagStayMoved, 1);
+        fj.zero(flags + kFlagHandedOff, 1);
         fj.copy(c->cnt_save.p, c->cnt.p, (int64_t)cnt_words);
         if (run_fill_copy(c, fj)) return BLANCE_ERR_DEVICE;
     }
@@ -2033,9 +2057,20 @@ int ChainPass::group_by_top(hipStream_t st, DevBuf& sums) {
 int ChainPass::gather_records() {
     // A pass of stays only (the last sweep of every plan that converges)?  Worth a try when the state's pass of the
     // sweep before was one but for a few steps: k_stay_by_top checks every step in parallel.
-    stay_fits = !sharded && !c->no_stay_top && a.NP > 0 && !cfl[kFlagNotLocal] && !cfl[kFlagOrphans] && !cfl[kFlagEvents] &&
-                rr.max_size <= kStayMaxLeaves && rr.n_stay_wgs > 0;
+    const bool fits_but_np = !sharded && !c->no_stay_top && !cfl[kFlagNotLocal] && !cfl[kFlagOrphans] && !cfl[kFlagEvents] &&
+                             rr.max_size <= kStayMaxLeaves && rr.n_stay_wgs > 0;
+    stay_fits = fits_but_np && a.NP > 0;
     try_stay = stay_fits && !run.no_stay && (c->force_stay_top || c->last_stays[m] * 100 >= (int64_t)P * 99);
+    // THE HAND-OFF.  A pass that walks its chains lets k_pass_chain stop in every region that has calmed
+    // down and hands the rest to k_stay_by_top, launched right behind: when k_stay_by_top fits, nothing of the pass is being
+    // run again, no hand-off of this plan has been refuted, the stay test's rows are in LDS (else no stay round is ever
+    // tried) and some chain is long enough to have handoff_min steps left behind its first stage.
+    const bool handoff_plan_ok = c->chain_handoff > 0 && pr.handoff_plan && c->speculate > 0 && !run.no_handoff && run.allow_spec &&
+                                 longest_chain() - 64 * 4 >= c->chain_handoff;
+    handoff = stay_fits && !try_stay && handoff_plan_ok && chain_rows_in_lds(cq, rr.max_size);
+    // (... and a pass with NumPartitions == 0 -- a fresh plan's first sweep -- whose next sweep's pass will fit makes the work
+    // list for it: that pass's chain kernel is too short to hide the grouping behind)
+    const bool handoff_next = fits_but_np && a.NP == 0 && c->np_later > 0 && handoff_plan_ok && a.it + 1 < h.max_iterations;
     // k_stay_by_top's work list (the steps grouped by the leaf of their top priority node: four launches over all steps)
     // depends on the grouping by region and on the top priority nodes only.  One made for this state at the same count of
     // regroupings still holds; and a pass that does NOT try k_stay_by_top makes it for the next sweep's on the second
@@ -2044,10 +2079,12 @@ int ChainPass::gather_records() {
     // (The second stream is made when it is first wanted, and only in a process of one or two planners: a stream is a
     // hardware queue, and with many contexts planning at once on one GPU -- bench.py's replicas: 16 contexts, 32 queues -- the
     // planners' own streams end up sharing queues and their long kernels run one after the other.)
-    group_ahead = stay_fits && !try_stay && !group_stands && c->speculate > 0 && a.it + 1 < h.max_iterations &&
-                  (c->side || g_live_contexts.load() <= 2);
+    const bool for_next = stay_fits && !try_stay && c->speculate > 0 && a.it + 1 < h.max_iterations;
+    group_ahead = (for_next || handoff || handoff_next) && !group_stands && (c->side || g_live_contexts.load() <= 2);
     if (group_ahead && !c->side && hipStreamCreate(&c->side) != hipSuccess) { c->side = nullptr; group_ahead = false; (void)hipGetLastError(); }
-    if (try_stay || group_ahead) {
+    // (no second stream: a list the hand-off needs is made on this one, a list for the next sweep's k_stay_by_top alone is not)
+    const bool group_here = (handoff || handoff_next) && !group_stands && !group_ahead;
+    if (try_stay || group_ahead || handoff || group_here) {
         RESERVE(topkey, sizeof(int32_t) * ((size_t)P + 1));
         RESERVE(top_order, sizeof(int32_t) * ((size_t)P + 1));
         RESERVE(top_off, sizeof(int32_t) * ((size_t)rr.n_leaves + 2));
@@ -2057,7 +2094,7 @@ int ChainPass::gather_records() {
             c->side_pending = false;
         }
     }
-    const bool group_now = (try_stay && !group_stands) || group_ahead;
+    const bool group_now = (try_stay && !group_stands) || group_ahead || group_here;
     BLANCE_LAUNCH(k_gather_chain, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (kCW + 1) + 64, sm, d, m, h.top_state, a.higher_mask,
                          c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>(), c->state_stick.as<int32_t>(),
                          c->state_has_stick.as<uint8_t>(), c->node_leaf_pos.as<int32_t>(),
@@ -2072,6 +2109,10 @@ int ChainPass::gather_records() {
         HIPTRY(hipEventRecord(c->side_done, c->side));
         c->side_pending = true;
         if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps grouped by top priority node for the next sweep, on the second stream\n", m);
+    } else if (group_here) {
+        const int ge = group_by_top(sm, c->scan_sums);
+        if (ge) return ge;
+        if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps grouped by top priority node for the hand-off\n", m);
     }
     return 0;
 }
@@ -2112,6 +2153,61 @@ int ChainPass::start_counters() {
     return 0;
 }
 
+void ChainPass::fill_stay_params(StayParams& sq) {
+    fill_pass_common(c, sq, m, a.k, a.NP);
+    fill_region_tables(c, rr, sq);
+    sq.wg_region = rr.wg_region.as<int32_t>(); sq.wg_chunk = rr.wg_chunk.as<int32_t>();
+    sq.crec = c->crec.as<int32_t>();
+    sq.top_off = c->top_off.as<int32_t>(); sq.top_order = c->top_order.as<int32_t>();
+    sq.out = c->out.as<int32_t>(); sq.flag = flags + kFlagStayMoved;
+    sq.gate = top_gate;
+}
+
+// k_stay_by_top behind a chain kernel that handed off: every region from the step its walk stopped at.  The launch waits
+// for the chain kernel's own words as well: a chain that escaped has left its outputs unwritten, and the pass does not stand.
+int ChainPass::stay_behind_handoff() {
+    if (c->side_pending) {                             // (the work list made beside the chain kernel)
+        HIPTRY(hipStreamWaitEvent(sm, c->side_done, 0));
+        c->side_pending = false;
+    }
+    StayParams sq;
+    fill_stay_params(sq);
+    sq.gate.mask |= (1u << kFlagNotLocal) | (1u << kFlagEscaped);
+    sq.from = c->handoff.as<int32_t>();
+    sq.node_leaf_pos = c->node_leaf_pos.as<int32_t>();
+    int e;
+    if ((e = open_timing())) return e;
+    if (!launch_stay_by_top(sm, sq, rr.n_stay_wgs, rr.max_size)) return fail(BLANCE_ERR_UNSUPPORTED, "k_stay_by_top shape behind a hand-off");
+    pr.launches += 1;
+    return close_timing(kPassStayTop);
+}
+
+// BLANCE_TRACE: where every region's walk stopped
+int ChainPass::trace_handoff() {
+    std::vector<int32_t> at((size_t)B), ro((size_t)B + 1);
+    HIPTRY(hipMemcpyAsync(at.data(), c->handoff.p, sizeof(int32_t) * at.size(), hipMemcpyDeviceToHost, sm));
+    HIPTRY(hipMemcpyAsync(ro.data(), c->reg_off.p, sizeof(int32_t) * ro.size(), hipMemcpyDeviceToHost, sm));
+    HIPTRY(stream_sync(c));
+    std::string line;
+    int n = 0;
+    if (B > 0 && at[0] < 0) {
+        fprintf(stderr, "[blance] chain pass state %d: hand-off (%d steps or more): the launch returned at its gate, no region walked\n", m, c->chain_handoff);
+        return 0;
+    }
+    for (int r = 0; r < B; r++) {
+        char buf[96];
+        if (at[r] >= ro[r] && at[r] < ro[r + 1]) {
+            snprintf(buf, sizeof buf, " region %d at step %d of %d;", r, at[r] - ro[r], ro[r + 1] - ro[r]);
+            n++;
+        } else {
+            snprintf(buf, sizeof buf, " region %d walked to its end (%d);", r, ro[r + 1] - ro[r]);
+        }
+        line += buf;
+    }
+    fprintf(stderr, "[blance] chain pass state %d: hand-off (%d steps or more) in %d of %d regions:%s\n", m, c->chain_handoff, n, B, line.c_str());
+    return 0;
+}
+
 // k_stay_by_top: every step of the pass checked as a stay, one thread per top priority node.  *stayed: the pass is done
 // (or, its verdict deferred, taken to be).
 int ChainPass::stay_attempt(bool* stayed) {
@@ -2121,13 +2217,7 @@ int ChainPass::stay_attempt(bool* stayed) {
         if (ge) return ge;
     } else if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps' grouping by top priority node stands\n", m);
     StayParams sq;
-    fill_pass_common(c, sq, m, a.k, a.NP);
-    fill_region_tables(c, rr, sq);
-    sq.wg_region = rr.wg_region.as<int32_t>(); sq.wg_chunk = rr.wg_chunk.as<int32_t>();
-    sq.crec = c->crec.as<int32_t>();
-    sq.top_off = c->top_off.as<int32_t>(); sq.top_order = c->top_order.as<int32_t>();
-    sq.out = c->out.as<int32_t>(); sq.flag = flags + kFlagStayMoved;
-    sq.gate = top_gate;
+    fill_stay_params(sq);
     if (!launch_stay_by_top(sm, sq, rr.n_stay_wgs, rr.max_size)) return 0;
     pr.launches += 1;
     if (defer) {
@@ -2306,9 +2396,9 @@ int ChainPass::commit() {
 // runs the pass in order), < 0 = error.
 int ChainPass::run_once() {
     int e;
-    if ((e = classify_and_group()) || (e = events()) || (e = gather_records())) return e;
+    if ((e = classify_and_group()) || (e = events())) return e;
     fill_chain_params();
-    if ((e = start_counters()) || (e = open_timing())) return e;
+    if ((e = gather_records()) || (e = start_counters()) || (e = open_timing())) return e;
     if (try_stay) {
         bool stayed = false;
         if ((e = stay_attempt(&stayed)) || run.redo) return e;
@@ -2322,27 +2412,52 @@ int ChainPass::run_once() {
     if ((e = blank_walk(&lean)) || run.redo) return e;
     if (!lean) {
         if (a.NP > 0 && !chain_rows_in_lds(cq, rr.max_size)) NTNTRY();      // (rows in LDS: the matrix in HBM is not touched)
-        if (!dispatch_chain(c, cq, rr.max_size)) return fail(BLANCE_ERR_UNSUPPORTED, "region chain shape");
+        ChainHandoff ch{nullptr, 0};
+        if (handoff) {
+            RESERVE(handoff, sizeof(int32_t) * ((size_t)B + 1));
+            // (the trace reads the stops back: a launch that returns at its gate writes none, and says so by these -1s)
+            if (c->trace) HIPTRY(hipMemsetAsync(c->handoff.p, 0xff, sizeof(int32_t) * (size_t)B, sm));
+            ch = ChainHandoff{c->handoff.as<int32_t>(), c->chain_handoff};
+        }
+        if (!dispatch_chain(c, cq, rr.max_size, ch)) return fail(BLANCE_ERR_UNSUPPORTED, "region chain shape");
+    } else {
+        handoff = false;
     }
     pr.launches += 8;
     if ((e = close_timing(lean ? kPassBlank : kPassKernel))) return e;
-    int32_t fl[kXHead] = {0};
+    if (handoff && (e = stay_behind_handoff())) return e;
+    run.handoff = handoff;
+    if (c->trace && !lean) {
+        if (handoff) { if ((e = trace_handoff())) return e; }
+        else if (c->chain_handoff > 0) fprintf(stderr, "[blance] chain pass state %d: no hand-off\n", m);
+    }
+    int32_t fl[kXHead] = {0}, ho[2] = {0, 0};        // ho: k_stay_by_top's "not all stays" behind a hand-off, the steps it verified
     if (sharded) {
         if ((e = collective_a(fl))) return e;
     } else if (!lean) {                              // (the all-blank kernel's flags were read above: all clear)
         if (defer) {
             run.pending = Pending::kChain;
-            run.gate = gate_on((1u << kFlagNotLocal) | (1u << kFlagEscaped));
+            run.gate = gate_on((1u << kFlagNotLocal) | (1u << kFlagEscaped) | (handoff ? 1u << kFlagStayMoved : 0u));
         } else {
             HIPTRY(read_back(c, fl, flags, sizeof(int32_t) * kChainFlags));
+            if (handoff) {
+                HIPTRY(read_back(c, &ho[0], flags + kFlagStayMoved, sizeof(int32_t)));
+                HIPTRY(read_back(c, &ho[1], flags + kFlagHandedOff, sizeof(int32_t)));
+            }
         }
     }
     const bool pending = run.pending != Pending::kNone;
     if (!pending && (sharded || !lean)) HIPTRY(stream_sync(c));
     if (fl[kXPoison]) return fail(BLANCE_ERR_COMM, "another rank of the sharded plan failed");
-    if (!pending && !lean && refuted(fl)) {          // (the all-blank kernel's words were checked above)
+    // (a hand-off whose rest was not all stays: nothing of the pass stands, it runs again with every region walked to its end)
+    const bool handoff_refuted = !pending && handoff && !fl[kFlagNotLocal] && !fl[kFlagEscaped] && (ho[0] || c->speculate == 2);
+    if (!pending && !lean && (refuted(fl) || handoff_refuted)) {          // (the all-blank kernel's words were checked above)
         c->pass_ntn_ready = false;
-        pr.at.n_pass--;
+        pr.at.n_pass -= handoff ? 2 : 1;
+        if (handoff_refuted && !refuted(fl)) {
+            pr.handoff_plan = false;
+            run.redo_handoff = true;
+        }
         run.redo = true;
         return restore_counters();
     }
@@ -2350,7 +2465,7 @@ int ChainPass::run_once() {
         fprintf(stderr, "[blance] chain pass state %d: %d of %d steps committed as verified stays in %d batches\n",
                 m, fl[kFlagStaySteps], P, fl[kFlagStayBatches]);
     const bool stands = !fl[kFlagNotLocal] && !fl[kFlagEscaped];
-    c->last_stays[m] = stands ? fl[kFlagStaySteps] : 0;         // (a pending verdict: the caller fills this in)
+    c->last_stays[m] = stands ? (int64_t)fl[kFlagStaySteps] + ho[1] : 0;   // (a pending verdict: the caller fills this in)
     if (!stands) {                                  // not region-local after all: redo in order
         c->pass_ntn_ready = false;                  // (chains of big regions keep their rows in global memory: zeroed again on demand)
         return restore_counters();
@@ -2362,8 +2477,11 @@ int ChainPass::run_once() {
 static int run_chain_pass(blance_ctx* c, PlanRun& pr, const ChainPassArgs& a, ChainRun& run) {
     int e = ChainPass(c, pr, a, run).run_once();
     if (e || !run.redo) return e;
-    if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the assumed classification did not hold, the pass runs again\n", a.m);
-    run.allow_spec = false;
+    if (c->trace)
+        fprintf(stderr, run.redo_handoff ? "[blance] chain pass state %d: a step behind the hand-off moved, the pass runs again without\n" :
+                                           "[blance] chain pass state %d: the assumed classification did not hold, the pass runs again\n", a.m);
+    if (!run.redo_handoff) run.allow_spec = false;
+    run.no_handoff = true;
     run.defer = false;
     return ChainPass(c, pr, a, run).run_once();
 }
@@ -2615,7 +2733,7 @@ static int run_state_pass(blance_ctx* c, PlanRun& pr, Sweep& sw, int m) {
     for (int t = 0; t < M; t++)
         if (c->state_priority[t] < c->state_priority[m]) sp.higher_mask |= 1 << t;
     sp.r0 = c->rule_off[m]; sp.r1 = c->rule_off[m + 1];
-    while (c->pass_events.size() < 2 * (size_t)(pr.at.n_pass + 2)) {
+    while (c->pass_events.size() < 2 * (size_t)(pr.at.n_pass + 3)) {    // (a pass that hands off times two kernels)
         hipEvent_t ev;
         HIPTRY(hipEventCreate(&ev));
         c->pass_events.push_back(ev);
@@ -2719,20 +2837,27 @@ static Verdict sweep_verdict(blance_ctx* c, PlanRun& pr, Sweep& sw) {
     const Pending pending = sw.pend.pending;
     if (pending == Pending::kNone) return Verdict::kStands;
     const bool refuted = (sw.pend.spec && (f[kFlagOrphans] || f[kFlagEvents])) || f[kFlagForced];
-    const bool bad = f[kFlagNotLocal] || (pending == Pending::kStayTop ? f[kFlagStayMoved] : f[kFlagEscaped]);
+    const bool handed = sw.pend.handoff;                        // (k_stay_by_top behind the chain kernel: both verdicts count)
+    const bool bad = f[kFlagNotLocal] || (pending == Pending::kStayTop ? f[kFlagStayMoved] : f[kFlagEscaped]) || (handed && f[kFlagStayMoved]);
     if (c->trace)
         fprintf(stderr, "[blance] chain pass state %d: deferred verdict (%s): %s; %d verified stays in %d batches\n", pr.m_last,
                 pending == Pending::kStayTop ? "k_stay_by_top" : pending == Pending::kBlank ? "all-blank kernel" : "chain kernel",
                 refuted ? "assumption refuted" : bad ? "the pass did not stand" : "stands", f[kFlagStaySteps], f[kFlagStayBatches]);
     if (!refuted && !bad) {
-        if (pending == Pending::kChain) c->last_stays[pr.m_last] = f[kFlagStaySteps];
+        if (pending == Pending::kChain) c->last_stays[pr.m_last] = (int64_t)f[kFlagStaySteps] + (handed ? f[kFlagHandedOff] : 0);
         return Verdict::kStands;
     }
     // nothing behind the gate ran: the live lists and prevMap are as the pass found them; the counters are not
     sw.retry = ChainRun();
+    sw.retry.no_handoff = true;
     if (refuted) sw.retry.allow_spec = false;
     else if (pending == Pending::kStayTop) sw.retry.no_stay = true;
     else if (pending == Pending::kBlank) sw.retry.no_lean = true;
+    else if (handed && !f[kFlagNotLocal] && !f[kFlagEscaped]) {
+        // a step behind the hand-off moved: the chain kernel alone, every region to its end -- and for the rest of the plan
+        pr.handoff_plan = false;
+        if (c->trace) fprintf(stderr, "[blance] chain pass state %d: a step behind the hand-off moved, the pass runs again without\n", pr.m_last);
+    }
     else sw.retry.skip = true;                                  // (straight to the pass in order)
     if (pending != Pending::kStayTop || refuted) {              // (k_stay_by_top changes no counter)
         c->pass_ntn_ready = false;

@@ -112,6 +112,7 @@ enum ChainFlag : int {
     kFlagEvents = 7,          // nodes outside their partition's region
     kChainFlags = 8,
     kFlagStayMoved = 22, kFlagForced = 23, kFlagTopMoved = 24,
+    kFlagHandedOff = 25,      // steps k_pass_chain handed off: stays, if k_stay_by_top's verdict stands (a count, never in a Gate's mask)
 };
 constexpr int kGateWords = 32;                   // a Gate's mask has one bit per word
 static_assert(kScalErr < kScalFlags && kScalFlags + kChainFlags <= kScalSpecCount && kScalSpecCount + 2 <= kScalSortVarying &&
@@ -120,7 +121,7 @@ static_assert(kScalErr < kScalFlags && kScalFlags + kChainFlags <= kScalSpecCoun
               "the scalar words overlap");
 static_assert(kScalSpecCount % 2 == 0 && kScalSortVarying % 2 == 0 && kScalQueueStats % 2 == 0, "a 64-bit scalar word is not 8-byte aligned");
 static_assert(kFlagTopMoved < kGateWords && kChainFlags <= kGateWords, "a Gate's mask cannot name the word");
-static_assert(kScalFlags + kFlagTopMoved < kScalReadback && kScalQueueStats + 8 <= kScalReadback,
+static_assert(kScalFlags + kFlagHandedOff < kScalReadback && kFlagTopMoved < kFlagHandedOff && kScalQueueStats + 8 <= kScalReadback,
               "the per-sweep readback misses a word the host decides on");
 static_assert(kScalFlatScan >= kScalFlags + kGateWords && kScalFlatScan >= kScalReadback && kScalFlatScan + 2 <= kScalFlatBad &&
               kScalFlatBad < kScalWords, "the flat driver's words must lie outside what a Gate can address");
@@ -166,6 +167,18 @@ struct ChainParams {
     uint32_t gate;                 // k_pass_chain: words of flags[] (a Gate's mask) that, any of them set, make the launch return
 };
 
+// k_pass_chain's second parameter block (its HANDOFF instance reads it; beside ChainParams, not inside: the plain instance's
+// scalar loads of ChainParams, and with them its register use, stay what they were)
+struct ChainHandoff {
+    // The hand-off (k_pass_chain): a region whose last stage was all stay rounds, with no event left and at
+    // least handoff_min steps to go, stops at that stage boundary and stores the chain index of its first step not done;
+    // k_stay_by_top checks the rest in parallel.  A region that never stops stores its chain's end.  Null / 0: no hand-off.
+    // The steps handed off are added to flags[kFlagHandedOff] (one atomic per region; the statistics words kFlagStaySteps and
+    // kFlagStayBatches count only what the kernel itself committed).
+    int32_t* at;                   // [n_regions]
+    int32_t min;
+};
+
 // k_stay_by_top (k_stay.h): a chain pass of stays verified by one thread per top priority node
 constexpr int kStayMaxLeaves = 512;
 struct StayParams {
@@ -187,6 +200,11 @@ struct StayParams {
     int32_t* out;
     int32_t* flag;                 // set to 1 by any step that is not a certain stay
     Gate gate;                     // closed: the launch returns at once
+    // Behind a chain kernel that handed off (ChainHandoff::at): region r's steps with a chain index below from[r] are
+    // done -- they are replayed from `out` (the nodes they emitted bump the row), not tested and not written.  Null: every
+    // step is tested, from an empty row.
+    const int32_t* from;           // [n_regions]
+    const int32_t* node_leaf_pos;  // [NX] global leaf of a node (with `from`: what a replayed step emitted, as leaves)
 };
 
 

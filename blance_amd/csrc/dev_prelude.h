@@ -38,7 +38,7 @@ bool launch_pass_tree(hipStream_t stream, PassParams q, int knobs);
 bool launch_pass_queue(hipStream_t stream, PassParams q);
 size_t queue_bits_words(int NX);   // words of PassParams::ntn_bits for a cluster of NX node names
 // k_pass_chain (tu_chain.hip): one wave64 per region; false when the shape has no variant
-bool launch_chain(hipStream_t stream, ChainParams& q, int max_size, bool fast);
+bool launch_chain(hipStream_t stream, ChainParams& q, int max_size, bool fast, const ChainHandoff& ho = ChainHandoff{nullptr, 0});
 // ... whether launch_chain would keep the regions' nodeToNodeCounts rows in LDS (then the matrix in HBM is not touched)
 bool chain_rows_in_lds(const ChainParams& q, int max_size);
 // k_pass_chain_blank (tu_chain.hip): the lean first-sweep kernel

@@ -154,8 +154,11 @@ constexpr int kChainCtl = 32;                       // words of the command bloc
 template <int NPTC>
 constexpr int chain_waves_max() { return NPTC >= 8 ? 4 : kChainWaves; }
 
-template <int NPTC, int KM, bool FAST>
-__global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(ChainParams q) {
+// HANDOFF: the instance that may end a region's walk early (the hand-off, below).  It is an instance of its own so that the
+// walk of every other pass -- the plain instance -- is the code it was: the hand-off's few uniform values cost the walking wave
+// SGPR spills (77 -> 86 at <2, 2, false>), which only the passes that can gain from stopping should pay.
+template <int NPTC, int KM, bool FAST, bool HANDOFF = false>
+__global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(ChainParams q, ChainHandoff ho) {
     BLANCE_DYN_LDS(lds);
     if (q.flags[kFlagNotLocal] || gate_closed(Gate{q.flags, q.gate})) return;
     const int lane = threadIdx.x & 63;
@@ -163,6 +166,7 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
     const int rg = q.region_base + blockIdx.x;
     const int lo = q.reg_lo[rg], hi = q.reg_hi[rg], size = hi - lo;
     const int cbeg = q.reg_off[rg], cend = q.reg_off[rg + 1];
+    if (HANDOFF && ho.at && threadIdx.x == 0) ho.at[rg] = cend;                       // (until wave 0's lane 0 says otherwise, below)
     if (cbeg >= cend && !(q.ev_off && q.ev_off[rg] != q.ev_off[rg + 1])) return;   // no step, no event
     const int N = q.N, NX = q.NX, M = q.M, NP = q.NP, s = q.s, k = q.k;
     const int stage = 64 * NWv;                      // steps whose records / outputs are in LDS at a time
@@ -451,7 +455,14 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
     int ev_cur = q.ev_off ? q.ev_off[rg] : 0;
     const int ev_end = q.ev_off ? q.ev_off[rg + 1] : 0;
     int next_ev_oi = ev_cur < ev_end ? q.ev_oi[q.ev_perm[ev_cur]] : INT_MAX;
+    // THE HAND-OFF.  A stage that stay rounds alone have committed (no general step, no blank run, no event) leaves the
+    // region's counters as it found them; with no event left and the kernel not escaped, the steps behind it are a pass of
+    // stays until one of them fails the test -- and that every one of them passes it is what k_stay_by_top (k_stay.h) checks
+    // for all steps at once, on the whole chip.  The walk ends at that stage boundary when at least handoff_min steps
+    // remain: the outputs and the counters go out as at a chain's end, ho.at[rg] names the first step not done.
+    bool stage_calm = true;
     auto apply_event = [&]() {
+        if constexpr (HANDOFF) stage_calm = false;
         const int e = q.ev_perm[ev_cur];
         const int el = q.ev_leaf[e], ew = q.ev_w[e];
 #pragma unroll
@@ -489,6 +500,7 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
     };
     for (int base = cbeg; base < cend && !escaped; base += stage) {
       const int nb = cend - base < stage ? cend - base : stage;
+      if constexpr (HANDOFF) stage_calm = true;
       PH(0);
       // The stage's housekeeping rides on its first round when that round is certain to come: no event can be due (the test
       // for one reads the stage's first record), the last step was a stay.  Else it is a command of its own.
@@ -682,6 +694,7 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
                 BLANCE_WAVE_SYNC();
                 gmin_dirty = true;
                 if (r > 0) try_spec = false;          // the run's steps were moves
+                if constexpr (HANDOFF) { if (r > 0) stage_calm = false; }
                 b += r;
                 if (__ballot(range_bad)) { escaped = true; stop_range = true; break; }
                 if (b >= nb) break;
@@ -691,6 +704,7 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
         }
         // ---- general step: findBestNodes (plan.go:98-248) + commit (plan.go:290-301)
         PH(1);
+        if constexpr (HANDOFF) stage_calm = false;
         const int recw = lane < kCW ? recbuf[b * kCW + lane] : 0;
 #define REC(i) __builtin_amdgcn_readlane(recw, (i))
         const int w = REC(1);
@@ -931,6 +945,14 @@ __global__ __launch_bounds__(64 * chain_waves_max<NPTC>()) void k_pass_chain(Cha
       const int n_done = (!escaped || q.flat) ? b : 0;
       prev_base = base; prev_done = n_done;          // (written out by the four waves when the next stage starts)
       PH(19);
+      if (HANDOFF && ho.at && ho.min > 0 && stage_calm && !escaped && next_ev_oi == INT_MAX &&
+          cend - (base + nb) >= ho.min) {
+          if (lane == 0) {                           // (the thread that stored the chain's end above; uniform: everything above is)
+              ho.at[rg] = base + nb;
+              atomicAdd(&q.flags[kFlagHandedOff], cend - (base + nb));
+          }
+          break;
+      }
     }
     if (prev_done > 0) post_service(2, 0);           // the last stage's outputs
     if (lane == 0) ctl[0] = 0;                       // the helpers leave

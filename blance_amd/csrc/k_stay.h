@@ -21,6 +21,12 @@ namespace blance {
 // pass with k_pass_chain from the same (untouched) state.
 // Work list: steps grouped by the GLOBAL leaf index of their top priority node, pass order inside a
 // group (stable counting sort by the driver): top_off[leaf] .. top_off[leaf + 1] into top_order.
+// BEHIND A HAND-OFF (StayParams::from).  k_pass_chain has walked region r's steps below chain index from[r] and
+// left the counters as they are after them; the pass stands if every step from there on is a stay.  A top priority node's
+// list is in pass order, so the walked steps are a prefix of it.  They are not tested and not written: they are REPLAYED --
+// the row is bumped at the leaves of the nodes such a step emitted (read from `out`: the step may have moved), and in its
+// round the lane takes part in the rank loop with those leaves, so that the steps behind it see its bumps.  A wave whose
+// list lies wholly in the prefix has nothing to test and leaves; so does a workgroup of such waves, before it sets up.
 constexpr int kStayWaves = 4;                        // top priority nodes of one workgroup, a wave each
 constexpr int kStaySplit = 64 / kStayWaves;          // workgroups per entry of the (region, 64 leaves) work table
 
@@ -59,9 +65,18 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
     const int NX = q.NX, NP = q.NP, k = q.k;
     const int leaf0 = 64 * q.wg_chunk[wgi] + sub * kStayWaves;       // this workgroup's top priority nodes: leaves leaf0 .. leaf0 + 3 of the region
     if (leaf0 >= size) return;
+    const int from = q.from ? q.from[rg] : INT_MIN;  // steps with a chain index below it are done
     {
         const int l1 = leaf0 + kStayWaves < size ? leaf0 + kStayWaves : size;
         if (q.top_off[lo + leaf0] == q.top_off[lo + l1]) return;     // no step has one of them on top
+        if (q.from) {                                // ... or none that is still to be tested (the lists are in pass order)
+            bool any = false;
+            for (int l = leaf0; l < l1; l++) {
+                const int b = q.top_off[lo + l], e = q.top_off[lo + l + 1];
+                if (b < e && q.top_order[e - 1] >= from) any = true;
+            }
+            if (!any) return;                        // (uniform)
+        }
     }
     // region tables (as in k_pass_chain), then a row of nodeToNodeCounts per wave: what the rounds so far have emitted
     int* cntL = (int*)lds;                           // [size]
@@ -116,6 +131,7 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
     if (my_leaf >= size) return;
     const int gl = lo + my_leaf;
     const int beg = q.top_off[gl], end = q.top_off[gl + 1];
+    if (q.from && (beg >= end || q.top_order[end - 1] < from)) return;                   // nothing of mine is left to test
     int* row = rowT + wave * size;
     bool bad = false;
     // the record words the stay test reads (stick lo / hi, top leaf, counts word, top's exclude class, own leaves) of the
@@ -134,7 +150,8 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
     if (beg + lane < end) fetch(ci0);
     for (int base = beg; base < end; base += 64) {
         const int nv = end - base < 64 ? end - base : 64;                                 // steps of this round (uniform)
-        const bool valid = lane < nv;
+        const bool done = lane < nv && ci0 < from;                                          // a walked step: replayed below
+        const bool valid = lane < nv && !done;
         int cur[kW];
 #pragma unroll
         for (int e = 0; e < kW; e++) cur[e] = nx[e];
@@ -156,6 +173,24 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
             oi[j] = li;                                                                   // (-1: no such node, equal to nothing below)
             rk[j] = 0;
         }
+        if (__ballot(done)) {                                                             // (uniform; a prefix of the round's lanes)
+            // what a walked step emitted, as leaves of the region (anything else -- a pass that escaped leaves its outputs
+            // unwritten -- bumps nothing: that pass does not stand whatever is found here)
+            if (done) {
+                const int32_t* op = q.out + (size_t)ci * q.OW;
+                const int no = op[0];
+#pragma unroll
+                for (int j = 0; j < KM; j++) {
+                    int li = -1;
+                    if (j < k && j < no) {
+                        const int n = op[1 + j];
+                        if (n >= 0 && n < NX) li = q.node_leaf_pos[n] - lo;
+                        if (li < 0 || li >= size) li = -1;
+                    }
+                    oi[j] = li;
+                }
+            }
+        }
         // how many earlier steps of this round hold my nodes (the round's lanes in pass order)
         for (int e = 0; e + 1 < nv; e++) {
             const bool before = e < lane;
@@ -173,7 +208,7 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
             on[j] = -3; so[j] = 0.0; oc[j + 1] = -1;
             if (j < k) {
                 const int li = oi[j] >= 0 ? oi[j] : 0;
-                oi[j] = li;
+                if (!done) oi[j] = li;                                                    // (a replayed lane keeps its -1s: they bump nothing)
                 on[j] = nidL[li];
                 oc[j + 1] = clsL[li];
                 if (valid && !(flgL[li] & 1)) bad = true;
@@ -216,6 +251,11 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
         }
         if (__ballot(bad)) break;                                                         // (uniform: the pass does not stand)
         BLANCE_WAVE_SYNC();                                                               // (every lane has read the row of the rounds before)
+        if (done) {
+#pragma unroll
+            for (int j = 0; j < KM; j++)
+                if (j < k && oi[j] >= 0) atomicAdd(&row[oi[j]], 1);                       // plan.go:238-245, as the walk did
+        }
         if (valid) {
             int32_t* op = q.out + (size_t)ci * q.OW;
             op[0] = k;

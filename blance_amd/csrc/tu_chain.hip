@@ -6,17 +6,24 @@
 namespace blance {
 
 template <int NPTC, int KM, bool FAST>
-static void launch_chain_v(hipStream_t stream, const ChainParams& q, size_t lds, int waves) {
-    auto kern = k_pass_chain<NPTC, KM, FAST>;
+static void launch_chain_v(hipStream_t stream, const ChainParams& q, const ChainHandoff& ho, size_t lds, int waves) {
     // (the walking wave and its helpers for the stay test, k_pass_chain.h; never more than the instance's launch bounds)
     if (waves > chain_waves_max<NPTC>()) waves = chain_waves_max<NPTC>();
-    BLANCE_LAUNCH(kern, q.n_launch, 64 * waves, lds, stream, q);
+    if constexpr (!FAST) {
+        if (ho.at) {                             // (the hand-off's own instance: launch_chain refuses it with the packed keys)
+            auto kern = k_pass_chain<NPTC, KM, false, true>;
+            BLANCE_LAUNCH(kern, q.n_launch, 64 * waves, lds, stream, q, ho);
+            return;
+        }
+    }
+    auto kern = k_pass_chain<NPTC, KM, FAST>;
+    BLANCE_LAUNCH(kern, q.n_launch, 64 * waves, lds, stream, q, ho);
 }
 
 template <int NPTC, int KM>
-static void launch_chain_mode(hipStream_t stream, const ChainParams& q, size_t lds, bool fast, int waves) {
-    if (fast) launch_chain_v<NPTC, KM, true>(stream, q, lds, waves);
-    else launch_chain_v<NPTC, KM, false>(stream, q, lds, waves);
+static void launch_chain_mode(hipStream_t stream, const ChainParams& q, const ChainHandoff& ho, size_t lds, bool fast, int waves) {
+    if (fast) launch_chain_v<NPTC, KM, true>(stream, q, ho, lds, waves);
+    else launch_chain_v<NPTC, KM, false>(stream, q, ho, lds, waves);
 }
 
 // (a stage = 64 steps per wave: records and outputs; a table of top priority nodes per wave)
@@ -45,7 +52,8 @@ static int chain_waves(const ChainParams& q, int max_size) {
 }
 
 // one wave64 per region; lanes own NPTC leaves each, k <= KM picks per step
-bool launch_chain(hipStream_t stream, ChainParams& q, int max_size, bool fast) {
+bool launch_chain(hipStream_t stream, ChainParams& q, int max_size, bool fast, const ChainHandoff& ho) {
+    if (ho.at && fast) return false;             // (k_stay_by_top needs NumPartitions > 0, the packed keys have none)
     int nptc = (max_size + 63) / 64;
     size_t ntn_bytes = sizeof(int32_t) * (size_t)(max_size + 1) * (max_size + 1);
     q.ntn_in_lds = chain_rows_in_lds(q, max_size);
@@ -55,14 +63,14 @@ bool launch_chain(hipStream_t stream, ChainParams& q, int max_size, bool fast) {
     size_t lds = chain_lds_base(q, max_size, waves);
     if (q.NP > 0 && q.ntn_in_lds) lds += ntn_bytes;
     if (q.k <= 2) {
-        if (nptc <= 2) launch_chain_mode<2, 2>(stream, q, lds, fast, waves);
-        else if (nptc <= 4) launch_chain_mode<4, 2>(stream, q, lds, fast, waves);
-        else if (nptc <= 8) launch_chain_mode<8, 2>(stream, q, lds, fast, waves);
+        if (nptc <= 2) launch_chain_mode<2, 2>(stream, q, ho, lds, fast, waves);
+        else if (nptc <= 4) launch_chain_mode<4, 2>(stream, q, ho, lds, fast, waves);
+        else if (nptc <= 8) launch_chain_mode<8, 2>(stream, q, ho, lds, fast, waves);
         else return false;
     } else if (q.k <= 4) {
-        if (nptc <= 2) launch_chain_mode<2, 4>(stream, q, lds, fast, waves);
-        else if (nptc <= 4) launch_chain_mode<4, 4>(stream, q, lds, fast, waves);
-        else if (nptc <= 8) launch_chain_mode<8, 4>(stream, q, lds, fast, waves);
+        if (nptc <= 2) launch_chain_mode<2, 4>(stream, q, ho, lds, fast, waves);
+        else if (nptc <= 4) launch_chain_mode<4, 4>(stream, q, ho, lds, fast, waves);
+        else if (nptc <= 8) launch_chain_mode<8, 4>(stream, q, ho, lds, fast, waves);
         else return false;
     } else {
         return false;
