@@ -292,6 +292,12 @@ class PlanMoves(C.Structure):
                 ("out", MovesResult), ("n_moves", C.c_int64), ("n_by_kind", C.c_int64 * 4), ("n_parts_moved", C.c_int64)]
 
 
+class WireNames(C.Structure):
+    """blance_wire_names of include/blance_hip.h (blance_plan_wire_names): three byte blobs with n + 1 int64 offsets."""
+    _fields_ = [("part_bytes", C.c_void_p), ("part_off", C.c_void_p), ("node_bytes", C.c_void_p), ("node_off", C.c_void_p),
+                ("state_bytes", C.c_void_p), ("state_off", C.c_void_p)]
+
+
 # blance_plan_stats as a numpy record (pointers as addresses): Planner.plan_batch_stats fills many at once
 PLAN_STATS_ARRAYS = ("load_min", "load_max", "load_sum", "load_sumsq", "nodes_used", "unmet_slots", "rule_violations")
 PLAN_STATS_DTYPE = np.dtype({

@@ -22,6 +22,8 @@
 #include "k_flat.h"
 #include "k_period.h"
 #include "k_plan_moves.h"
+#include "k_plan_wire.h"
+#include "host/json_escape.hpp"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
 #include "tu_seq.hip"
 #include "tu_tree.hip"
@@ -294,6 +296,11 @@ struct blance_ctx : CtxHandles {
     std::vector<RbItem> rb_items;
     DevBuf vres, vseen;             // blance_upload: the device's part of the validation (k_validate_parts)
     DevBuf mv[11];                  // blance_calc_moves: inputs, per-partition slices, offsets, compacted outputs (kept between calls)
+    // blance_plan_wire_names / blance_plan_wire_get: the names of the problem the context holds in their
+    // escaped forms and document order, the byte offsets of the ranks, the document
+    bool wire_names = false;        // `wire` holds the names of the problem uploaded last
+    int wire_stage = kWireStageDefault;   // bytes of k_wire_write's LDS stage (test knob BLANCE_WIRE_STAGE lowers it)
+    DevBuf wire[10];
     int64_t comm_calls = 0, comm_bytes = 0;
     size_t comm_events_used = 0;             // (comm_events: CtxHandles)
     double comm_ms = 0.0;                    // device time between those pairs, all plans so far
@@ -565,6 +572,10 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     if (const char* sp = getenv("BLANCE_SPECULATE")) c->speculate = !strcmp(sp, "fail") ? 2 : atoi(sp) != 0;   // 0: every decision read back first
     if (const char* ft = getenv("BLANCE_FUSED_TAIL")) c->fused_tail = atoi(ft) != 0;      // BLANCE_FUSED_TAIL=0: the unfused tail
     if (const char* ds = getenv("BLANCE_DUMP_SWEEP")) c->dump_sweep = atoi(ds);
+    if (const char* ws = getenv("BLANCE_WIRE_STAGE")) {
+        const int v = atoi(ws);
+        c->wire_stage = v < kWireStageMin ? kWireStageMin : v > kWireStageMax ? kWireStageMax : v;
+    }
     if (hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
         hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreate(&c->side_go) != hipSuccess || hipEventCreate(&c->side_done) != hipSuccess) {
@@ -757,6 +768,7 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     HIPTRY(hipSetDevice(c->device));
     c->uploaded = false;
     c->planned = false;
+    c->wire_names = false;                           // (they were the names of the problem this one replaces)
     c->h = *pb;
     const int N = pb->n_nodes, NX = pb->n_nodes_ext, M = pb->n_states, P = pb->n_parts;
     const int64_t PM = (int64_t)P * M;
@@ -3341,6 +3353,186 @@ extern "C" int blance_plan_moves_get(blance_ctx* c, blance_plan_moves* mv) {
     });
 }
 
+// ---- the planned map as PartitionMap JSON bytes (blance_plan_wire_names / blance_plan_wire_get)
+namespace {
+struct WireBlob { const char* bytes; const int64_t* off; int64_t n; };
+inline int wire_cmp(const WireBlob& b, int64_t x, int64_t y) {       // bytewise, as the host encoder orders map keys
+    const size_t xn = (size_t)(b.off[x + 1] - b.off[x]), yn = (size_t)(b.off[y + 1] - b.off[y]);
+    const size_t m = xn < yn ? xn : yn;
+    const int c = m ? memcmp(b.bytes + b.off[x], b.bytes + b.off[y], m) : 0;
+    if (c) return c;
+    return xn < yn ? -1 : (xn > yn ? 1 : 0);
+}
+// the ids of a blob's strings in byte order of the strings; false: two strings are equal
+bool wire_sort(const WireBlob& b, std::vector<int32_t>& order) {
+    const int64_t n = b.n;
+    order.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) order[(size_t)i] = (int32_t)i;
+    bool sorted = true;                                  // already in key order, strictly?  (then there is no duplicate either)
+    for (int64_t i = 1; i < n && sorted; i++) sorted = wire_cmp(b, i - 1, i) < 0;
+    if (sorted) return true;
+    // by the first eight bytes as one big-endian word (a shorter string padded with zeros), the whole strings on a tie
+    struct Key { uint64_t pre; int32_t id; };
+    std::vector<Key> keys((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const size_t len = (size_t)(b.off[i + 1] - b.off[i]);
+        uint64_t pre = 0;
+        for (size_t k = 0; k < 8; k++) pre = (pre << 8) | (k < len ? (unsigned char)b.bytes[b.off[i] + (int64_t)k] : 0u);
+        keys[(size_t)i] = Key{pre, (int32_t)i};
+    }
+    std::sort(keys.begin(), keys.end(), [&](const Key& x, const Key& y) {
+        if (x.pre != y.pre) return x.pre < y.pre;
+        return wire_cmp(b, x.id, y.id) < 0;
+    });
+    for (int64_t i = 0; i < n; i++) order[(size_t)i] = keys[(size_t)i].id;
+    for (int64_t i = 1; i < n; i++)
+        if (wire_cmp(b, order[(size_t)i - 1], order[(size_t)i]) == 0) return false;
+    return true;
+}
+// the escaped forms of a blob's strings in the order `order` gives (null: as they lie), `tail` behind each, with n + 1 offsets;
+// false: 2^31 bytes or more
+bool wire_escape(const WireBlob& b, const int32_t* order, const char* tail, std::string& out, std::vector<int32_t>& off) {
+    off.assign((size_t)b.n + 1, 0);
+    for (int64_t i = 0; i < b.n; i++) {
+        const int64_t id = order ? order[(size_t)i] : i;
+        blance_json::put_string(out, b.bytes + b.off[id], (size_t)(b.off[id + 1] - b.off[id]));
+        out += tail;
+        if (out.size() > (size_t)INT32_MAX) return false;
+        off[(size_t)i + 1] = (int32_t)out.size();
+    }
+    return true;
+}
+}  // namespace
+
+static int wire_names_locked(blance_ctx* c, const blance_wire_names* nm) {
+    if (!c->uploaded) return fail(BLANCE_ERR_BAD_ARG, "no problem on the context (blance_upload or blance_plan first)");
+    const blance_problem& h = c->h;
+    const WireBlob part{nm->part_bytes, nm->part_off, h.n_parts}, node{nm->node_bytes, nm->node_off, h.n_nodes_ext},
+        state{nm->state_bytes, nm->state_off, h.n_states};
+    for (const WireBlob* b : {&part, &node, &state}) {
+        if (!b->off) return fail(BLANCE_ERR_BAD_ARG, "null offsets");
+        if (b->off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "name offsets must start at 0");
+        for (int64_t i = 0; i < b->n; i++)
+            if (b->off[i + 1] < b->off[i]) return fail(BLANCE_ERR_BAD_ARG, "name offsets not monotone");
+        if (b->off[b->n] > 0 && !b->bytes) return fail(BLANCE_ERR_BAD_ARG, "null name bytes");
+    }
+    std::vector<int32_t> order, sorder, poff, noff, soff;
+    if (!wire_sort(state, sorder)) return fail(BLANCE_ERR_BAD_ARG, "two states with one name");
+    if (!wire_sort(part, order))
+        return fail(BLANCE_ERR_UNSUPPORTED, "two partitions with one name (the reference's map would keep one of them)");
+    std::string pesc, nesc, sesc;
+    if (!wire_escape(part, order.data(), "", pesc, poff) || !wire_escape(node, nullptr, "", nesc, noff) ||
+        !wire_escape(state, sorder.data(), ":", sesc, soff))
+        return fail(BLANCE_ERR_UNSUPPORTED, "the escaped names take 2^31 bytes or more");
+    HIPTRY(hipSetDevice(c->device));
+    c->wire_names = false;                               // (the buffers are written again from here on)
+    struct Up { DevBuf& b; const void* src; size_t bytes; };
+    const Up ups[] = {{c->wire[0], order.data(), sizeof(int32_t) * order.size()}, {c->wire[1], pesc.data(), pesc.size()},
+                      {c->wire[2], poff.data(), sizeof(int32_t) * poff.size()},   {c->wire[3], nesc.data(), nesc.size()},
+                      {c->wire[4], noff.data(), sizeof(int32_t) * noff.size()},   {c->wire[5], sesc.data(), sesc.size()},
+                      {c->wire[6], soff.data(), sizeof(int32_t) * soff.size()},   {c->wire[7], sorder.data(), sizeof(int32_t) * sorder.size()}};
+    Mover up(c, true);
+    c->stage.used = 0;                                   // (the stream is idle between calls)
+    int e = 0;
+    for (const Up& u : ups) {
+        if (u.b.reserve(u.bytes + 16)) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        if ((e = up.copy(u.b.p, u.src, u.bytes))) return e;
+    }
+    if ((e = up.flush())) return e;
+    HIPTRY(stream_sync(c));                              // nothing of this frame is read after the call
+    HIPTRY(hipGetLastError());
+    c->wire_names = true;
+    return BLANCE_OK;
+}
+
+extern "C" int blance_plan_wire_names(blance_ctx* c, const blance_wire_names* nm) {
+    return guarded([&]() -> int {
+    if (!c || !nm) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    rb_discard(c);
+    return settle(c, wire_names_locked(c, nm));
+    });
+}
+
+static int plan_wire_locked(blance_ctx* c, char* buf, size_t cap, size_t* need, double* device_ms) {
+    if (!c->planned) return fail(BLANCE_ERR_BAD_ARG, "nothing planned yet");
+    if (c->stats.iterations == 0) return fail(BLANCE_ERR_BAD_ARG, "the plan made no sweep (max_iterations <= 0): there is no map to encode");
+    if (!c->wire_names) return fail(BLANCE_ERR_BAD_ARG, "no names set for the problem the context holds (blance_plan_wire_names)");
+    const bool size_only = !buf && cap == 0;
+    const blance_problem& h = c->h;
+    const int P = h.n_parts;
+    float ms = 0.f;
+    if (P == 0) {                                        // json.Marshal of an empty, non-nil map
+        *need = 2;
+        if (!size_only) {
+            if (cap < 2) return fail(BLANCE_ERR_CAPACITY, "the caller's buffer is too small (see *need)");
+            memcpy(buf, "{}", 2);
+        }
+        if (device_ms) *device_ms = 0.0;
+        return BLANCE_OK;
+    }
+    HIPTRY(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    constexpr size_t kHead = 256;                        // the 64-bit total on a cache line of its own, in front of len [P + 1]
+    DevBuf &wlen = c->wire[8], &wdoc = c->wire[9];
+    if (wlen.reserve(kHead + sizeof(int32_t) * ((size_t)P + 2))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+    const DevProblem d = result_problem(c);
+    PlanWireParams q;
+    memset(&q, 0, sizeof q);
+    q.P = P; q.M = h.n_states; q.L = d.L; q.NX = h.n_nodes_ext;
+    q.order = c->wire[0].as<int32_t>();
+    q.part_esc = c->wire[1].as<char>(); q.part_off = c->wire[2].as<int32_t>();
+    q.node_esc = c->wire[3].as<char>(); q.node_off = c->wire[4].as<int32_t>();
+    q.state_esc = c->wire[5].as<char>(); q.state_off = c->wire[6].as<int32_t>(); q.state_id = c->wire[7].as<int32_t>();
+    q.lists = d.live; q.list_len = d.live_len; q.list_kind = d.live_kind;
+    q.total = wlen.as<unsigned long long>();
+    q.len = (int32_t*)((char*)wlen.p + kHead);
+    q.stage = c->wire_stage;
+    HIPTRY(hipMemsetAsync(wlen.p, 0, kHead, sm));
+    HIPTRY(hipEventRecord(c->ev0, sm));
+    const int wgs1 = cdiv((int64_t)P + 1, 256);
+    const size_t lds1 = (((size_t)q.NX * 4 + 15) & ~(size_t)15) + sizeof(unsigned long long) * 256;
+    BLANCE_LAUNCH(k_wire_size, wgs1 < kWireMaxWgs ? wgs1 : kWireMaxWgs, 256, lds1, sm, q);
+    SCANTRY(P + 1, q.len);
+    if (size_only) HIPTRY(hipEventRecord(c->ev1, sm));
+    // the one host round trip: the total sizes the document; the scan's last offset is checked against it
+    unsigned long long total = 0;
+    int32_t scanned = 0;
+    HIPTRY(read_back(c, &total, q.total, sizeof total));
+    HIPTRY(read_back(c, &scanned, q.len + P, sizeof scanned));
+    HIPTRY(stream_sync(c));
+    HIPTRY(hipGetLastError());
+    if (total > (unsigned long long)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "a document of 2^31 bytes or more");
+    if ((unsigned long long)scanned != total) return fail(BLANCE_ERR_DEVICE, "k_wire_size: the lengths and the total disagree");
+    *need = (size_t)total;
+    if (!size_only) {
+        if (cap < (size_t)total) return fail(BLANCE_ERR_CAPACITY, "the caller's buffer is too small (see *need)");
+        if (wdoc.reserve((size_t)total + 16)) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        q.doc = wdoc.as<char>();
+        BLANCE_LAUNCH(k_wire_write, cdiv(P, kWireRun), kWireRun, (size_t)q.stage, sm, q);
+        HIPTRY(hipEventRecord(c->ev1, sm));
+        Mover down(c, false);
+        c->stage.used = 0;
+        int e = 0;
+        if ((e = down.copy(buf, wdoc.p, (size_t)total))) return e;
+        if ((e = down.finish())) return e;
+    }
+    HIPTRY(stream_sync(c));
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (device_ms) *device_ms = ms;
+    return BLANCE_OK;
+}
+
+extern "C" int blance_plan_wire_get(blance_ctx* c, char* buf, size_t cap, size_t* need, double* device_ms) {
+    return guarded([&]() -> int {
+    if (!c || !need || (!buf && cap)) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    rb_discard(c);
+    return settle(c, plan_wire_locked(c, buf, cap, need, device_ms));
+    });
+}
+
 extern "C" int blance_download(blance_ctx* c, blance_result* res) {
     return guarded([&]() -> int {
     if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
@@ -3592,6 +3784,7 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
     HIPTRY(hipSetDevice(c->device));
     c->uploaded = false;                                 // the context holds no problem after a batch
     c->planned = false;
+    c->wire_names = false;
     std::vector<BatchItem> items;
     std::vector<int> fallback;
     for (int cls : {64, 256})

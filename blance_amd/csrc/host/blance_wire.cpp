@@ -5,6 +5,7 @@
 // Reference behaviour followed: encoding/json over map[string]*Partition with the
 // struct tags of api.go:28-36 (`name`, `nodesByState`); see the header for the rules.
 #include "blance_wire.h"
+#include "json_escape.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -142,26 +143,6 @@ struct Parser {
         }
         return v;
     }
-    // length of the valid UTF-8 sequence at q (0 if invalid), Go's utf8.DecodeRune rules
-    static int utf8_len(const unsigned char* q, const unsigned char* end) {
-        unsigned char c = q[0];
-        if (c < 0x80) return 1;
-        if (c < 0xC2) return 0;
-        if (c < 0xE0) return (end - q >= 2 && (q[1] & 0xC0) == 0x80) ? 2 : 0;
-        if (c < 0xF0) {
-            if (end - q < 3 || (q[1] & 0xC0) != 0x80 || (q[2] & 0xC0) != 0x80) return 0;
-            if (c == 0xE0 && q[1] < 0xA0) return 0;
-            if (c == 0xED && q[1] > 0x9F) return 0;          // surrogates
-            return 3;
-        }
-        if (c < 0xF5) {
-            if (end - q < 4 || (q[1] & 0xC0) != 0x80 || (q[2] & 0xC0) != 0x80 || (q[3] & 0xC0) != 0x80) return 0;
-            if (c == 0xF0 && q[1] < 0x90) return 0;
-            if (c == 0xF4 && q[1] > 0x8F) return 0;
-            return 4;
-        }
-        return 0;
-    }
     // Parses a string; on return [*out, *out + *n) are its decoded bytes: a slice of the
     // input when nothing had to be rewritten (the common case), else of `scratch`.
     bool str(const char** out, size_t* n) {
@@ -219,7 +200,7 @@ struct Parser {
                 continue;
             }
             if (c < 0x80) { scratch.push_back((char)c); p++; continue; }
-            int l = utf8_len((const unsigned char*)p, (const unsigned char*)e);
+            int l = blance_json::utf8_len((const unsigned char*)p, (const unsigned char*)e);
             if (l == 0) { put_utf8(scratch, 0xFFFD); p++; }          // one bad byte -> U+FFFD
             else { scratch.append(p, (size_t)l); p += l; }
         }
@@ -548,55 +529,7 @@ struct Decoder {
 };
 
 // ---------------------------------------------------------------- encoder
-const char kHex[] = "0123456789abcdef";
-
-void put_string(std::string& o, const char* s, size_t n) {     // encodeState.string, escapeHTML = true
-    o.push_back('"');
-    size_t start = 0, i = 0;
-    const unsigned char* u = (const unsigned char*)s;
-    while (i < n) {
-        unsigned char c = u[i];
-        if (c < 0x80) {
-            if (c >= 0x20 && c != '"' && c != '\\' && c != '<' && c != '>' && c != '&') { i++; continue; }
-            o.append(s + start, i - start);
-            switch (c) {
-                case '"': o += "\\\""; break;
-                case '\\': o += "\\\\"; break;
-                case '\b': o += "\\b"; break;
-                case '\f': o += "\\f"; break;
-                case '\n': o += "\\n"; break;
-                case '\r': o += "\\r"; break;
-                case '\t': o += "\\t"; break;
-                default:
-                    o += "\\u00";
-                    o.push_back(kHex[c >> 4]);
-                    o.push_back(kHex[c & 0xF]);
-            }
-            i++;
-            start = i;
-            continue;
-        }
-        int l = Parser::utf8_len(u + i, u + n);
-        if (l == 0) {
-            o.append(s + start, i - start);
-            o += "\\ufffd";
-            i++;
-            start = i;
-            continue;
-        }
-        if (l == 3 && u[i] == 0xE2 && u[i + 1] == 0x80 && (u[i + 2] == 0xA8 || u[i + 2] == 0xA9)) {   // U+2028 / U+2029
-            o.append(s + start, i - start);
-            o += "\\u202";
-            o.push_back(kHex[u[i + 2] & 0xF]);
-            i += 3;
-            start = i;
-            continue;
-        }
-        i += (size_t)l;
-    }
-    o.append(s + start, n - start);
-    o.push_back('"');
-}
+using blance_json::put_string;      // encodeState.string, escapeHTML = true (json_escape.hpp)
 
 struct View {                                  // string i of a blob (blance_wire_encode checks the offsets first)
     const blance_wire_view* v;

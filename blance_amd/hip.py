@@ -19,7 +19,7 @@ EXPORTS = ["blance_abi_version", "blance_last_error", "blance_result_capacity", 
            "blance_plan_resident", "blance_download", "blance_calc_moves", "blance_plan_stats_get",
            "blance_comm_unique_id", "blance_comm_init_rccl", "blance_comm_set", "blance_comm_stats",
            "blance_is_emulated", "blance_host_alloc", "blance_host_free", "blance_comm_time_ms", "blance_host_trim",
-           "blance_plan_moves_capacity", "blance_plan_moves_get"]
+           "blance_plan_moves_capacity", "blance_plan_moves_get", "blance_plan_wire_names", "blance_plan_wire_get"]
 
 _libs = {}
 
@@ -102,6 +102,11 @@ def load_library(path=None):
         lib.blance_plan_moves_get.argtypes = [C.c_void_p, C.POINTER(abi.PlanMoves)]
         lib.blance_plan_moves_capacity.restype = C.c_int64
         lib.blance_plan_moves_capacity.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.PlanMoves)]
+    if hasattr(lib, "blance_plan_wire_get"):                 # likewise: Planner.set_wire_names / plan_wire refuse without them
+        lib.blance_plan_wire_names.restype = C.c_int
+        lib.blance_plan_wire_names.argtypes = [C.c_void_p, C.POINTER(abi.WireNames)]
+        lib.blance_plan_wire_get.restype = C.c_int
+        lib.blance_plan_wire_get.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
@@ -504,6 +509,58 @@ class Planner:
             return None, info
         n = info["n_moves"]
         return (out[0], out[1][:n], out[2][:n], out[3][:n]), info
+
+    def set_wire_names(self, names, node_names=None, state_names=None):
+        """blance_plan_wire_names(): the names of the problem this planner holds (after upload / plan), for plan_wire.
+        names: the problem (its part_names, node_names, state_names), or the partition names with the two other lists
+        beside them; every name a str or bytes (bytes carry invalid UTF-8).  Whatever replaces the planner's problem drops
+        the names (upload, plan, any plan_batch*); plan_resident keeps them."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_wire_names"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_wire_names (build the current sources)")
+        if node_names is None and state_names is None:
+            names, node_names, state_names = names.part_names, names.node_names, names.state_names
+        nm, keep = abi.WireNames(), []
+        for field, strs in (("part", names), ("node", node_names), ("state", state_names)):
+            raw = [x if isinstance(x, bytes) else x.encode("utf-8", "surrogatepass") for x in strs]
+            off = np.zeros(len(raw) + 1, dtype=np.int64)
+            if raw:
+                off[1:] = np.cumsum([len(x) for x in raw])
+            blob = b"".join(raw)
+            buf = C.create_string_buffer(blob, len(blob) + 1)
+            keep += [buf, off]
+            setattr(nm, field + "_bytes", C.cast(buf, C.c_void_p).value)
+            setattr(nm, field + "_off", off.ctypes.data)
+        self._check(self.lib.blance_plan_wire_names(self._h, C.byref(nm)))
+
+    def plan_wire(self, size_only=False, capacity=None, arena=None):
+        """blance_plan_wire_get(): json.Marshal(PartitionMap) of the map the last plan / plan_resident of this planner
+        produced, composed on the device -- the bytes wire.encode makes of the downloaded result.  Needs set_wire_names.
+        capacity: bytes of the output buffer (None: a size-only call first, then exactly the document's length); arena: a
+        HostArena for that buffer.  Returns (bytes, info), or (None, info) when size_only; info: need, device_ms.  A capacity
+        that is too small raises BlanceError(ERR_CAPACITY) with `need` in its `info`."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_wire_get"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_wire_get (build the current sources)")
+        need, ms = C.c_size_t(0), C.c_double(0.0)
+
+        def call(ptr, cap):
+            st = self.lib.blance_plan_wire_get(self._h, ptr, cap, C.byref(need), C.byref(ms))
+            info = {"need": int(need.value), "device_ms": float(ms.value)}
+            if st != abi.OK:
+                err = BlanceError(st, (self.lib.blance_last_error() or b"").decode())
+                err.info = info if st == abi.ERR_CAPACITY else None
+                raise err
+            return info
+
+        if size_only:
+            return None, call(None, 0)
+        if capacity is None:
+            capacity = call(None, 0)["need"]
+        new = (lambda n, dt: np.empty(n, dtype=dt)) if arena is None else arena.empty
+        out = new(max(int(capacity), 1), np.uint8)
+        info = call(out.ctypes.data, int(capacity))
+        return out[:info["need"]].tobytes(), info
 
     def calc_moves(self, n_states, favor_min_nodes, beg_off, beg_nodes, end_off, end_nodes):
         """blance_calc_moves(): CalcPartitionMoves for every partition (CSR over

@@ -313,3 +313,44 @@ def encode_arrays(keys, names, part_kind, part_off, states, nodes, entry_state, 
     v.entry_off = arr(entry_off, np.int64)
     v.entry_nodes = arr(entry_nodes, np.int32)
     return _encode_view(lib, v)
+
+
+class ResultEncoder:
+    """json.Marshal of downloaded plans of one problem, by the host encoder: the route Planner.plan_wire replaces.  The
+    name blobs are built once; encode(res) turns a FlatResult's arrays into the encoder's view with numpy (no Python loop
+    over partitions) -- key = name = the partition's name, every partition with a nodesByState map, one entry per
+    (partition, state) whose out_kind is not ABSENT -- and calls blance_wire_encode.  Names are str or bytes."""
+
+    def __init__(self, part_names, node_names, state_names, lib_path=None):
+        self.lib = load_library(lib_path)
+        self.P, self.M = len(part_names), len(state_names)
+        self._keep = []
+        v = View()
+        v.n_parts, v.n_states, v.n_nodes = self.P, self.M, len(node_names)
+        for field, strs in (("key", part_names), ("name", part_names), ("state", state_names), ("node", node_names)):
+            b, off = _blob([_b(s) for s in strs])
+            buf = C.create_string_buffer(b, len(b) + 1)
+            self._keep += [buf, off]
+            setattr(v, field + "_bytes", C.cast(buf, C.c_void_p).value)
+            setattr(v, field + "_off", off.ctypes.data)
+        self.part_kind = np.full(max(self.P, 1), LIST, dtype=np.uint8)
+        v.part_kind = self.part_kind.ctypes.data
+        self.view = v
+
+    def encode(self, res):
+        P, M = self.P, self.M
+        kind = np.asarray(res.out_kind[:P * M])
+        off = np.asarray(res.out_off[:P * M + 1], dtype=np.int64)
+        present = kind != ABSENT
+        part_off = np.zeros(P + 1, dtype=np.int64)
+        part_off[1:] = np.cumsum(present.reshape(P, M).sum(axis=1)) if P * M else 0
+        entry_state = np.ascontiguousarray(np.tile(np.arange(M, dtype=np.int32), P)[present])
+        entry_kind = np.ascontiguousarray(kind[present])
+        entry_off = np.zeros(len(entry_state) + 1, dtype=np.int64)
+        entry_off[1:] = np.cumsum(np.diff(off)[present])                # (an absent list is empty in the CSR: the node
+        entry_nodes = np.ascontiguousarray(res.out_nodes[:int(off[-1])], dtype=np.int32)   # ids are the entries', in order)
+        v = self.view
+        v.n_entries, v.n_node_refs = len(entry_state), len(entry_nodes)
+        v.part_off, v.entry_state, v.entry_kind = part_off.ctypes.data, entry_state.ctypes.data, entry_kind.ctypes.data
+        v.entry_off, v.entry_nodes = entry_off.ctypes.data, entry_nodes.ctypes.data
+        return _encode_view(self.lib, v)

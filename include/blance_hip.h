@@ -333,6 +333,38 @@ typedef struct blance_plan_moves {
 int64_t blance_plan_moves_capacity(const blance_problem* pb, const blance_plan_moves* mv);
 int blance_plan_moves_get(blance_ctx* ctx, blance_plan_moves* mv);
 
+/* ---- the map a context holds as PartitionMap JSON bytes (additive to ABI 6: look the symbols up before use) ----
+ * json.Marshal(PartitionMap) (api.go:24-36) of the map the last blance_plan / blance_plan_resident of this context
+ * produced, composed on the device from the planned lists where they lie: the bytes are exactly what
+ * the host encoder of blance_wire.h returns for the view a caller would build from blance_download -- key = name = the
+ * partition's name, every partition with a nodesByState map, one entry per (partition, state) whose out_kind is not
+ * BLANCE_LIST_ABSENT, `null` for BLANCE_LIST_NIL, the node names in list order for BLANCE_LIST_SET.
+ *
+ * blance_plan_wire_names gives the context the names of the problem it holds (after blance_upload or blance_plan; P, NX
+ * and M are that problem's n_parts, n_nodes_ext and n_states): byte blobs with n + 1 offsets, as blance_wire_view's.
+ * Everything that depends on the names alone is done here, once: every string escaped, the partitions sorted by name
+ * bytewise, the states sorted by name.  The call copies what it needs and retains nothing of the caller's.  The names stay
+ * with the context across blance_plan_resident; whatever replaces the context's problem drops them (blance_upload,
+ * blance_plan, any blance_plan_batch*).  Errors, with nothing uploaded and earlier names left as they were:
+ * BLANCE_ERR_BAD_ARG for a NULL argument, no problem on the context, offsets that do not start at 0 or are not monotone,
+ * two states with one name; BLANCE_ERR_UNSUPPORTED for two partitions with one name (the reference's rv[partition.Name],
+ * plan.go:326-329, would keep one of them) and for an escaped blob of 2^31 bytes or more. */
+typedef struct blance_wire_names {
+    const char* part_bytes;  const int64_t* part_off;   /* [P + 1]  partition names by partition id */
+    const char* node_bytes;  const int64_t* node_off;   /* [NX + 1] node names by node id */
+    const char* state_bytes; const int64_t* state_off;  /* [M + 1]  state names by state id */
+} blance_wire_names;
+int blance_plan_wire_names(blance_ctx* ctx, const blance_wire_names* names);
+/* *need = the document's length; buf receives the document when cap >= *need, else the call returns BLANCE_ERR_CAPACITY
+ * with *need written and buf untouched.  Size only: buf == NULL and cap == 0 -- the sizing pass alone runs, *need is
+ * written and nothing else is downloaded.  buf in blance_host_alloc memory is written by DMA where it lies, any other
+ * buffer through the context's staging buffer.  device_ms (may be NULL): the device's time for the kernels of the call.
+ * BLANCE_ERR_BAD_ARG, nothing launched: a NULL ctx or need, buf NULL with cap > 0, nothing planned yet or no problem on
+ * the context, a plan with iterations == 0, no names set for the problem the context holds.  BLANCE_ERR_UNSUPPORTED: a
+ * document of 2^31 bytes or more.  The call does not disturb the context (blance_download, blance_plan_stats_get,
+ * blance_plan_moves_get and blance_plan_resident behave after it as without it) and makes no collective. */
+int blance_plan_wire_get(blance_ctx* ctx, char* buf, size_t cap, size_t* need, double* device_ms);
+
 /* ---- one plan on several GPUs (BASELINE.json config 4) ------------------------------------
  * The steps of a state pass that runs as region chains (one chain per hierarchy region)
  * shard over the ranks by region: every rank holds the whole problem (upload the same problem on
