@@ -1232,6 +1232,29 @@ static int group_by_key(blance_ctx* c, hipStream_t st, DevBuf& sums, int n, cons
 static int launch_scan_excl(blance_ctx* c, int n, int32_t* data) { return launch_scan_excl_on(c, c->stream, c->scan_sums, n, data); }
 #define SCANTRY(n, data) do { int e__ = launch_scan_excl(c, (n), (data)); if (e__) return e__; } while (0)
 
+// The launch shapes of the bulk primitives below, each named once: the driver and the single-kernel cases of
+// tests/kernels/kernel_cases.inc go through the same lines.
+// pass_order's stable partition of the static order by partitionSorter category (plan.go:542-561): item i has category
+// cat[index[i]] < kCatBuckets, out[] = index[] in category order.  counts: kCatBuckets * cdiv(n, kPartChunk) words.
+constexpr int kCatBuckets = 3, kCatBits = 2;
+static int partition_by_category(blance_ctx* c, int n, const uint8_t* cat, const int32_t* index, int32_t* counts, int32_t* out) {
+    const int n_chunks = cdiv(n, kPartChunk);
+    hipStream_t sm = c->stream;
+    BLANCE_LAUNCH(k_part_count, n_chunks, 64, 64, sm, n, (const int32_t*)nullptr, cat, index, n_chunks, kCatBuckets, counts);
+    SCANTRY(kCatBuckets * n_chunks, counts);
+    BLANCE_LAUNCH(k_part_scatter, n_chunks, 64, 64, sm, n, (const int32_t*)nullptr, cat, index, index, n_chunks, kCatBuckets, kCatBits,
+                  counts, out, (int32_t*)nullptr);
+    return 0;
+}
+static void launch_sort_varbits(hipStream_t sm, int n, const unsigned long long* keys, unsigned long long* vbits) {
+    BLANCE_LAUNCH(k_sort_varbits, cdiv(n, 256 * kVarbitsPer), 256, 0, sm, n, keys, vbits);
+}
+static void launch_flat_row_count(hipStream_t sm, const FlatParams& fq, int32_t* row_count) {
+    BLANCE_LAUNCH(k_flat_row_count, cdiv(fq.P, 256), 256, 0, sm, fq, row_count);
+}
+static void launch_flat_scan_min(hipStream_t sm, int n_waves, const int32_t* part, int32_t* scan, int32_t* not_whole, int end) {
+    BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, n_waves, part, scan, not_whole, end);
+}
 
 
 // stable LSD radix sort of the n (key, value) pairs in the f_*_a buffers; *sorted_vals = the buffer the sorted
@@ -1251,7 +1274,7 @@ static int radix_sort_pairs(blance_ctx* c, int n, int64_t* launches, int32_t** s
         varying = *known_varying;
     } else {
         HIPTRY(hipMemsetAsync(vbits, 0, sizeof varying, c->stream));
-        BLANCE_LAUNCH(k_sort_varbits, cdiv(n, 256 * kVarbitsPer), 256, 0, c->stream, n, ka, vbits);
+        launch_sort_varbits(c->stream, n, ka, vbits);
         HIPTRY(read_back(c, &varying, vbits, sizeof varying));
         HIPTRY(stream_sync(c));
         *launches += 1;
@@ -1268,6 +1291,46 @@ static int radix_sort_pairs(blance_ctx* c, int n, int64_t* launches, int32_t** s
     }
     *sorted_vals = va;                               // (the loop swapped the roles after every pass)
     *other_vals = vb;
+    return 0;
+}
+
+// The first RS picks of a fresh run from step `pos` on, sorted: how many each node receives (f_m, f_moff), the (score, node)
+// elements in node-major order, the stable sort (k_flat.h "fresh identical run")
+static int fresh_run_sorted(blance_ctx* c, const FlatParams& fq, int pos, int RS, int64_t* launches, int32_t** sorted_vals,
+                            int32_t** other_vals) {
+    hipStream_t sm = c->stream;
+    BLANCE_LAUNCH(k_fresh_threshold, 1, 1024, 16384 + 64, sm, fq, pos, RS, c->f_m.as<int32_t>(),
+                  c->f_moff.as<int32_t>());
+    BLANCE_LAUNCH_NOSYNC(k_fresh_emit, cdiv(RS, 256), 256, 0, sm, fq, pos, RS, c->f_moff.as<int32_t>(),
+                         c->f_keys_a.as<unsigned long long>(), c->f_vals_a.as<int32_t>());
+    return radix_sort_pairs(c, RS, launches, sorted_vals, other_vals, nullptr);
+}
+// ... its closed form (k_fresh_cycle): the nodes of nodesNext by id, again and again
+static void fresh_cycle_sorted(blance_ctx* c, int N, int RS, int32_t** sorted_vals, int32_t** other_vals) {
+    *sorted_vals = c->f_vals_a.as<int32_t>();
+    *other_vals = c->f_vals_b.as<int32_t>();
+    BLANCE_LAUNCH_NOSYNC(k_fresh_cycle, cdiv(RS > N ? RS : N, 256), 256, 0, c->stream, RS, c->n_alive, N,
+                         c->alive_ids.as<int32_t>(), c->alive_rank.as<int32_t>(), *sorted_vals, c->f_m.as<int32_t>());
+}
+// The exclusion automaton over the R steps from `pos` (k_flat.h, above fresh_excluded): S = the exclusion-free sequence,
+// picks[k R] = what the steps take, *bad = the first step that is not exact (INT_MAX: none), read back through bad_word.
+// (threads of a few steps each: coalesced record reads; up to 64 workgroups)
+static int fresh_excl_groups(int R) {
+    const int G = cdiv(R, 4 * 1024);
+    return G < 1 ? 1 : G > 64 ? 64 : G;
+}
+static int fresh_excl_resolve(blance_ctx* c, const FlatParams& fq, int pos, int R, const int32_t* S, int32_t* picks,
+                              int32_t* bad_word, int32_t* bad) {
+    hipStream_t sm = c->stream;
+    *bad = INT_MAX;
+    HIPTRY(hipMemcpyAsync(bad_word, bad, sizeof *bad, hipMemcpyHostToDevice, sm));
+    const int G = fresh_excl_groups(R);
+    RESERVE(f_comp, (size_t)G * 1024 + 64 + 64);
+    unsigned char* comp = c->f_comp.as<unsigned char>();
+    BLANCE_LAUNCH(k_fresh_excl_scan, G, 1024, 2048 + 64, sm, fq, pos, R, S, comp, comp + (size_t)G * 1024);
+    BLANCE_LAUNCH_NOSYNC(k_fresh_excl_apply, G, 1024, 0, sm, fq, pos, R, S, comp, comp + (size_t)G * 1024, picks, bad_word);
+    HIPTRY(read_back(c, bad, bad_word, sizeof *bad));
+    HIPTRY(stream_sync(c));
     return 0;
 }
 
@@ -1430,7 +1493,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
     }
     if (q.NP > 0 && !rows_counted) {                // only read by the stay test when NP > 0; (else: k_gather has counted)
         if (rowcount_reset(c)) return BLANCE_ERR_DEVICE;
-        BLANCE_LAUNCH(k_flat_row_count, cdiv(P, 256), 256, 0, sm, fq, c->f_row_count.as<int32_t>());
+        launch_flat_row_count(sm, fq, c->f_row_count.as<int32_t>());
         *launches += 1;
     }
     // bulk paths have fixed costs (a host round trip, a sort): short runs stay sequential
@@ -1458,7 +1521,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
             if (c->scan_part.reserve(sizeof(int32_t) * 2 * ((size_t)fq.scan_waves + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
             fq.scan_part = c->scan_part.as<int32_t>();
             BLANCE_LAUNCH(k_flat_scan, scan_blocks, 256, 0, sm, fq, pos, P);
-            BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, fq.scan_waves, (const int32_t*)fq.scan_part, scan_words, (int32_t*)nullptr, P);
+            launch_flat_scan_min(sm, fq.scan_waves, fq.scan_part, scan_words, nullptr, P);
             HIPTRY(read_back(c, got, scan_words, sizeof got));
             HIPTRY(stream_sync(c));
             *launches += 1;
@@ -1498,10 +1561,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
             // nodes of nodesNext by id, again and again -- the sorted sequence and every node's share of it without
             // threshold search, emission and sort (the empty cluster's greedy plan is a round robin).
             if (known_run && fq.int_keys && c->counts_start_zero) {
-                sorted_vals = c->f_vals_a.as<int32_t>();
-                other_vals = c->f_vals_b.as<int32_t>();
-                BLANCE_LAUNCH_NOSYNC(k_fresh_cycle, cdiv(RS > q.N ? RS : q.N, 256), 256, 0, sm, RS, c->n_alive, q.N,
-                                     c->alive_ids.as<int32_t>(), c->alive_rank.as<int32_t>(), sorted_vals, c->f_m.as<int32_t>());
+                fresh_cycle_sorted(c, q.N, RS, &sorted_vals, &other_vals);
                 *launches += 1;
             } else {
                 if (dirty) {
@@ -1509,26 +1569,14 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
                     dirty = false;
                     *launches += 1;
                 }
-                BLANCE_LAUNCH(k_fresh_threshold, 1, 1024, 16384 + 64, sm, fq, pos, RS, c->f_m.as<int32_t>(),
-                              c->f_moff.as<int32_t>());
-                BLANCE_LAUNCH_NOSYNC(k_fresh_emit, cdiv(RS, 256), 256, 0, sm, fq, pos, RS, c->f_moff.as<int32_t>(),
-                                     c->f_keys_a.as<unsigned long long>(), c->f_vals_a.as<int32_t>());
-                const int e = radix_sort_pairs(c, RS, launches, &sorted_vals, &other_vals, nullptr);
+                const int e = fresh_run_sorted(c, fq, pos, RS, launches, &sorted_vals, &other_vals);
                 if (e) return e;
             }
             const int32_t* picks = sorted_vals;
             if (excl) {
                 int32_t bad = INT_MAX;
-                HIPTRY(hipMemcpyAsync(bad_word, &bad, sizeof bad, hipMemcpyHostToDevice, sm));
-                // (threads of a few steps each: coalesced record reads; up to 64 workgroups)
-                int G = cdiv(R, 4 * 1024);
-                G = G < 1 ? 1 : G > 64 ? 64 : G;
-                RESERVE(f_comp, (size_t)G * 1024 + 64 + 64);
-                unsigned char* comp = c->f_comp.as<unsigned char>();
-                BLANCE_LAUNCH(k_fresh_excl_scan, G, 1024, 2048 + 64, sm, fq, pos, R, sorted_vals, comp, comp + (size_t)G * 1024);
-                BLANCE_LAUNCH_NOSYNC(k_fresh_excl_apply, G, 1024, 0, sm, fq, pos, R, sorted_vals, comp, comp + (size_t)G * 1024, other_vals, bad_word);
-                HIPTRY(read_back(c, &bad, bad_word, sizeof bad));
-                HIPTRY(stream_sync(c));
+                const int e = fresh_excl_resolve(c, fq, pos, R, sorted_vals, other_vals, bad_word, &bad);
+                if (e) return e;
                 *launches += 1;
                 if (bad < R) R = bad;               // a pending node came up again: the run ends before that step
                 picks = other_vals;
@@ -2601,17 +2649,14 @@ static int open_sweep(blance_ctx* c, PlanRun& pr, Sweep& sw) {
 // The order of state m's pass (plan.go:542-561): the static order stably partitioned by category in sweep 1, the static
 // order itself wherever every partition has the same category.
 static int pass_order(blance_ctx* c, PlanRun& pr, const Sweep& sw, int m, const int32_t** order) {
-    const int P = c->h.n_parts, n_chunks = cdiv(P, kPartChunk);
+    const int P = c->h.n_parts;
     hipStream_t sm = c->stream;
     const bool sort_cat = sw.first && !(pr.at.passes_this_sweep == 0 ? c->uniform_first : c->uniform_all);
     if (sort_cat) {
         BLANCE_LAUNCH_NOSYNC(k_category, cdiv(P, 256), 256, 0, sm, pr.d, m, sw.any_removed, sw.add_nil, c->cat.as<uint8_t>());
-        BLANCE_LAUNCH(k_part_count, n_chunks, 64, 64, sm, P, (const int32_t*)nullptr, c->cat.as<uint8_t>(),
-                      c->part_order.as<int32_t>(), n_chunks, 3, c->chunk_counts.as<int32_t>());
-        SCANTRY(3 * n_chunks, c->chunk_counts.as<int32_t>());
-        BLANCE_LAUNCH(k_part_scatter, n_chunks, 64, 64, sm, P, (const int32_t*)nullptr, c->cat.as<uint8_t>(),
-                      c->part_order.as<int32_t>(), c->part_order.as<int32_t>(), n_chunks, 3, 2,
-                      c->chunk_counts.as<int32_t>(), c->order.as<int32_t>(), (int32_t*)nullptr);
+        const int pe = partition_by_category(c, P, c->cat.as<uint8_t>(), c->part_order.as<int32_t>(), c->chunk_counts.as<int32_t>(),
+                                             c->order.as<int32_t>());
+        if (pe) return pe;
     } else {
         // sweeps >= 2 run with nodesToRemove = nodesToAdd = [] (non-nil, plan.go:53-55): no partition's
         // nodes are in either, so every category is "1" (plan.go:542-561) and the pass order is the
