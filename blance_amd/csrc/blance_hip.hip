@@ -1255,6 +1255,26 @@ static void launch_flat_row_count(hipStream_t sm, const FlatParams& fq, int32_t*
 static void launch_flat_scan_min(hipStream_t sm, int n_waves, const int32_t* part, int32_t* scan, int32_t* not_whole, int end) {
     BLANCE_LAUNCH(k_flat_scan_min, 1, 1024, 256, sm, n_waves, part, scan, not_whole, end);
 }
+// (the launch shapes of run_flat_pass's stay side, named once: tests/kernels/kernel_cases.inc runs the same)
+static void launch_flat_prepare(hipStream_t sm, const FlatParams& fq, int32_t* tot, double* g, double* top_g, int32_t* top_n) {
+    BLANCE_LAUNCH(k_flat_prepare, 1, 1024, sizeof(RedSlot) * 32 + 64, sm, fq, tot, g, top_g, top_n);
+}
+static void launch_flat_prepare_count_live(hipStream_t sm, const FlatParams& fq, int32_t* tot, double* g, double* top_g, int32_t* top_n,
+                                           const DevProblem& d, int32_t* row_count) {
+    BLANCE_LAUNCH(k_flat_prepare_count_live, 1 + cdiv(fq.P, 1024), 1024, sizeof(RedSlot) * 32 + 64, sm, fq, tot, g, top_g, top_n, d, row_count);
+}
+static void launch_flat_stay_live(hipStream_t sm, const FlatParams& fq, const DevProblem& d, const int32_t* order,
+                                  const int32_t* state_stickiness, const uint8_t* state_has_stickiness, int32_t* moved) {
+    BLANCE_LAUNCH(k_flat_stay_live, cdiv(fq.P, 256), 256, 0, sm, fq, d, order, state_stickiness, state_has_stickiness, moved);   // (uses a wave ballot)
+}
+static int flat_scan_waves(int beg, int end) { return cdiv(end - beg, 256) * 4; }
+// (fq.scan_waves = flat_scan_waves(beg, end), fq.scan_part sized for it)
+static void launch_flat_scan(hipStream_t sm, const FlatParams& fq, int beg, int end) {
+    BLANCE_LAUNCH(k_flat_scan, cdiv(end - beg, 256), 256, 0, sm, fq, beg, end);
+}
+static void launch_flat_commit_stay(hipStream_t sm, const FlatParams& fq, int beg, int end, int bump) {
+    BLANCE_LAUNCH_NOSYNC(k_flat_commit_stay, cdiv(end - beg, 256), 256, 0, sm, fq, beg, end, bump);
+}
 
 
 // stable LSD radix sort of the n (key, value) pairs in the f_*_a buffers; *sorted_vals = the buffer the sorted
@@ -1453,8 +1473,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
     fq.int_keys = (q.NP == 0 && !c->any_node_weight) ? 1 : 0;
     // the load totals and the smallest partition-independent scores: what the scan and the fresh run's threshold test against
     auto prepare = [&]() {
-        BLANCE_LAUNCH(k_flat_prepare, 1, 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
-                      c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>());
+        launch_flat_prepare(sm, fq, c->f_tot.as<int32_t>(), c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>());
     };
     if (assume_stays) {
         // The stay test of the whole pass on the live lists (no step records: k_gather is not run), its row bound counted
@@ -1465,14 +1484,14 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
         // writes it, and nobody needs the first step that moved.
         if (q.NP > 0) {
             if (rowcount_reset(c)) return BLANCE_ERR_DEVICE;
-            BLANCE_LAUNCH(k_flat_prepare_count_live, 1 + cdiv(P, 1024), 1024, sizeof(RedSlot) * 32 + 64, sm, fq, c->f_tot.as<int32_t>(),
-                          c->f_g.as<double>(), c->f_top_g.as<double>(), c->f_top_n.as<int32_t>(), fc.d, c->f_row_count.as<int32_t>());
+            launch_flat_prepare_count_live(sm, fq, c->f_tot.as<int32_t>(), c->f_g.as<double>(), c->f_top_g.as<double>(),
+                                           c->f_top_n.as<int32_t>(), fc.d, c->f_row_count.as<int32_t>());
             if (c->trace) fprintf(stderr, "[blance] flat pass state %d: the row count rides on k_flat_prepare's launch\n", q.s);
         } else {
             prepare();
         }
-        BLANCE_LAUNCH(k_flat_stay_live, cdiv(P, 256), 256, 0, sm, fq, fc.d, fc.order, c->state_stick.as<int32_t>(),
-                      c->state_has_stick.as<uint8_t>(), scal + kScalFlags + kFlagTopMoved);   // (uses a wave ballot)
+        launch_flat_stay_live(sm, fq, fc.d, fc.order, c->state_stick.as<int32_t>(), c->state_has_stick.as<uint8_t>(),
+                              scal + kScalFlags + kFlagTopMoved);
         if (c->trace) fprintf(stderr, "[blance] flat pass state %d: k_flat_stay_live leaves the verdict word, no k_flat_scan_min\n", q.s);
         // (kernel_launches is the driver's own tally, pinned mode by mode in tests/test_driver_decisions_emulated.py; the steps
         // folded away here and in the other shortcuts still count in it.  What runs on the stream is in profiles/.)
@@ -1516,11 +1535,10 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
                 dirty = false;
                 *launches += 1;
             }
-            const int scan_blocks = cdiv(P - pos, 256);
-            fq.scan_waves = scan_blocks * 4;
+            fq.scan_waves = flat_scan_waves(pos, P);
             if (c->scan_part.reserve(sizeof(int32_t) * 2 * ((size_t)fq.scan_waves + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
             fq.scan_part = c->scan_part.as<int32_t>();
-            BLANCE_LAUNCH(k_flat_scan, scan_blocks, 256, 0, sm, fq, pos, P);
+            launch_flat_scan(sm, fq, pos, P);
             launch_flat_scan_min(sm, fq.scan_waves, fq.scan_part, scan_words, nullptr, P);
             HIPTRY(read_back(c, got, scan_words, sizeof got));
             HIPTRY(stream_sync(c));
@@ -1540,7 +1558,7 @@ static int run_flat_pass(blance_ctx* c, PassParams q, int32_t* scal, int64_t* la
                 *batched += P;
                 break;
             }
-            BLANCE_LAUNCH_NOSYNC(k_flat_commit_stay, cdiv(first_nonstay - pos, 256), 256, 0, sm, fq, pos, first_nonstay, whole ? 0 : 1);
+            launch_flat_commit_stay(sm, fq, pos, first_nonstay, whole ? 0 : 1);
             *launches += 1;
             *batched += first_nonstay - pos;
             pos = first_nonstay;

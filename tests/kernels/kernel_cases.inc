@@ -1,12 +1,13 @@
 // TEST INFRASTRUCTURE ONLY: the data-parallel building blocks of the planner, one at a time, on inputs a test makes by hand.
 // Included behind blance_hip.hip by two wrappers: tests/simt/emu_kernel_cases.cpp (the SIMT emulator, g++) and
 // tests/kernels/kernel_cases.hip (hipcc, gfx950) -- the translation unit's static host helpers and blance_ctx are visible
-// here, so an entry runs launch_scan_excl_on, group_by_key, radix_sort_pairs and the fresh-run helpers of run_flat_pass
-// themselves, with the launch shapes the driver uses.
+// here, so an entry runs launch_scan_excl_on, group_by_key, radix_sort_pairs, the fresh-run helpers of run_flat_pass and the
+// launch_flat_* helpers of its stay side themselves, with the launch shapes the driver uses.
 //
 // Conventions: plain host arrays in and out; every device buffer is sized from the entry's own arguments; whatever a kernel
 // would index with (keys < B, node ids < N, list lengths) is checked first and a bad value returns kCaseBadArg WITHOUT a
-// launch; the work runs on a fresh context's stream, which is synchronised before anything is copied back.
+// launch; the work runs on a fresh context's stream, which is synchronised before anything is copied back; outputs are
+// filled with 0x5a first and have a guard word behind them.
 // (tests/kernel_case_tables.py has the cases and the references.)
 #include <vector>
 
@@ -66,6 +67,69 @@ std::vector<int32_t> case_records(int R, int M, int w, const int32_t* excl) {
         if (excl && excl[t] >= 0) { r[kRecHead] = (kListSet << 16) | 1; r[kRecHead + 1] = excl[t]; }
     }
     return rec;
+}
+
+// The sibling for arbitrary steps: lists[P M L], len[P M], kind[P M] (kListAbsent / kListNil / kListSet), the step's weight and
+// its stickiness -- a partition's live lists as k_gather copies them into a record (unused slots -1).
+std::vector<int32_t> case_records_lists(int P, int M, int L, const int32_t* lists, const int32_t* len, const uint8_t* kind,
+                                        const int32_t* w, const double* stick) {
+    const int SW = 1 + L, RW = kRecHead + M * SW;
+    std::vector<int32_t> rec((size_t)P * RW, 0);
+    for (int i = 0; i < P; i++) {
+        int32_t* r = &rec[(size_t)i * RW];
+        r[0] = i; r[1] = w[i];
+        memcpy(&r[2], &stick[i], 8);
+        for (int t = 0; t < M; t++) {
+            const size_t idx = (size_t)i * M + t;
+            const int n = kind[idx] == kListAbsent ? 0 : len[idx];
+            int32_t* rs = r + kRecHead + t * SW;
+            rs[0] = n | ((int)kind[idx] << 16);
+            for (int j = 0; j < L; j++) rs[1 + j] = j < n ? lists[idx * L + j] : -1;
+        }
+    }
+    return rec;
+}
+// every list of the steps is something a kernel may read: a known kind, at most L nodes, node ids in [0, NX)
+bool case_lists_ok(int P, int M, int L, int NX, const int32_t* lists, const int32_t* len, const uint8_t* kind) {
+    if (!lists || !len || !kind) return false;
+    for (size_t idx = 0; idx < (size_t)P * M; idx++) {
+        if (kind[idx] > kListSet || len[idx] < 0 || len[idx] > L) return false;
+        for (int j = 0; j < len[idx]; j++) if (lists[idx * L + j] < 0 || lists[idx * L + j] >= NX) return false;
+    }
+    return true;
+}
+
+constexpr int kCaseMaxNX = 8192 + 64, kCaseMaxP = 1 << 16, kCaseMaxL = 64;
+
+// The node tables of a flat pass and what k_flat_prepare leaves for the stay test, on the device: cnt[(M + 1) NX], alive[N],
+// node_w[NX], node_has_w[NX]; tot[NX], g[NX], top_g[kTopList], top_n[kTopList] with one guard word behind each; row_count[NX + 1]
+// zeroed, one guard word behind it.
+struct FlatCase {
+    DevBuf cnt, alive, node_w, node_has_w, tot, g, top_g, top_n, row_count;
+};
+bool case_flat_args_ok(int N, int NX, int M, const int32_t* cnt, const uint8_t* alive, const int32_t* node_w, const uint8_t* node_has_w,
+                       int NP, int s) {
+    return N >= 1 && NX >= N && NX <= kCaseMaxNX && M >= 1 && M <= kMaxStates && s >= 0 && s < M && NP >= 0 && cnt && alive && node_w &&
+           node_has_w;
+}
+int case_flat_tables(FlatCase& f, FlatParams& fq, int N, int NX, int M, const int32_t* cnt, const uint8_t* alive, const int32_t* node_w,
+                     const uint8_t* node_has_w, int NP, int booster_kind, int s) {
+    CASETRY(case_up(f.cnt, cnt, (size_t)(M + 1) * NX));
+    CASETRY(case_up(f.alive, alive, (size_t)N));
+    CASETRY(case_up(f.node_w, node_w, (size_t)NX));
+    CASETRY(case_up(f.node_has_w, node_has_w, (size_t)NX));
+    CASETRY(case_up<int32_t>(f.tot, nullptr, 0, (size_t)NX + 1, 0x5a));
+    CASETRY(case_up<double>(f.g, nullptr, 0, (size_t)NX + 1, 0x5a));
+    CASETRY(case_up<double>(f.top_g, nullptr, 0, (size_t)kTopList + 1, 0x5a));
+    CASETRY(case_up<int32_t>(f.top_n, nullptr, 0, (size_t)kTopList + 1, 0x5a));
+    std::vector<int32_t> rows((size_t)NX + 2, 0);
+    rows[(size_t)NX + 1] = 0x5a5a5a5a;
+    CASETRY(case_up(f.row_count, rows.data(), rows.size()));
+    fq.N = N; fq.NX = NX; fq.M = M; fq.s = s; fq.NP = NP; fq.booster_kind = booster_kind;
+    fq.alive = f.alive.as<uint8_t>(); fq.node_weight = f.node_w.as<int32_t>(); fq.node_has_weight = f.node_has_w.as<uint8_t>();
+    fq.cnt = f.cnt.as<int32_t>(); fq.tot = f.tot.as<int32_t>(); fq.g = f.g.as<double>();
+    fq.top_g = f.top_g.as<double>(); fq.top_n = f.top_n.as<int32_t>(); fq.row_count = f.row_count.as<int32_t>();
+    return 0;
 }
 }  // namespace
 
@@ -308,6 +372,143 @@ int kcase_fresh_excl_shape(int R, int32_t* G, int32_t* per) {
     *G = fresh_excl_groups(R);
     *per = (R + *G * 1024 - 1) / (*G * 1024);
     return 0;
+}
+
+
+// k_flat_prepare alone.  Out: tot[NX + 1], g[NX + 1] and top_g[kTopList + 1] as raw 64-bit words, top_n[kTopList + 1] -- the
+// last element of each is its guard.  Nodes [N, NX) are the removed ones: they get tot and g, never a place in the top list.
+int kcase_flat_prepare(int N, int NX, int M, const int32_t* cnt, const uint8_t* alive, const int32_t* node_w, const uint8_t* node_has_w,
+                       int NP, int booster_kind, int s, int32_t* tot, unsigned long long* g, unsigned long long* top_g, int32_t* top_n) {
+    if (!case_flat_args_ok(N, NX, M, cnt, alive, node_w, node_has_w, NP, s) || !tot || !g || !top_g || !top_n) return kCaseBadArg;
+    CaseCtx cx;
+    CASETRY(cx.open());
+    blance_ctx* c = cx.c;
+    FlatCase f;
+    FlatParams fq{};
+    CASETRY(case_flat_tables(f, fq, N, NX, M, cnt, alive, node_w, node_has_w, NP, booster_kind, s));
+    launch_flat_prepare(c->stream, fq, f.tot.as<int32_t>(), f.g.as<double>(), f.top_g.as<double>(), f.top_n.as<int32_t>());
+    CASETRY(case_sync(c));
+    CASETRY(case_down(tot, f.tot.p, (size_t)NX + 1));
+    CASETRY(case_down(g, f.g.p, (size_t)NX + 1));
+    CASETRY(case_down(top_g, f.top_g.p, (size_t)kTopList + 1));
+    return case_down(top_n, f.top_n.p, (size_t)kTopList + 1);
+}
+
+// k_flat_prepare -> k_flat_scan over the steps [beg, end) -> k_flat_scan_min, as run_flat_pass's loop launches them.  The steps
+// are given as lists (case_records_lists); row_count[NX + 1] is the caller's.  Out: scan[2 + 1] and part[2 * waves + 1], the
+// last word of each its guard; part_words = 2 * waves + 1 is checked, waves as kcase_flat_scan_waves(beg, end) gives them.
+int kcase_flat_scan(int N, int NX, int M, const int32_t* cnt, const uint8_t* alive, const int32_t* node_w, const uint8_t* node_has_w,
+                    int NP, int booster_kind, int s, int P, int L, const int32_t* lists, const int32_t* len, const uint8_t* kind,
+                    const int32_t* w, const double* stick, const int32_t* row_count, int k, int top_state, int higher_mask, int beg,
+                    int end, int32_t* scan, int32_t* part, int part_words) {
+    if (!case_flat_args_ok(N, NX, M, cnt, alive, node_w, node_has_w, NP, s) || P < 1 || P > kCaseMaxP || L < 1 || L > kCaseMaxL ||
+        !w || !stick || !row_count || k < 1 || top_state < 0 || top_state >= M || beg < 0 || beg >= end || end > P || !scan || !part)
+        return kCaseBadArg;
+    if (!case_lists_ok(P, M, L, NX, lists, len, kind)) return kCaseBadArg;
+    const int waves = flat_scan_waves(beg, end);
+    if (part_words != 2 * waves + 1) return kCaseBadArg;
+    CaseCtx cx;
+    CASETRY(cx.open());
+    blance_ctx* c = cx.c;
+    FlatCase f;
+    FlatParams fq{};
+    CASETRY(case_flat_tables(f, fq, N, NX, M, cnt, alive, node_w, node_has_w, NP, booster_kind, s));
+    const std::vector<int32_t> rec = case_records_lists(P, M, L, lists, len, kind, w, stick);
+    DevBuf drec, dscan, dpart;
+    CASETRY(case_up(drec, rec.data(), rec.size()));
+    CASETRY(case_up<int32_t>(dscan, nullptr, 0, 3, 0x5a));
+    CASETRY(case_up<int32_t>(dpart, nullptr, 0, (size_t)2 * waves + 1, 0x5a));
+    HIPTRY(hipMemcpy(f.row_count.p, row_count, sizeof(int32_t) * ((size_t)NX + 1), hipMemcpyHostToDevice));
+    fq.L = L; fq.P = P; fq.k = k; fq.top_state = top_state; fq.higher_mask = higher_mask; fq.RW = kRecHead + M * (1 + L); fq.OW = 1 + k;
+    fq.rec = drec.as<int32_t>(); fq.scan = dscan.as<int32_t>(); fq.scan_part = dpart.as<int32_t>(); fq.scan_waves = waves;
+    launch_flat_prepare(c->stream, fq, f.tot.as<int32_t>(), f.g.as<double>(), f.top_g.as<double>(), f.top_n.as<int32_t>());
+    launch_flat_scan(c->stream, fq, beg, end);
+    launch_flat_scan_min(c->stream, waves, fq.scan_part, fq.scan, nullptr, end);
+    CASETRY(case_sync(c));
+    CASETRY(case_down(scan, dscan.p, 3));
+    return case_down(part, dpart.p, (size_t)2 * waves + 1);
+}
+int kcase_flat_scan_waves(int beg, int end) { return beg < 0 || beg >= end ? kCaseBadArg : flat_scan_waves(beg, end); }
+
+// The stay test of a whole pass on the live lists, as run_flat_pass launches it under assume_stays: k_flat_prepare_count_live
+// (NP > 0) or k_flat_prepare, then k_flat_stay_live.  The partitions are a hand-made DevProblem: live[P M L], live_len[P M],
+// live_kind[P M], weights_nil, part_has_weight[P], part_weight[P]; order[P] a permutation; the states' stickiness.
+// words[3]: copied in and out, the kernel's verdict word is words[1].  row_count[NX + 2]: the counted rows, the "" row, a guard.
+int kcase_flat_stay_live(int N, int NX, int M, const int32_t* cnt, const uint8_t* alive, const int32_t* node_w,
+                         const uint8_t* node_has_w, int NP, int booster_kind, int s, int P, int L, const int32_t* live,
+                         const int32_t* live_len, const uint8_t* live_kind, const int32_t* order, int weights_nil,
+                         const uint8_t* part_has_weight, const int32_t* part_weight, const int32_t* state_stick,
+                         const uint8_t* state_has_stick, int k, int top_state, int higher_mask, int32_t* words, int32_t* row_count) {
+    if (!case_flat_args_ok(N, NX, M, cnt, alive, node_w, node_has_w, NP, s) || P < 1 || P > kCaseMaxP || L < 1 || L > kCaseMaxL ||
+        !order || !part_has_weight || !part_weight || !state_stick || !state_has_stick || k < 1 || top_state < 0 || top_state >= M ||
+        !words || !row_count)
+        return kCaseBadArg;
+    if (!case_lists_ok(P, M, L, NX, live, live_len, live_kind)) return kCaseBadArg;
+    for (int i = 0; i < P; i++) if (order[i] < 0 || order[i] >= P) return kCaseBadArg;
+    CaseCtx cx;
+    CASETRY(cx.open());
+    blance_ctx* c = cx.c;
+    FlatCase f;
+    FlatParams fq{};
+    CASETRY(case_flat_tables(f, fq, N, NX, M, cnt, alive, node_w, node_has_w, NP, booster_kind, s));
+    DevBuf dlive, dlen, dkind, dorder, dphw, dpw, dss, dhs, dwords;
+    CASETRY(case_up(dlive, live, (size_t)P * M * L));
+    CASETRY(case_up(dlen, live_len, (size_t)P * M));
+    CASETRY(case_up(dkind, live_kind, (size_t)P * M));
+    CASETRY(case_up(dorder, order, (size_t)P));
+    CASETRY(case_up(dphw, part_has_weight, (size_t)P));
+    CASETRY(case_up(dpw, part_weight, (size_t)P));
+    CASETRY(case_up(dss, state_stick, (size_t)M));
+    CASETRY(case_up(dhs, state_has_stick, (size_t)M));
+    CASETRY(case_up(dwords, words, 3));
+    DevProblem d{};
+    d.N = N; d.NX = NX; d.M = M; d.L = L; d.P = P; d.weights_nil = weights_nil ? 1 : 0;
+    d.part_weight = dpw.as<int32_t>(); d.part_has_weight = dphw.as<uint8_t>();
+    d.live = dlive.as<int32_t>(); d.live_len = dlen.as<int32_t>(); d.live_kind = dkind.as<uint8_t>();
+    fq.L = L; fq.P = P; fq.k = k; fq.top_state = top_state; fq.higher_mask = higher_mask; fq.RW = kRecHead + M * (1 + L); fq.OW = 1 + k;
+    if (NP > 0)
+        launch_flat_prepare_count_live(c->stream, fq, f.tot.as<int32_t>(), f.g.as<double>(), f.top_g.as<double>(), f.top_n.as<int32_t>(), d,
+                                       f.row_count.as<int32_t>());
+    else
+        launch_flat_prepare(c->stream, fq, f.tot.as<int32_t>(), f.g.as<double>(), f.top_g.as<double>(), f.top_n.as<int32_t>());
+    launch_flat_stay_live(c->stream, fq, d, dorder.as<int32_t>(), dss.as<int32_t>(), dhs.as<uint8_t>(), dwords.as<int32_t>() + 1);
+    CASETRY(case_sync(c));
+    CASETRY(case_down(words, dwords.p, 3));
+    return case_down(row_count, f.row_count.p, (size_t)NX + 2);
+}
+
+// k_flat_commit_stay over the steps [beg, end) of P (k = 1: two output words a step).  Every step of the range holds ONE node
+// o < N in state s -- what a certain stay guarantees the kernel.  ntn[(NX + 1) N + 1]: copied in and out, the last word a guard
+// of the caller's; out[2 P + 1]: filled with the guard, then written by the kernel.
+int kcase_flat_commit_stay(int N, int NX, int M, int P, int L, const int32_t* lists, const int32_t* len, const uint8_t* kind,
+                           const int32_t* w, const double* stick, int s, int top_state, int NP, int beg, int end, int bump,
+                           int32_t* ntn, int32_t* out) {
+    if (N < 1 || NX < N || NX > kCaseMaxNX || (int64_t)(NX + 1) * N > (1 << 24) || M < 1 || M > kMaxStates || s < 0 || s >= M ||
+        top_state < 0 || top_state >= M || NP < 0 || P < 1 || P > kCaseMaxP || L < 1 || L > kCaseMaxL || !w || !stick || beg < 0 ||
+        beg >= end || end > P || !ntn || !out)
+        return kCaseBadArg;
+    if (!case_lists_ok(P, M, L, NX, lists, len, kind)) return kCaseBadArg;
+    for (int i = beg; i < end; i++) {
+        const size_t idx = (size_t)i * M + s;
+        if (kind[idx] == kListAbsent || len[idx] != 1 || lists[idx * L] >= N) return kCaseBadArg;
+    }
+    CaseCtx cx;
+    CASETRY(cx.open());
+    blance_ctx* c = cx.c;
+    const std::vector<int32_t> rec = case_records_lists(P, M, L, lists, len, kind, w, stick);
+    const size_t n_ntn = (size_t)(NX + 1) * N + 1;
+    DevBuf drec, dntn, dout;
+    CASETRY(case_up(drec, rec.data(), rec.size()));
+    CASETRY(case_up(dntn, ntn, n_ntn));
+    CASETRY(case_up<int32_t>(dout, nullptr, 0, (size_t)2 * P + 1, 0x5a));
+    FlatParams fq{};
+    fq.N = N; fq.NX = NX; fq.M = M; fq.L = L; fq.P = P; fq.s = s; fq.k = 1; fq.top_state = top_state; fq.NP = NP;
+    fq.RW = kRecHead + M * (1 + L); fq.OW = 2;
+    fq.rec = drec.as<int32_t>(); fq.ntn = dntn.as<int32_t>(); fq.out = dout.as<int32_t>();
+    launch_flat_commit_stay(c->stream, fq, beg, end, bump);
+    CASETRY(case_sync(c));
+    CASETRY(case_down(ntn, dntn.p, n_ntn));
+    return case_down(out, dout.p, (size_t)2 * P + 1);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 """The bulk primitives one kernel at a time, under the SIMT emulator: the exclusive scan, the stable counting sort (int32
 keys and the category form), the stable 64-bit radix sort, k_flat_scan_min / k_flat_row_count, the fresh-run selection and
-the exclusion automaton -- at the sizes on both sides of every tile, chunk, round, slice and workgroup seam, against plain
+the exclusion automaton -- at the sizes on both sides of every tile, chunk, round, slice and workgroup seam --, and the flat
+pass's certain-stay decision: k_flat_prepare, k_flat_scan (both predicates, every table step alone in its wave),
+k_flat_prepare_count_live + k_flat_stay_live over the same tables as live lists, k_flat_commit_stay; against plain
 references (tests/kernel_case_tables.py has the tables, the references and the checks; tests/test_kernel_cases_gpu.py
 runs the same on the device).
 
@@ -9,7 +11,8 @@ n = 0 is not a case of the scan: no call site passes it.  The driver scans P + 1
 category partition that only runs with P > 0.
 
 The exclusion table on the references alone (test_excl_table_exercises_both_outcomes): of 135 cases with exclusions, 123
-run to the end and 12 end early at a bad step."""
+run to the end and 12 end early at a bad step.  The stay and fresh tables (test_flat_tables_have_both_outcomes): every
+group has steps that pass its predicate and steps that fail it."""
 import os
 import subprocess
 
@@ -118,3 +121,49 @@ def test_excl_table_exercises_both_outcomes():
 @pytest.mark.parametrize("R", T.EXCL_R)
 def test_fresh_exclusion_automaton(kc, R):
     T.check_excl(kc, R)
+
+
+@pytest.mark.parametrize("N", T.PREPARE_N)
+def test_flat_prepare(kc, N):
+    T.check_flat_prepare(kc, N)
+
+
+@pytest.mark.parametrize("group", T.STAY_GROUPS)
+def test_flat_scan_stay_table(kc, group):
+    T.check_flat_scan_table(kc, "stay", group)
+
+
+@pytest.mark.parametrize("group", T.FRESH_GROUPS)
+def test_flat_scan_fresh_table(kc, group):
+    T.check_flat_scan_table(kc, "fresh", group)
+
+
+@pytest.mark.parametrize("P", T.FLAT_SCAN_P)
+def test_flat_scan_geometry(kc, P):
+    T.check_flat_scan_geometry(kc, P)
+
+
+@pytest.mark.parametrize("group", T.STAY_GROUPS)
+def test_flat_stay_live(kc, group):
+    T.check_flat_stay_live(kc, group)
+
+
+def test_flat_stay_live_stickiness_sources(kc):
+    T.check_flat_stay_live_stickiness(kc)
+
+
+@pytest.mark.parametrize("P", T.COMMIT_P)
+def test_flat_commit_stay(kc, P):
+    T.check_flat_commit_stay(kc, P)
+
+
+def test_flat_entries_refuse_what_a_kernel_would_index_with(kc):
+    T.check_flat_refusals(kc)
+
+
+@pytest.mark.parametrize("kind,group", [("stay", g) for g in T.STAY_GROUPS] + [("fresh", g) for g in T.FRESH_GROUPS])
+def test_flat_tables_have_both_outcomes(kind, group):
+    """On the references alone: in every group of the stay and the fresh table some listed step passes the predicate and
+    some step fails it, and every listed step is the only one of its wave that can fail (T.table_outcomes)."""
+    yes, no = T.table_outcomes(kind, group)
+    assert yes >= 1 and no >= 1

@@ -79,3 +79,41 @@ def test_fresh_cycle_is_the_general_path(kc, N, mask, RS):
 @pytest.mark.parametrize("R", T.EXCL_R)
 def test_fresh_exclusion_automaton(kc, R):
     T.check_excl(kc, R)
+
+
+@pytest.mark.parametrize("N", T.PREPARE_N)
+def test_flat_prepare(kc, N):
+    T.check_flat_prepare(kc, N)
+
+
+@pytest.mark.parametrize("group", T.STAY_GROUPS)
+def test_flat_scan_stay_table(kc, group):
+    T.check_flat_scan_table(kc, "stay", group)
+
+
+@pytest.mark.parametrize("group", T.FRESH_GROUPS)
+def test_flat_scan_fresh_table(kc, group):
+    T.check_flat_scan_table(kc, "fresh", group)
+
+
+@pytest.mark.parametrize("P", T.FLAT_SCAN_P)
+def test_flat_scan_geometry(kc, P):
+    T.check_flat_scan_geometry(kc, P)
+
+
+@pytest.mark.parametrize("group", T.STAY_GROUPS)
+def test_flat_stay_live(kc, group):
+    T.check_flat_stay_live(kc, group)
+
+
+def test_flat_stay_live_stickiness_sources(kc):
+    T.check_flat_stay_live_stickiness(kc)
+
+
+@pytest.mark.parametrize("P", T.COMMIT_P)
+def test_flat_commit_stay(kc, P):
+    T.check_flat_commit_stay(kc, P)
+
+
+def test_flat_entries_refuse_what_a_kernel_would_index_with(kc):
+    T.check_flat_refusals(kc)
