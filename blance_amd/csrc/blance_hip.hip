@@ -1119,6 +1119,17 @@ static void fill_region_tables(const blance_ctx* c, const blance_ctx::RuleRegion
     q.leaf_node = c->leaf_node.as<int32_t>(); q.leaf_cls = rr.leaf_cls.as<int32_t>(); q.cls_size = rr.cls_size.as<int32_t>();
 }
 
+// (the launch shapes of the sweep's record, list-edit and tail kernels, named once: tests/kernels/sweep_cases.inc runs the same)
+struct LaunchShape { int grid, block; size_t lds; };
+// a workgroup stages its records in LDS at a row stride of RW | 1 words
+static LaunchShape shape_gather(int P, int RW) { return {cdiv(P, 256), 256, sizeof(int32_t) * 256 * (size_t)(RW | 1) + 64}; }
+static LaunchShape shape_gather_chain(int P) { return {cdiv(P, 256), 256, sizeof(int32_t) * 256 * (kCW + 1) + 64}; }
+static LaunchShape shape_chain_classify(int P) { return {cdiv(P + 1, 256), 256, 0}; }     // (one thread more: n_ev[P])
+static LaunchShape shape_ntn_bits(int rows) { return {cdiv(rows, 4), 256, 0}; }           // (a wave64 per row)
+static LaunchShape shape_scatter(int P) { return {cdiv(P, 256), 256, 0}; }
+static LaunchShape shape_converge(int P) { return {cdiv(P, 256), 256, 0}; }
+static LaunchShape shape_sweep_tail(int P) { return {cdiv(P, 256), 256, 0}; }
+
 // f_row_count zeroed for a kernel that adds to it (k_flat_row_count, k_flat_row_count_live, k_gather)
 static int rowcount_reset(blance_ctx* c) {
     if (!c->rowcount_clean) HIPTRY(hipMemsetAsync(c->f_row_count.p, 0, sizeof(int32_t) * ((size_t)c->h.n_nodes_ext + 1), c->stream));
@@ -1177,7 +1188,8 @@ static int dispatch_pass(blance_ctx* c, const PassParams& q0) {
         q.beg = pos; q.end = q0.end;
         if (q.NP > 0 && c->bits_stale) {
             const long long words = (long long)queue_bits_words(q.NX);
-            BLANCE_LAUNCH(k_ntn_bits, cdiv(q.NX + 1, 4), 256, 0, c->stream, q.N, q.NX + 1, (int)(words / (q.NX + 1)), q.ntn, q.ntn_bits);
+            const LaunchShape bs = shape_ntn_bits(q.NX + 1);
+            BLANCE_LAUNCH(k_ntn_bits, bs.grid, bs.block, bs.lds, c->stream, q.N, q.NX + 1, (int)(words / (q.NX + 1)), q.ntn, q.ntn_bits);
             c->bits_stale = false;
         }
         if (!launch_pass_queue(c->stream, q)) { q.beg = pos; return dispatch_pass_tree_or_seq(c, q); }
@@ -1419,7 +1431,8 @@ static int flat_chain_prepare(blance_ctx* c, FlatChainPrep& fc, int64_t* launche
     int32_t* flags = c->scalars.as<int32_t>() + kScalFlags;
     HIPTRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * kChainFlags, sm));
     c->flags_clean = false;
-    BLANCE_LAUNCH(k_gather_chain, cdiv(h.n_parts, 256), 256, sizeof(int32_t) * 256 * (kCW + 1) + 64, sm, fc.d, fc.m, h.top_state, fc.higher_mask,
+    const LaunchShape gs = shape_gather_chain(h.n_parts);
+    BLANCE_LAUNCH(k_gather_chain, gs.grid, gs.block, gs.lds, sm, fc.d, fc.m, h.top_state, fc.higher_mask,
                          fc.order, (const int32_t*)nullptr, c->state_stick.as<int32_t>(),
                          c->state_has_stick.as<uint8_t>(), c->fl_iota.as<int32_t>(),
                          c->fl_zero.as<int32_t>(), c->fl_reglo.as<int32_t>(), c->fl_iota.as<int32_t>(),
@@ -2052,7 +2065,8 @@ int ChainPass::classify_and_group() {
     // same lists right behind, raises the two words itself (gather_chain_record's `classify`): no k_chain_classify.
     spec = run.allow_spec && !regroup && !sharded && c->speculate > 0;
     if (!spec) {
-        BLANCE_LAUNCH_NOSYNC(k_chain_classify, cdiv(P + 1, 256), 256, 0, sm, d, m, h.top_state,
+        const LaunchShape cs = shape_chain_classify(P);
+        BLANCE_LAUNCH_NOSYNC(k_chain_classify, cs.grid, cs.block, cs.lds, sm, d, m, h.top_state,
                              a.order, rr.node_region.as<int32_t>(), c->regid.as<int32_t>(),
                              c->n_ev.as<int32_t>(), flags, top_gate);
     } else {
@@ -2173,7 +2187,8 @@ int ChainPass::gather_records() {
         }
     }
     const bool group_now = (try_stay && !group_stands) || group_ahead || group_here;
-    BLANCE_LAUNCH(k_gather_chain, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (kCW + 1) + 64, sm, d, m, h.top_state, a.higher_mask,
+    const LaunchShape gs = shape_gather_chain(P);
+    BLANCE_LAUNCH(k_gather_chain, gs.grid, gs.block, gs.lds, sm, d, m, h.top_state, a.higher_mask,
                          c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>(), c->state_stick.as<int32_t>(),
                          c->state_has_stick.as<uint8_t>(), c->node_leaf_pos.as<int32_t>(),
                          rr.node_region.as<int32_t>(), rr.reg_lo.as<int32_t>(), rr.leaf_cls.as<int32_t>(),
@@ -2462,7 +2477,7 @@ int ChainPass::commit() {
     if (a.tail) {
         *a.tail = SweepTail{true, true, m, OW, c->chain_order.as<int32_t>(), c->chain_inv.as<int32_t>(), gate};
     } else {
-        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(), gate);
+        BLANCE_LAUNCH_NOSYNC(k_scatter, shape_scatter(P).grid, shape_scatter(P).block, shape_scatter(P).lds, sm, d, m, OW, c->chain_order.as<int32_t>(), c->out.as<int32_t>(), gate);
         pr.launches++;
     }
     pr.at.batched += P;
@@ -2713,8 +2728,9 @@ static int run_pass_in_order(blance_ctx* c, PlanRun& pr, Sweep& sw, const StateP
                          (sw.known_passes == 0 || (sw.known_passes == 1 && sw.known_k == 1 && sw.NP == 0 && ((sp.higher_mask >> sw.known_state) & 1)));
     const bool ungathered = assume_stays || fresh_cycle_whole(c, opening, sw.NP, k, sp.higher_mask);   // (no step record is read)
     if (count_rows && !assume_stays && rowcount_reset(c)) return BLANCE_ERR_DEVICE;
+    const LaunchShape gs = shape_gather(P, RW);
     if (!ungathered)
-        BLANCE_LAUNCH(k_gather, cdiv(P, 256), 256, sizeof(int32_t) * 256 * (RW | 1) + 64, sm, d, m, h.top_state, RW, sp.order,
+        BLANCE_LAUNCH(k_gather, gs.grid, gs.block, gs.lds, sm, d, m, h.top_state, RW, sp.order,
                              c->state_stick.as<int32_t>(), c->state_has_stick.as<uint8_t>(), c->rec.as<int32_t>(),
                              count_rows ? c->f_row_count.as<int32_t>() : (int32_t*)nullptr, NX);
     PassParams q;
@@ -2784,7 +2800,7 @@ static int run_pass_in_order(blance_ctx* c, PlanRun& pr, Sweep& sw, const StateP
     if (pr.fuse && m == pr.m_last)
         sw.tail = SweepTail{true, !nothing_to_apply, m, q.OW, sp.order, nullptr, kNoGate};
     else if (!nothing_to_apply)
-        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, m, q.OW, sp.order, c->out.as<int32_t>(), kNoGate);
+        BLANCE_LAUNCH_NOSYNC(k_scatter, shape_scatter(P).grid, shape_scatter(P).block, shape_scatter(P).lds, sm, d, m, q.OW, sp.order, c->out.as<int32_t>(), kNoGate);
     return 0;
 }
 
@@ -2859,7 +2875,7 @@ static int close_sweep(blance_ctx* c, PlanRun& pr, Sweep& sw) {
     if (tail.set && tail.scatter && (!tail.inv || tail.gate.flags != cg.flags || tail.gate.mask != cg.mask)) {
         // (no inverse of the pass order -- a flat pass --, or the list edits wait for other words than the convergence
         // test: on their own, as before)
-        BLANCE_LAUNCH_NOSYNC(k_scatter, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.order, c->out.as<int32_t>(), tail.gate);
+        BLANCE_LAUNCH_NOSYNC(k_scatter, shape_scatter(P).grid, shape_scatter(P).block, shape_scatter(P).lds, sm, d, tail.m, tail.OW, tail.order, c->out.as<int32_t>(), tail.gate);
         pr.launches++;
         tail.scatter = false;
     }
@@ -2867,11 +2883,12 @@ static int close_sweep(blance_ctx* c, PlanRun& pr, Sweep& sw) {
         // the sweep's tail: the list edits, the convergence test and write-back, and -- when another sweep may follow --
         // that sweep's counters and kinds, in one pass over the partitions
         int32_t* next = sw.it + 1 < h.max_iterations ? c->cnt_next.as<int32_t>() : nullptr;
-        BLANCE_LAUNCH(k_sweep_tail, cdiv(P, 256), 256, 0, sm, d, tail.m, tail.OW, tail.scatter ? tail.inv : nullptr,
+        const LaunchShape ts = shape_sweep_tail(P);
+        BLANCE_LAUNCH(k_sweep_tail, ts.grid, ts.block, ts.lds, sm, d, tail.m, tail.OW, tail.scatter ? tail.inv : nullptr,
                       tail.scatter ? c->out.as<int32_t>() : nullptr, scal + kScalNotMatch, next, cg);   // (uses a wave ballot)
         sw.tail_counts = next != nullptr;
     } else {
-        BLANCE_LAUNCH(k_converge, cdiv(P, 256), 256, 0, sm, d, scal + kScalNotMatch, cg);   // (uses a wave ballot)
+        BLANCE_LAUNCH(k_converge, shape_converge(P).grid, shape_converge(P).block, shape_converge(P).lds, sm, d, scal + kScalNotMatch, cg);   // (uses a wave ballot)
     }
     pr.launches++;
     return 0;

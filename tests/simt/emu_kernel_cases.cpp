@@ -54,3 +54,5 @@ void emu_case_stay_live(int P, int N, int32_t* live, int32_t* live_len, uint8_t*
 
 // the bulk primitives one at a time (tests/test_kernel_cases_emulated.py): the same entries the device build runs
 #include "../kernels/kernel_cases.inc"
+// the sweep's record, list-edit and tail kernels (tests/test_sweep_cases_emulated.py)
+#include "../kernels/sweep_cases.inc"

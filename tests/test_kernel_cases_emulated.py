@@ -23,6 +23,7 @@ from test_simt_emulated import HERE, _deps
 
 SRC = os.path.join(HERE, "simt", "emu_kernel_cases.cpp")
 INC = os.path.join(HERE, "kernels", "kernel_cases.inc")
+INC_SWEEP = os.path.join(HERE, "kernels", "sweep_cases.inc")
 SO = os.path.join(HERE, "simt", "_build", "libblance_emu_kernel_cases.so")
 
 
@@ -31,7 +32,7 @@ def build_emu_cases():
     of one run take turns at a lock: one compiles, under a name of its own that is moved into place whole, the others find
     it made."""
     import fcntl
-    deps = _deps() + [SRC, INC]
+    deps = _deps() + [SRC, INC, INC_SWEEP]
     os.makedirs(os.path.dirname(SO), exist_ok=True)
     with open(SO + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
