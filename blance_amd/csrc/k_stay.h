@@ -14,8 +14,8 @@ namespace blance {
 // position), exclude classes consistent with that order, all below the smallest partition-independent
 // score of the region -- a lower bound of every other candidate), and writes what the step emits.
 // One WAVE per top priority node, a step per lane, 64 steps a round: the ranks inside a round come from
-// a loop over the round's lanes (v_readlane), the ranks of earlier rounds from a row of counters in
-// LDS the round's lanes bump when they are through.  (Round 5 had one THREAD per top priority node
+// wave ballots over the bits of the leaf indices (stay_round_ranks), the ranks of earlier rounds from a
+// row of counters in LDS the round's lanes bump when they are through.  (Round 5 had one THREAD per top priority node
 // walk its steps with the row in LDS: 100 dependent steps a thread at config 3, 0.34 ms for what is
 // 100,000 independent checks.)  A single step that fails the test raises `flag` and the host runs the
 // pass with k_pass_chain from the same (untouched) state.
@@ -25,13 +25,14 @@ namespace blance {
 // left the counters as they are after them; the pass stands if every step from there on is a stay.  A top priority node's
 // list is in pass order, so the walked steps are a prefix of it.  They are not tested and not written: they are REPLAYED --
 // the row is bumped at the leaves of the nodes such a step emitted (read from `out`: the step may have moved), and in its
-// round the lane takes part in the rank loop with those leaves, so that the steps behind it see its bumps.  A wave whose
+// round the lane takes part in the ranks with those leaves, so that the steps behind it see its bumps.  A wave whose
 // list lies wholly in the prefix has nothing to test and leaves; so does a workgroup of such waves, before it sets up.
 constexpr int kStayWaves = 4;                        // top priority nodes of one workgroup, a wave each
 constexpr int kStaySplit = 64 / kStayWaves;          // workgroups per entry of the (region, 64 leaves) work table
 
 // nodeSorter.Score (plan.go:638-679) with both NumPartitions quotients divided out in place: the expressions
-// chain_score's LDS tables are filled with, so the same bits
+// chain_score's LDS tables are filled with, so the same bits.  (The quotients were tried as LDS tables -- (0.001 * tot) / NP
+// per leaf, i / NP for i < 256, filled by the set-up -- and made no difference beyond spread at config 3: DESIGN.md 4.1b.)
 __device__ __forceinline__ double stay_score(int cnt, int ntn, int tot, int hasw, int w, int NP, double cf, int booster) {
     double lp = 0.0, ff = 0.0;
     if (NP > 0) {
@@ -52,6 +53,55 @@ __device__ __forceinline__ double stay_score(int cnt, int ntn, int tot, int hasw
     }
     r = r - cf;
     return r;
+}
+
+// bits of a leaf index local to a region of `size` leaves (0 for a region of one leaf)
+__host__ __device__ inline int stay_leaf_bits(int size) {
+    int nb = 0;
+    while ((1 << nb) < size) nb++;
+    return nb;
+}
+
+// The ranks of one round: rk[j] = how many (lane, slot) pairs of EARLIER lanes of the wave hold the leaf this lane holds in
+// slot j -- a value an earlier lane holds in two slots counts twice; oi < 0 is "no such node": it matches nothing and its
+// rank is 0.  Leaves are below 1 << nbits.  Bit-sliced: per source slot one ballot of "holds a leaf" and one per bit of the
+// leaf index; a lane ANDs each ballot or its complement, by its own bit, into the mask of the lanes that hold its leaf, and
+// counts the mask's bits below its own lane.  EVERY lane of the wave calls this, in uniform control flow (ballots).
+// KM <= 2 matches all source slots at once (KM * KM masks), KM = 4 one source slot at a time (4 masks, not 16).
+template <int KM>
+__device__ __forceinline__ void stay_round_ranks(const int (&oi)[KM], int nbits, int (&rk)[KM]) {
+    constexpr int JB = KM <= 2 ? KM : 1;
+    const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
+#pragma unroll
+    for (int j = 0; j < KM; j++) rk[j] = 0;
+#pragma unroll
+    for (int j0 = 0; j0 < KM; j0 += JB) {
+        unsigned long long m[KM][JB];
+#pragma unroll
+        for (int a = 0; a < JB; a++) {
+            const unsigned long long v = __ballot(oi[j0 + a] >= 0) & below;
+#pragma unroll
+            for (int j = 0; j < KM; j++) m[j][a] = v;
+        }
+        for (int b = 0; b < nbits; b++) {
+            unsigned long long s[JB];
+#pragma unroll
+            for (int a = 0; a < JB; a++) s[a] = __ballot((oi[j0 + a] >> b) & 1);
+#pragma unroll
+            for (int j = 0; j < KM; j++) {
+                const bool mine = (oi[j] >> b) & 1;
+#pragma unroll
+                for (int a = 0; a < JB; a++) m[j][a] &= mine ? s[a] : ~s[a];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KM; j++) {
+#pragma unroll
+            for (int a = 0; a < JB; a++) rk[j] += __popcll(m[j][a]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < KM; j++) if (oi[j] < 0) rk[j] = 0;
 }
 
 template <int KM>
@@ -89,6 +139,7 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
     int* rowT = cszL + size;                         // [kStayWaves][size]
     int* redN = rowT + kStayWaves * size;            // [kStayWaves]
     double* redS = (double*)(redN + kStayWaves + ((size * (7 + kStayWaves) + kStayWaves) & 1));     // [kStayWaves], 8-byte aligned
+    const int nbits = stay_leaf_bits(size);          // bits of a leaf index of this region (uniform)
     double ms = pos_inf();
     int mn = INT_MAX;
     for (int i = tid; i < size; i += 64 * kStayWaves) {
@@ -171,7 +222,6 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
             int li = (valid && j < k) ? cur[5 + j] : -1;
             if (valid && j < k && (li < 0 || li >= size)) { bad = true; li = -1; }
             oi[j] = li;                                                                   // (-1: no such node, equal to nothing below)
-            rk[j] = 0;
         }
         if (__ballot(done)) {                                                             // (uniform; a prefix of the round's lanes)
             // what a walked step emitted, as leaves of the region (anything else -- a pass that escaped leaves its outputs
@@ -191,17 +241,8 @@ __global__ __launch_bounds__(64 * kStayWaves) void k_stay_by_top(StayParams q) {
                 }
             }
         }
-        // how many earlier steps of this round hold my nodes (the round's lanes in pass order)
-        for (int e = 0; e + 1 < nv; e++) {
-            const bool before = e < lane;
-#pragma unroll
-            for (int j2 = 0; j2 < KM; j2++) {
-                const int xe = __builtin_amdgcn_readlane(oi[j2], e);
-                if (xe < 0) continue;                                                     // (uniform)
-#pragma unroll
-                for (int j = 0; j < KM; j++) rk[j] += (before && xe == oi[j]) ? 1 : 0;
-            }
-        }
+        // how many earlier steps of this round hold my nodes (the round's lanes in pass order; lanes past nv hold nothing)
+        stay_round_ranks<KM>(oi, nbits, rk);
         double so[KM];
 #pragma unroll
         for (int j = 0; j < KM; j++) {
