@@ -271,6 +271,12 @@ struct blance_ctx : CtxHandles {
     bool force_stay_top = false;    // test knob (& 128): try k_stay_by_top in every chain pass with NumPartitions > 0
     bool periodic = true;           // an all-blank chain pass with periodic records walks two periods (k_period.h); off: & 256, or BLANCE_PERIODIC=0
     int periodic_cut = 0;           // test knob BLANCE_PERIODIC_CUT (k_period_segments)
+    // the periodic pass behind a round robin takes its period from the upload, not from a search (k_period_find's known
+    // mode); off: & 65536, or BLANCE_PERIOD_KNOWN=0.  What the upload contributes:
+    bool period_known = true;
+    uint32_t assign_kinds = 0;      // k_validate_parts: bit m -- some list to assign of state m is absent, bit 16 + m -- some is not
+    bool cycle_order_stands = false; // sweep 1's second pass runs in the order of its first (one partitionSorter category in both)
+    bool leaves_distinct = false;   // no two nodes share a leaf of the hierarchy
     DevBuf cnt_base, xbuf, gath;    // sharded pass: loads at pass start, [flags | load change], gathered output slices
     std::vector<int32_t> h_reg_off; // host copy of the chain offsets (slice sizes of the all-gather)
     int chain_group_state = -1;     // the state whose chain pass last grouped the steps by region (chain_order, chain_oi, reg_off) ...
@@ -566,6 +572,8 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     c->periodic = !(opt && (opt->reserved[2] & 256));
     if (const char* pe = getenv("BLANCE_PERIODIC")) c->periodic = atoi(pe) != 0;      // BLANCE_PERIODIC=0: the way out
     if (const char* pc = getenv("BLANCE_PERIODIC_CUT")) c->periodic_cut = atoi(pc);
+    c->period_known = !(opt && (opt->reserved[2] & 65536));
+    if (const char* pk = getenv("BLANCE_PERIOD_KNOWN")) c->period_known = atoi(pk) != 0;
     c->trace = getenv("BLANCE_TRACE") != nullptr;
     if (const char* cw = getenv("BLANCE_CHAIN_WAVES")) c->chain_waves = atoi(cw);
     if (const char* ho = getenv("BLANCE_CHAIN_HANDOFF")) c->chain_handoff = atoi(ho) > 0 ? atoi(ho) : 0;   // 0: the way out; n: hand off n steps or more
@@ -863,11 +871,16 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
         // ones: the first pass gave each partition at least one node (slot 0 always finds a candidate among >= 1 nodes, by
         // the rule or by the fallback of plan.go:216-218; nothing is excluded as "higher priority" yet) and that node is in
         // nodesToAdd.  The category is computed from the LIVE lists, so it changes from pass to pass of a sweep.
-        bool any_added = false, all_alive_added = true;
+        bool any_added = false, all_alive_added = true, any_alive_added = false;
         for (int n = 0; n < NX; n++) {
-            if (pb->node_added[n]) any_added = true;
+            if (pb->node_added[n]) { any_added = true; if (n < N && !pb->node_removed[n]) any_alive_added = true; }
             else if (n < N && !pb->node_removed[n]) all_alive_added = false;
         }
+        // (A plan from nothing whose first pass gave every partition ONE node of nodesNext: the second pass's category is "2"
+        // where that node is in nodesToAdd, else "1" -- one category, and so the first pass's order again, when nodesToAdd is
+        // nil, names every node of nodesNext or names none; "0" needs a removed node.  Not a matter of the knob below: a
+        // stable partition by one category is the order it was given.)
+        c->cycle_order_stands = !c->any_removed && (pb->nodes_to_add_nil || all_alive_added || !any_alive_added);
         const bool never = !c->any_removed && (pb->nodes_to_add_nil || !any_added);
         c->uniform_first = never || (!c->any_removed && na == 0);
         c->uniform_all = never || (!c->any_removed && na == 0 && all_alive_added && c->n_alive >= 1);
@@ -899,6 +912,7 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     c->L = L;
     c->np_later = pb->n_prev + (int)ps.fresh;              // plan.go:50
     c->assign_empty = na == 0;
+    c->assign_kinds = (uint32_t)vr[10];
     c->counts_start_zero = pb->n_loads == 0 && ps.aprev == 0;
     c->out_capacity = ps.cap;
 
@@ -925,8 +939,12 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
         int n_leaves = 1;
         for (int v = 0; v < pb->n_vertices; v++) if (pb->vertex_leaf_hi[v] > n_leaves) n_leaves = pb->vertex_leaf_hi[v];
         std::vector<int32_t> leaf_node((size_t)n_leaves, -1);
+        c->leaves_distinct = true;
         for (int a = 0; a < NX; a++)
-            if (pb->node_leaf_pos[a] >= 0 && pb->node_leaf_pos[a] < n_leaves) leaf_node[pb->node_leaf_pos[a]] = a;
+            if (pb->node_leaf_pos[a] >= 0 && pb->node_leaf_pos[a] < n_leaves) {
+                if (leaf_node[pb->node_leaf_pos[a]] >= 0) c->leaves_distinct = false;
+                leaf_node[pb->node_leaf_pos[a]] = a;
+            }
         PUT(leaf_node, leaf_node.data(), leaf_node.size());
         // Does the rule cut the leaves into regions?  Every node whose leaf lies in
         // a region must have exactly that region as its include set.
@@ -1908,6 +1926,7 @@ struct ChainPassArgs {
     const int32_t* order;          // the pass order: the stable partition of sweep 1, the static order itself afterwards
     bool same_tops;                // no partition has changed its top priority node since this state's last chain pass
     SweepTail* tail;               // non-null: the sweep's last pass, its k_scatter goes to the sweep's tail
+    bool known_cycle = false;      // the pass behind a round robin: its periodic form knows its period (run_state_pass)
 };
 
 // this rank failed before collective A of a sharded chain pass: take part in it with the poison word set
@@ -2345,9 +2364,17 @@ int ChainPass::periodic_walk(bool* walked) {
     RESERVE(cnt_p1, sizeof(int32_t) * (cnt_words + 1));
     int32_t* pb = c->period.as<int32_t>();
     const int gx = cdiv(max_len, 256);
-    BLANCE_LAUNCH(k_period_find, B, 1024, 64, sm, B, cq.reg_off, cq.crec, pb);
-    const int gv = cdiv((long long)max_len * (kCW / 4), 256);
-    BLANCE_LAUNCH_NOSYNC(k_period_verify, gv * B, 256, 0, sm, B, gv, cq.reg_off, cq.crec, pb);
+    // (a known cycle, run_state_pass: the period is the region's count of nodes of nodesNext and nothing breaks it -- one
+    // trip over the region's leaves, no record read, no k_period_verify)
+    const bool known = a.known_cycle;
+    BLANCE_LAUNCH(k_period_find, B, known ? 256 : 1024, 64, sm, B, known ? 1 : 0, N, cq.reg_off, cq.reg_lo, cq.reg_hi, cq.leaf_node,
+                  cq.alive, cq.crec, pb);
+    if (!known) {
+        const int gv = cdiv((long long)max_len * (kCW / 4), 256);
+        BLANCE_LAUNCH_NOSYNC(k_period_verify, gv * B, 256, 0, sm, B, gv, cq.reg_off, cq.crec, pb);
+    } else if (c->trace) {
+        fprintf(stderr, "[blance] chain pass state %d: the period taken from the round robin of the pass before, no search and no k_period_verify\n", m);
+    }
     BLANCE_LAUNCH_NOSYNC(k_period_segments, cdiv(B, 64), 64, 0, sm, B, c->periodic_cut > 0 ? c->periodic_cut : 0, cq.reg_off, pb);
     ChainParams sq = cq;
     // (the plane automaton for regions of up to 128 leaves, the lane-minimum kernel for wider ones)
@@ -2588,6 +2615,7 @@ struct Sweep {
                                    // present list a non-nil slice
     int known_passes = 0, known_state = -1, known_k = 0;        // run_flat_pass's `opening`
     bool known_broken = false;
+    bool known_cycle = false;      // the known pass was committed as a round robin over nodesNext (fresh_cycle_whole)
     // The sweep's last pass, when it is a chain pass, leaves its verdict on the device (ChainRun::defer) and the words
     // come back with the convergence word: one round trip for both.  A bad verdict brings the sweep back for that
     // state alone (retry says how), with everything the pass enqueued behind its gate undone by never having run.
@@ -2779,7 +2807,7 @@ static int run_pass_in_order(blance_ctx* c, PlanRun& pr, Sweep& sw, const StateP
             c->top_gate = (1u << kFlagTopMoved) | (1u << kFlagForced);
             if (c->trace) fprintf(stderr, "[blance] sweep %d: state %d's pass taken to be one run of stays, checked with the sweep's readback\n", sw.it, m);
         }
-        if (whole_known) { sw.known_passes++; sw.known_state = m; sw.known_k = k; }
+        if (whole_known) { sw.known_passes++; sw.known_state = m; sw.known_k = k; sw.known_cycle = ungathered && !assume_stays; }
         else sw.known_broken = true;
     } else if (flat_chain) {
         sw.known_broken = true;
@@ -2838,6 +2866,18 @@ static int run_state_pass(blance_ctx* c, PlanRun& pr, Sweep& sw, int m) {
         ChainPassArgs ca{m, sp.k, sw.NP, sp.higher_mask, sp.r0, sw.it, sp.order,
                          !sw.first && !c->tops_moved && m != h.top_state && c->top_prio_strict,
                          pr.fuse && m == pr.m_last ? &sw.tail : nullptr};
+        // A KNOWN CYCLE (k_period.h): the sweep's second pass, behind a top-state pass that
+        // k_fresh_cycle_commit settled as a round robin over nodesNext -- step j of the pass order took alive_ids[j % A] --
+        // and in the same order.  No partition holds anything else (assign_empty), none has a weight of its own, and the
+        // record's `present` bit is one and the same (every list to assign of this state is absent, or none is): words 1..23
+        // of a step's record are then a function of its top priority node alone (gather_chain_record), distinct nodes give
+        // distinct records (their leaves differ), and the chain of a region repeats its nodes of nodesNext from its first
+        // step to its last.  All known before the pass is enqueued.
+        const uint32_t kinds_m = (c->assign_kinds >> m) & 0x10001u;
+        ca.known_cycle = c->period_known && sw.first && !sw.retrying && !sw.known_broken && pr.at.passes_this_sweep == 2 &&
+                         sw.known_passes == 1 && sw.known_cycle && sw.known_state == h.top_state && sw.known_k == 1 &&
+                         m != h.top_state && sw.NP == 0 && c->assign_empty && h.partition_weights_nil && c->cycle_order_stands &&
+                         c->leaves_distinct && kinds_m != 0x10001u;
         ChainRun run;
         if (sw.retrying) run = sw.retry;
         run.defer = !sw.retrying && m == pr.m_last;
@@ -2916,7 +2956,7 @@ static Verdict sweep_verdict(blance_ctx* c, PlanRun& pr, Sweep& sw) {
             c->top_group_state = -1;                            // (... and a gated k_gather_chain no top priority keys)
             c->pass_ntn_ready = false;
             pr.at = sw.at_open;
-            sw.known_passes = 0; sw.known_state = -1; sw.known_k = 0; sw.known_broken = false;
+            sw.known_passes = 0; sw.known_state = -1; sw.known_k = 0; sw.known_broken = false; sw.known_cycle = false;
             sw.retry = ChainRun();
             sw.retrying = false;
             sw.top_spec_off = true;

@@ -22,7 +22,9 @@ namespace blance {
 // walks whatever lies behind `limit`.  BASELINE config 3: T = 128 (the primaries
 // cycle through a zone), 32,768 steps per region -> 256 walked, 32,512 copied.
 // Nothing is assumed: both conditions are checked on the device for every region,
-// and a region that fails either is walked in full by the same kernel.
+// and a region that fails either is walked in full by the same kernel.  (The first
+// is not SEARCHED for where the driver holds it from the upload: k_period_find's
+// known mode.)
 // ============================================================================
 constexpr int kPeriodCap = 4096;                 // longest period looked for
 constexpr int kPeriodMinRounds = 4;              // a region joins if its periodic stretch is at least this many periods
@@ -41,12 +43,42 @@ __device__ __forceinline__ bool period_same_input(const int32_t* a, const int32_
 // none.  The workgroup looks at blockDim.x candidates per trip in rising order and stops after the first trip with a
 // match (config 3: T = 128, one trip); then it sets up the region's other words, which once took a launch of their own:
 // limit = the chain's length (k_period_verify narrows it behind the kernel boundary), not ok, no d yet.
-__global__ __launch_bounds__(1024) void k_period_find(int B, const int32_t* reg_off, const int32_t* crec, int32_t* pb) {
+//
+// known != 0: THE PERIOD WITHOUT THE SEARCH.  The driver holds that the pass before this one was committed as a round robin
+// over nodesNext (k_fresh_cycle_commit: step j of the pass order took alive_ids[j % A]), that this pass runs in the same
+// order, and that words 1..23 of a record are a function of the step's top priority node alone (run_state_pass lists
+// the conditions).  The grouping by region is stable, so the chain of region rg has the region's nodes of nodesNext as
+// its tops, in id order, again and again from its first step to its last; distinct nodes lie on distinct leaves, so the
+// smallest t whose record equals the first step's is their number, and no step breaks the repetition -- what the search and
+// k_period_verify would find: T = the region's count of alive leaves (k_period_judge's test of a leaf) if a candidate,
+// limit = the chain's length.  No record is read, and k_period_verify is not launched.
+__global__ __launch_bounds__(1024) void k_period_find(int B, int known, int N, const int32_t* reg_off, const int32_t* reg_lo,
+                                                      const int32_t* reg_hi, const int32_t* leaf_node, const uint8_t* alive,
+                                                      const int32_t* crec, int32_t* pb) {
     BLANCE_DYN_LDS(lds);
     int* best = (int*)lds;
     const int rg = blockIdx.x, tid = threadIdx.x;
     const int cbeg = reg_off[rg], len = reg_off[rg + 1] - cbeg;
     const int last = len - 1 < kPeriodCap ? len - 1 : kPeriodCap;       // candidates: t in [1, last]
+    if (known) {
+        if (tid == 0) *best = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int pos = reg_lo[rg] + tid; pos < reg_hi[rg]; pos += (int)blockDim.x) {
+            const int n = leaf_node[pos];
+            if (n >= 0 && n < N && alive[n]) mine++;
+        }
+        if (mine) atomicAdd(best, mine);
+        __syncthreads();
+        if (tid == 0) {
+            const int count = *best;
+            pb[kPT * B + rg] = (count >= 1 && count <= last) ? count : INT_MAX;
+            pb[kPLimit * B + rg] = len;
+            pb[kPOk * B + rg] = 0;
+            pb[kPD * B + rg] = INT_MIN;
+        }
+        return;
+    }
     if (tid == 0) *best = INT_MAX;
     __syncthreads();
     int found = INT_MAX;

@@ -25,6 +25,8 @@ struct DevProblem {   // device pointers + sizes shared by the elementwise kerne
 // Result block: [0] error bits, [1] longest list (L), [2] partitions not in prevMap, [3] INT_MAX - (4 i + check) of the first
 // list i whose shape is wrong (0: none); 64-bit words from byte 16:
 // [2] result capacity (sum of max(k, len)), [3] sum of |weights|, [4] |weight| * prev entries.
+// [10] the kinds of the lists to assign, state by state: bit m -- some partition's list of state m is absent, bit 16 + m -- some
+// partition's is not (a chain record's `present` bit is the same in every step of state m's pass when only one of them is set).
 constexpr int kVErrMonotone = 1, kVErrKind = 2, kVErrLong = 4, kVErrOrder = 8, kVErrAssignId = 16, kVErrPrevId = 32;
 struct ValidateParams {
     int32_t P, M, weights_nil;
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(256) void k_validate_parts(ValidateParams v) {
     unsigned long long (*red)[8] = (unsigned long long (*)[8])lds;      // [4 waves][8]
     const long long PM = (long long)v.P * v.M;
     const long long n = PM > v.P ? PM : v.P, stride = (long long)gridDim.x * blockDim.x;
-    int err = 0, L = 0, fresh = 0, first = 0;
+    int err = 0, L = 0, fresh = 0, first = 0, kinds = 0;
     unsigned long long cap = 0, sumw = 0, aprev = 0;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
         if (idx < PM) {
@@ -56,6 +58,7 @@ __global__ __launch_bounds__(256) void k_validate_parts(ValidateParams v) {
             const int l = a > b ? a : b;
             L = l > L ? l : L;
             const int k = v.k[idx % v.M];
+            kinds |= 1 << ((int)(idx % v.M) + (v.a_kind[idx] == kListAbsent ? 0 : 16));
             if (a >= 0) cap += (unsigned long long)(a > k ? a : k);
         }
         if (idx < v.P) {
@@ -81,6 +84,7 @@ __global__ __launch_bounds__(256) void k_validate_parts(ValidateParams v) {
         const int l2 = __shfl_xor(L, o, 64);
         L = l2 > L ? l2 : L;
         fresh += __shfl_xor(fresh, o, 64);
+        kinds |= __shfl_xor(kinds, o, 64);
         cap += ((unsigned long long)(unsigned)__shfl_xor((int)(unsigned)(cap >> 32), o, 64) << 32) | (unsigned)__shfl_xor((int)(unsigned)cap, o, 64);
         sumw += ((unsigned long long)(unsigned)__shfl_xor((int)(unsigned)(sumw >> 32), o, 64) << 32) | (unsigned)__shfl_xor((int)(unsigned)sumw, o, 64);
         aprev += ((unsigned long long)(unsigned)__shfl_xor((int)(unsigned)(aprev >> 32), o, 64) << 32) | (unsigned)__shfl_xor((int)(unsigned)aprev, o, 64);
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(256) void k_validate_parts(ValidateParams v) {
     const int wv = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         red[wv][0] = (unsigned long long)(unsigned)err; red[wv][1] = (unsigned long long)(unsigned)first; red[wv][2] = (unsigned long long)(unsigned)L;
-        red[wv][3] = (unsigned long long)(unsigned)fresh; red[wv][4] = cap; red[wv][5] = sumw; red[wv][6] = aprev;
+        red[wv][3] = (unsigned long long)(unsigned)fresh; red[wv][4] = cap; red[wv][5] = sumw; red[wv][6] = aprev; red[wv][7] = (unsigned long long)(unsigned)kinds;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -99,6 +103,7 @@ __global__ __launch_bounds__(256) void k_validate_parts(ValidateParams v) {
             L = (int)red[w2][2] > L ? (int)red[w2][2] : L;
             fresh += (int)red[w2][3];
             cap += red[w2][4]; sumw += red[w2][5]; aprev += red[w2][6];
+            kinds |= (int)red[w2][7];
         }
         unsigned long long* r64 = (unsigned long long*)(v.res + 4);
         if (err) atomicOr(v.res, err);
@@ -108,6 +113,7 @@ __global__ __launch_bounds__(256) void k_validate_parts(ValidateParams v) {
         if (cap) atomicAdd(r64, cap);
         if (sumw) atomicAdd(r64 + 1, sumw);
         if (aprev) atomicAdd(r64 + 2, aprev);
+        if (kinds) atomicOr(v.res + 10, kinds);
     }
 }
 // node ids of a CSR's payload in [0, NX)
