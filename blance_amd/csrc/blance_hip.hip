@@ -21,6 +21,7 @@
 #include "k_sweep.h"
 #include "k_flat.h"
 #include "k_period.h"
+#include "k_cycle.h"
 #include "k_plan_moves.h"
 #include "k_plan_wire.h"
 #include "host/json_escape.hpp"
@@ -277,6 +278,11 @@ struct blance_ctx : CtxHandles {
     uint32_t assign_kinds = 0;      // k_validate_parts: bit m -- some list to assign of state m is absent, bit 16 + m -- some is not
     bool cycle_order_stands = false; // sweep 1's second pass runs in the order of its first (one partitionSorter category in both)
     bool leaves_distinct = false;   // no two nodes share a leaf of the hierarchy
+    // The chain pass behind a round robin takes its grouping by region and k_stay_by_top's work list from tables of the upload
+    // (k_cycle.h, RuleRegions::cyc), not from two counting sorts.  0: off (& 131072, or BLANCE_CYCLE_GROUP=0); 2: the test knob
+    // BLANCE_CYCLE_GROUP=refute -- the kernel's check of the premise fails for step 0, the pass goes in order.
+    int cycle_group = 1;
+    int64_t cycle_group_epoch = -1; // the count of regroupings at which the grouping by region was taken from those tables (-1: it was not)
     DevBuf cnt_base, xbuf, gath;    // sharded pass: loads at pass start, [flags | load change], gathered output slices
     std::vector<int32_t> h_reg_off; // host copy of the chain offsets (slice sizes of the all-gather)
     int chain_group_state = -1;     // the state whose chain pass last grouped the steps by region (chain_order, chain_oi, reg_off) ...
@@ -352,6 +358,11 @@ struct blance_ctx : CtxHandles {
         DevBuf wg_region, wg_chunk;     // k_stay_by_top: entry b of its work table = the tops at leaves reg_lo + 64 chunk .. + 63 of its region
         int n_stay_wgs = 0, n_leaves = 0;
         int cls_run = 0;                // S if every exclude class is an aligned run of S = 2^e <= 64 node-carrying leaves, else 0
+        // k_cycle.h: where step j of a round robin over nodesNext lies in the region chains and in k_stay_by_top's work list,
+        // for the upload's partition count.  Built when no two nodes share a leaf and every node of nodesNext lies in a region.
+        bool cyc_ok = false;
+        DevBuf cyc, cyc_reg_off, cyc_top_off;   // [n_alive][kCycWords], [n_regions + 1], [n_leaves + 1]
+        std::vector<int32_t> h_cyc_reg_off;     // the host's copy of the chain offsets
     };
     std::vector<RuleRegions> rule_regions;
     DevBuf leaf_node, regid, chain_order, bucket_counts, reg_off, cnt_save, crec;
@@ -574,6 +585,8 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     if (const char* pc = getenv("BLANCE_PERIODIC_CUT")) c->periodic_cut = atoi(pc);
     c->period_known = !(opt && (opt->reserved[2] & 65536));
     if (const char* pk = getenv("BLANCE_PERIOD_KNOWN")) c->period_known = atoi(pk) != 0;
+    c->cycle_group = opt && (opt->reserved[2] & 131072) ? 0 : 1;
+    if (const char* cg = getenv("BLANCE_CYCLE_GROUP")) c->cycle_group = !strcmp(cg, "refute") ? 2 : atoi(cg) != 0;
     c->trace = getenv("BLANCE_TRACE") != nullptr;
     if (const char* cw = getenv("BLANCE_CHAIN_WAVES")) c->chain_waves = atoi(cw);
     if (const char* ho = getenv("BLANCE_CHAIN_HANDOFF")) c->chain_handoff = atoi(ho) > 0 ? atoi(ho) : 0;   // 0: the way out; n: hand off n steps or more
@@ -1030,6 +1043,37 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
                 if (put(up, rr.reg_hi, rhi.data(), rhi.size())) return BLANCE_ERR_DEVICE;
                 if (put(up, rr.leaf_cls, leaf_cls.data(), leaf_cls.size())) return BLANCE_ERR_DEVICE;
                 if (put(up, rr.cls_size, cls_size.data(), cls_size.size())) return BLANCE_ERR_DEVICE;
+            }
+            // The tables of k_cycle.h.  Step j = s A + a of a round robin has top priority node alive_ids[a]: region r_a, rank
+            // q_a among the region's nodes of nodesNext, c_r of them in the region.  A region's chain has a step per full
+            // cycle and node, and one more for every node the last, partial cycle still reaches.
+            rr.cyc_ok = false;
+            std::vector<int32_t> cyc, cyc_top_off;
+            if (ok && c->leaves_distinct && c->n_alive >= 1) {
+                const int A = c->n_alive, B = (int)rlo.size(), full = P / A, part = P % A;
+                bool all_in = true;
+                for (int a = 0; a < A && all_in; a++) all_in = node_region[alive_ids[a]] >= 0;
+                if (all_in) {
+                    std::vector<int32_t> count((size_t)B, 0), last((size_t)B, 0), leaf_steps((size_t)n_leaves, 0);
+                    cyc.assign((size_t)A * kCycWords, 0);
+                    for (int a = 0; a < A; a++) {
+                        const int n = alive_ids[a], g = node_region[n];
+                        cyc[(size_t)a * kCycWords + kCycRegion] = g;
+                        cyc[(size_t)a * kCycWords + kCycRank] = count[g]++;
+                        cyc[(size_t)a * kCycWords + kCycLeaf] = pb->node_leaf_pos[n];
+                        if (a < part) last[g]++;
+                        leaf_steps[pb->node_leaf_pos[n]] = full + (a < part ? 1 : 0);
+                    }
+                    for (int a = 0; a < A; a++) cyc[(size_t)a * kCycWords + kCycCount] = count[cyc[(size_t)a * kCycWords + kCycRegion]];
+                    rr.h_cyc_reg_off.assign((size_t)B + 1, 0);
+                    for (int g = 0; g < B; g++) rr.h_cyc_reg_off[g + 1] = rr.h_cyc_reg_off[g] + full * count[g] + last[g];
+                    cyc_top_off.assign((size_t)n_leaves + 1, 0);
+                    for (int lp = 0; lp < n_leaves; lp++) cyc_top_off[lp + 1] = cyc_top_off[lp] + leaf_steps[lp];
+                    if (put(up, rr.cyc, cyc.data(), cyc.size())) return BLANCE_ERR_DEVICE;
+                    if (put(up, rr.cyc_reg_off, rr.h_cyc_reg_off.data(), rr.h_cyc_reg_off.size())) return BLANCE_ERR_DEVICE;
+                    if (put(up, rr.cyc_top_off, cyc_top_off.data(), cyc_top_off.size())) return BLANCE_ERR_DEVICE;
+                    rr.cyc_ok = true;
+                }
             }
             if ((st = up.flush())) return st;             // this rule's staging vectors go out of scope (their bytes are in the staging buffer)
         }
@@ -1927,6 +1971,8 @@ struct ChainPassArgs {
     bool same_tops;                // no partition has changed its top priority node since this state's last chain pass
     SweepTail* tail;               // non-null: the sweep's last pass, its k_scatter goes to the sweep's tail
     bool known_cycle = false;      // the pass behind a round robin: its periodic form knows its period (run_state_pass)
+    bool round_robin = false;      // ... the same, whether or not the period is taken from it: step j of `order` has top
+                                   // priority node alive_ids[j % n_alive] (the grouping from the upload's tables, k_cycle.h)
 };
 
 // this rank failed before collective A of a sharded chain pass: take part in it with the poison word set
@@ -2004,6 +2050,7 @@ struct ChainPass {
     int32_t* const flags;                    // the chain flags on the device
     Gate top_gate = kNoGate;
     bool regroup = false, spec = false, defer = false, gather_out = false;
+    bool cycle = false;                      // the grouping by region comes from the upload's tables (k_cycle_group)
     int32_t cfl[kChainFlags] = {0};          // the classification's flags (all zero when they were assumed)
     int32_t n_events = 0;
     bool stay_fits = false, try_stay = false, group_stands = false, group_ahead = false;
@@ -2043,6 +2090,8 @@ struct ChainPass {
     int events();
     int gather_records();
     int group_by_top(hipStream_t st, DevBuf& sums);
+    bool top_from_tables() const;
+    int top_by_tables();
     void fill_chain_params();
     int start_counters();
     void fill_stay_params(StayParams& sq);
@@ -2083,7 +2132,25 @@ int ChainPass::classify_and_group() {
     // flags come back.  Such a pass reads neither the region ids nor the event counts, and k_gather_chain, which walks the
     // same lists right behind, raises the two words itself (gather_chain_record's `classify`): no k_chain_classify.
     spec = run.allow_spec && !regroup && !sharded && c->speculate > 0;
-    if (!spec) {
+    // The pass behind a round robin (run_state_pass): the region of step j's top priority node is that of alive_ids[j % A], and
+    // the stable sort by it a closed form over the upload's tables -- k_cycle_group classifies, places every step and inverts
+    // the order in one launch, and checks the premise step by step (kFlagNotLocal: the pass goes in order, run_once drops the
+    // grouping).  The tallies count the launches it replaces.
+    cycle = a.round_robin && regroup && !sharded && rr.cyc_ok && c->cycle_group > 0 && a.order != nullptr;
+    if (cycle) {
+        const LaunchShape cs = shape_chain_classify(P);
+        BLANCE_LAUNCH_NOSYNC(k_cycle_group, cs.grid, cs.block, cs.lds, sm, d, m, h.top_state, a.order, rr.node_region.as<int32_t>(),
+                             c->n_alive, B, c->alive_ids.as<int32_t>(), rr.cyc.as<int32_t>(), rr.cyc_reg_off.as<int32_t>(),
+                             c->cycle_group == 2 ? 1 : 0, c->regid.as<int32_t>(), c->n_ev.as<int32_t>(),
+                             c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>(), c->chain_inv.as<int32_t>(),
+                             c->reg_off.as<int32_t>(), flags, top_gate);
+        pr.launches++;
+        c->chain_group_state = m;
+        c->group_epoch++;
+        c->chain_group_static = a.order == c->part_order.as<int32_t>();
+        c->cycle_group_epoch = c->group_epoch;
+        if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps grouped by region from the round robin's tables, no sort\n", m);
+    } else if (!spec) {
         const LaunchShape cs = shape_chain_classify(P);
         BLANCE_LAUNCH_NOSYNC(k_chain_classify, cs.grid, cs.block, cs.lds, sm, d, m, h.top_state,
                              a.order, rr.node_region.as<int32_t>(), c->regid.as<int32_t>(),
@@ -2091,7 +2158,7 @@ int ChainPass::classify_and_group() {
     } else {
         if (c->trace) fprintf(stderr, "[blance] chain pass state %d: no k_chain_classify, k_gather_chain raises its flag words\n", m);
     }
-    if (regroup) {
+    if (regroup && !cycle) {
         const int ge = group_by_key(c, sm, c->scan_sums, P, c->regid.as<int32_t>(), a.order, B, c->bucket_counts.as<int32_t>(),
                                     c->reg_off.as<int32_t>(), c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>());
         if (ge) return ge;
@@ -2100,7 +2167,7 @@ int ChainPass::classify_and_group() {
         c->chain_group_state = m;
         c->group_epoch++;
         c->chain_group_static = a.order == c->part_order.as<int32_t>();
-    } else if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the grouping by region of the last sweep stands\n", m);
+    } else if (!regroup && c->trace) fprintf(stderr, "[blance] chain pass state %d: the grouping by region of the last sweep stands\n", m);
     // events: how many?  (also: is every step region-local at all, are there orphan nodes); a sharded
     // plan reads the chain offsets in the same round trip (the slice sizes of collective B)
     defer = run.defer && !sharded && c->speculate > 0;
@@ -2111,11 +2178,19 @@ int ChainPass::classify_and_group() {
     run.redo = false;
     if (!spec) {
         HIPTRY(read_back(c, cfl, flags, sizeof cfl));
-        if (regroup) {                                     // (always: the next sweep may reuse the grouping, the host's copy with it)
+        if (cycle) {                                       // (the chain offsets are the upload's)
+            c->h_reg_off = rr.h_cyc_reg_off;
+        } else if (regroup) {                              // (always: the next sweep may reuse the grouping, the host's copy with it)
             c->h_reg_off.resize((size_t)B + 1);
             HIPTRY(read_back(c, c->h_reg_off.data(), c->reg_off.p, sizeof(int32_t) * ((size_t)B + 1)));
         }
         HIPTRY(stream_sync(c));
+    }
+    if (cycle && cfl[kFlagNotLocal]) {                     // the premise did not hold: chain_order is a permutation, not a grouping
+        c->chain_group_state = -1;
+        c->top_group_state = -1;
+        c->cycle_group_epoch = -1;
+        if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the round robin's tables do not describe this pass, the grouping is dropped\n", m);
     }
     return 0;
 }
@@ -2163,6 +2238,24 @@ int ChainPass::group_by_top(hipStream_t st, DevBuf& sums) {
     return 0;
 }
 
+// k_stay_by_top's work list from the upload's tables (k_cycle_top) where group_by_top would sort for it: the grouping by region
+// in force is the one k_cycle_group made.  On the planner's stream; counted as the five launches it replaces.
+bool ChainPass::top_from_tables() const {
+    return c->cycle_group > 0 && rr.cyc_ok && !sharded && c->chain_group_state == m && c->cycle_group_epoch == c->group_epoch &&
+           !cfl[kFlagNotLocal];
+}
+int ChainPass::top_by_tables() {
+    const int A = c->n_alive, wpa = std::max(1, cdiv(cdiv(P, A), 64));
+    BLANCE_LAUNCH_NOSYNC(k_cycle_top, cdiv((int64_t)A * wpa, 4), 256, 0, sm, P, A, wpa, rr.n_leaves, rr.cyc.as<int32_t>(),
+                         rr.cyc_reg_off.as<int32_t>(), rr.cyc_top_off.as<int32_t>(), c->top_off.as<int32_t>(),
+                         c->top_order.as<int32_t>(), top_gate);
+    c->top_group_state = m;
+    c->top_group_epoch = c->group_epoch;
+    pr.launches += 5;
+    if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps grouped by top priority node from the round robin's tables, no sort\n", m);
+    return 0;
+}
+
 // The compact records of the pass in chain order (k_gather_chain); whether k_stay_by_top is worth a try, and its work list
 // made on the second stream for the next sweep when it is not.
 int ChainPass::gather_records() {
@@ -2192,10 +2285,14 @@ int ChainPass::gather_records() {
     // planners' own streams end up sharing queues and their long kernels run one after the other.)
     const bool for_next = stay_fits && !try_stay && c->speculate > 0 && a.it + 1 < h.max_iterations;
     group_ahead = (for_next || handoff || handoff_next) && !group_stands && (c->side || g_live_contexts.load() <= 2);
+    // (the tables of the round robin give the list in one small launch on this stream: no second stream, no keys)
+    const bool by_tables = top_from_tables();
+    const bool list_by_tables = by_tables && (group_ahead || ((handoff || handoff_next) && !group_stands));
+    if (by_tables) group_ahead = false;
     if (group_ahead && !c->side && hipStreamCreate(&c->side) != hipSuccess) { c->side = nullptr; group_ahead = false; (void)hipGetLastError(); }
     // (no second stream: a list the hand-off needs is made on this one, a list for the next sweep's k_stay_by_top alone is not)
-    const bool group_here = (handoff || handoff_next) && !group_stands && !group_ahead;
-    if (try_stay || group_ahead || handoff || group_here) {
+    const bool group_here = (handoff || handoff_next) && !group_stands && !group_ahead && !by_tables;
+    if (try_stay || group_ahead || handoff || group_here || list_by_tables) {
         RESERVE(topkey, sizeof(int32_t) * ((size_t)P + 1));
         RESERVE(top_order, sizeof(int32_t) * ((size_t)P + 1));
         RESERVE(top_off, sizeof(int32_t) * ((size_t)rr.n_leaves + 2));
@@ -2205,7 +2302,7 @@ int ChainPass::gather_records() {
             c->side_pending = false;
         }
     }
-    const bool group_now = (try_stay && !group_stands) || group_ahead || group_here;
+    const bool group_now = (try_stay && !group_stands && !by_tables) || group_ahead || group_here;
     const LaunchShape gs = shape_gather_chain(P);
     BLANCE_LAUNCH(k_gather_chain, gs.grid, gs.block, gs.lds, sm, d, m, h.top_state, a.higher_mask,
                          c->chain_order.as<int32_t>(), c->chain_oi.as<int32_t>(), c->state_stick.as<int32_t>(),
@@ -2225,6 +2322,9 @@ int ChainPass::gather_records() {
         const int ge = group_by_top(sm, c->scan_sums);
         if (ge) return ge;
         if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps grouped by top priority node for the hand-off\n", m);
+    } else if (list_by_tables) {
+        const int ge = top_by_tables();
+        if (ge) return ge;
     }
     return 0;
 }
@@ -2325,7 +2425,7 @@ int ChainPass::trace_handoff() {
 int ChainPass::stay_attempt(bool* stayed) {
     *stayed = false;
     if (!group_stands) {
-        const int ge = group_by_top(sm, c->scan_sums);
+        const int ge = top_from_tables() ? top_by_tables() : group_by_top(sm, c->scan_sums);
         if (ge) return ge;
     } else if (c->trace) fprintf(stderr, "[blance] chain pass state %d: the steps' grouping by top priority node stands\n", m);
     StayParams sq;
@@ -2874,10 +2974,11 @@ static int run_state_pass(blance_ctx* c, PlanRun& pr, Sweep& sw, int m) {
         // distinct records (their leaves differ), and the chain of a region repeats its nodes of nodesNext from its first
         // step to its last.  All known before the pass is enqueued.
         const uint32_t kinds_m = (c->assign_kinds >> m) & 0x10001u;
-        ca.known_cycle = c->period_known && sw.first && !sw.retrying && !sw.known_broken && pr.at.passes_this_sweep == 2 &&
+        ca.round_robin = sw.first && !sw.retrying && !sw.known_broken && pr.at.passes_this_sweep == 2 &&
                          sw.known_passes == 1 && sw.known_cycle && sw.known_state == h.top_state && sw.known_k == 1 &&
                          m != h.top_state && sw.NP == 0 && c->assign_empty && h.partition_weights_nil && c->cycle_order_stands &&
                          c->leaves_distinct && kinds_m != 0x10001u;
+        ca.known_cycle = c->period_known && ca.round_robin;
         ChainRun run;
         if (sw.retrying) run = sw.retry;
         run.defer = !sw.retrying && m == pr.m_last;

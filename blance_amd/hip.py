@@ -197,7 +197,7 @@ class Planner:
 
     def __init__(self, device_id=0, engine=abi.ENGINE_AUTO, lib_path=None, force_threads=0,
                  chain_min_parts=0, seq_speculation=True, tree="auto", planes=True, stay_top="auto", periodic=True, queue=True,
-                 shard_one_rank=False, period_known=True):
+                 shard_one_rank=False, period_known=True, cycle_group=True):
         self.lib = load_library(lib_path)
         opt = abi.Options()
         opt.engine = engine
@@ -222,9 +222,12 @@ class Planner:
         # 32768 = its walking wave copies a batch's row bit maps itself (the helper waves do since round 6)
         # 65536 = the periodic pass behind a round robin searches for its period and verifies it, as every other periodic
         # pass does (the default takes it from the round robin: k_period_find's known mode; also BLANCE_PERIOD_KNOWN=0)
+        # 131072 = the chain pass behind a round robin groups its steps by region and by top priority node with the counting
+        # sorts every other pass uses (the default takes both groupings from tables of the upload: k_cycle.h; also
+        # BLANCE_CYCLE_GROUP=0)
         qbits = {True: 0, "on": 0, False: 512, "off": 512, "general": 1024, "dense": 1024 | 2048, "lean-cpp": 4096,
                  "exact-rebuild": 8192, "bits-self": 32768}[queue]
-        opt.reserved[2] = qbits | (16384 if shard_one_rank else 0) | (0 if period_known else 65536) | (0 if periodic else 256) | {"auto": 0, "off": 64, "force": 128}[stay_top] | (0 if planes else 32) | (0 if seq_speculation else 1) | {"auto": 0, "off": 2, "dense": 4 | 8, "on": 8, "long": 8 | 16,
+        opt.reserved[2] = qbits | (16384 if shard_one_rank else 0) | (0 if period_known else 65536) | (0 if cycle_group else 131072) | (0 if periodic else 256) | {"auto": 0, "off": 64, "force": 128}[stay_top] | (0 if planes else 32) | (0 if seq_speculation else 1) | {"auto": 0, "off": 2, "dense": 4 | 8, "on": 8, "long": 8 | 16,
                                                           "dense-long": 4 | 8 | 16}[tree]
         h = C.c_void_p()
         self._check(self.lib.blance_ctx_create(C.byref(opt), C.byref(h)))
