@@ -298,6 +298,22 @@ class WireNames(C.Structure):
                 ("state_bytes", C.c_void_p), ("state_off", C.c_void_p)]
 
 
+class WireLists(C.Structure):
+    """blance_wire_lists of include/blance_hip.h (blance_wire_decode_device): the decoded lists in the layout of prev_* /
+    assign_*, the counters, the refusal and the timings."""
+    _fields_ = [("part_kind", C.c_void_p), ("off", C.c_void_p), ("kind", C.c_void_p), ("nodes", C.c_void_p),
+                ("capacity", C.c_int64), ("n_node_refs", C.c_int64), ("n_parts_seen", C.c_int64),
+                ("refusal", C.c_int32), ("refusal_at", C.c_int64), ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+# BLANCE_WIRE_REFUSED_* of include/blance_hip.h: why blance_wire_decode_device refused a document
+WIRE_REFUSALS = ("accepted", "grammar", "type", "null_document", "unknown_partition", "unknown_state", "unknown_node",
+                 "repeated_partition", "repeated_state", "repeated_field", "unknown_field", "null_partition", "name_missing",
+                 "name_differs", "null_element", "invalid_utf8", "unpaired_surrogate", "control_character", "record_too_long",
+                 "document_too_long")
+WIRE_REFUSED = {name: code for code, name in enumerate(WIRE_REFUSALS)}
+
+
 # blance_plan_stats as a numpy record (pointers as addresses): Planner.plan_batch_stats fills many at once
 PLAN_STATS_ARRAYS = ("load_min", "load_max", "load_sum", "load_sumsq", "nodes_used", "unmet_slots", "rule_violations")
 PLAN_STATS_DTYPE = np.dtype({

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -24,6 +25,7 @@
 #include "k_cycle.h"
 #include "k_plan_moves.h"
 #include "k_plan_wire.h"
+#include "k_wire_decode.h"
 #include "host/json_escape.hpp"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
 #include "tu_seq.hip"
@@ -241,6 +243,15 @@ struct CtxHandles {
 // this plus a stage never hand off: the driver then plans the pass as before.
 constexpr int kChainHandoffMin = 8192;
 
+// blance_wire_dict_create: per kind of name (partitions, nodes, states) the hash table, the raw names and
+// their offsets on the device.  Owned by the context it was made on.
+struct blance_wire_dict {
+    blance_ctx* owner = nullptr;
+    int32_t n[3] = {0, 0, 0};       // P, NX, M
+    uint32_t mask[3] = {0, 0, 0};
+    DevBuf slots[3], bytes[3], off[3];
+};
+
 enum PassKind { kPassKernel = 0, kPassFlatBulk = 1, kPassBlank = 2, kPassStayTop = 3 };   // what ran a state pass (statistics)
 
 struct blance_ctx : CtxHandles {
@@ -313,6 +324,12 @@ struct blance_ctx : CtxHandles {
     bool wire_names = false;        // `wire` holds the names of the problem uploaded last
     int wire_stage = kWireStageDefault;   // bytes of k_wire_write's LDS stage (test knob BLANCE_WIRE_STAGE lowers it)
     DevBuf wire[10];
+    // blance_wire_dict_create / blance_wire_decode_device: the dictionaries made on this context, the
+    // document's copy and the scratch of the decoder (kept between calls)
+    int wd_tile = kWdTileDefault;   // bytes of a tile of the record split (test knob BLANCE_WIRE_IN_TILE lowers it)
+    int wd_stage = kWdStageDefault; // bytes of k_wd_parse's LDS stage (test knob BLANCE_WIRE_IN_STAGE)
+    std::vector<blance_wire_dict*> wd_dicts;
+    DevBuf wd[13];
     int64_t comm_calls = 0, comm_bytes = 0;
     size_t comm_events_used = 0;             // (comm_events: CtxHandles)
     double comm_ms = 0.0;                    // device time between those pairs, all plans so far
@@ -597,6 +614,14 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
         const int v = atoi(ws);
         c->wire_stage = v < kWireStageMin ? kWireStageMin : v > kWireStageMax ? kWireStageMax : v;
     }
+    if (const char* wt = getenv("BLANCE_WIRE_IN_TILE")) {
+        const int v = atoi(wt) & ~63;
+        c->wd_tile = v < kWdTileMin ? kWdTileMin : v > kWdTileMax ? kWdTileMax : v;
+    }
+    if (const char* wi = getenv("BLANCE_WIRE_IN_STAGE")) {
+        const int v = atoi(wi) & ~15;
+        c->wd_stage = v < kWdStageMin ? kWdStageMin : v > kWdStageMax ? kWdStageMax : v;
+    }
     if (hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
         hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreate(&c->side_go) != hipSuccess || hipEventCreate(&c->side_done) != hipSuccess) {
@@ -616,6 +641,7 @@ blance_ctx::~blance_ctx() {
     if (side) (void)hipStreamSynchronize(side);
     comm_release(this);
     if (rb_buf) pin_free(rb_buf);
+    for (blance_wire_dict* d : wd_dicts) delete d;
 }
 
 extern "C" void blance_ctx_destroy(blance_ctx* c) {
@@ -3751,6 +3777,238 @@ extern "C" int blance_plan_wire_get(blance_ctx* c, char* buf, size_t cap, size_t
     std::lock_guard<std::mutex> g(c->mu);
     rb_discard(c);
     return settle(c, plan_wire_locked(c, buf, cap, need, device_ms));
+    });
+}
+
+// ---- a PartitionMap document decoded on the device (blance_wire_dict_create / blance_wire_decode_device)
+namespace {
+// the open-addressing table of a blob's names (k_wire_decode.h: WdTable) at load <= 1/2 and the offsets as int32;
+// 0, or 1: two names are equal, 2: 2^31 bytes or more
+int wd_build_table(const WireBlob& b, std::vector<int32_t>& slots, uint32_t& mask, std::vector<int32_t>& off32) {
+    if (b.off[b.n] > (int64_t)INT32_MAX) return 2;
+    size_t cap = 2;
+    while (cap < 2 * (size_t)b.n) cap <<= 1;
+    mask = (uint32_t)(cap - 1);
+    slots.assign(2 * cap, -1);
+    off32.resize((size_t)b.n + 1);
+    for (int64_t i = 0; i <= b.n; i++) off32[(size_t)i] = (int32_t)b.off[i];
+    for (int64_t i = 0; i < b.n; i++) {
+        const unsigned char* s = (const unsigned char*)b.bytes + b.off[i];
+        const int n = (int)(b.off[i + 1] - b.off[i]);
+        uint32_t h = wd_hash_init();
+        for (int k = 0; k < n; k++) h = wd_hash_step(h, s[k]);
+        h = wd_hash_done(h, n);
+        uint32_t at = h & mask;
+        for (;;) {
+            const int32_t id = slots[2 * (size_t)at];
+            if (id < 0) break;
+            if ((uint32_t)slots[2 * (size_t)at + 1] == h && wire_cmp(b, id, i) == 0) return 1;
+            at = (at + 1) & mask;
+        }
+        slots[2 * (size_t)at] = (int32_t)i;
+        slots[2 * (size_t)at + 1] = (int32_t)h;
+    }
+    return 0;
+}
+}  // namespace
+
+static int wire_dict_locked(blance_ctx* c, const blance_wire_names* nm, int32_t P, int32_t NX, int32_t M, blance_wire_dict** out) {
+    if (P < 0 || NX < 0 || M < 0) return fail(BLANCE_ERR_BAD_ARG, "negative count");
+    if ((int64_t)P * M >= (int64_t)INT32_MAX) return fail(BLANCE_ERR_BAD_ARG, "n_parts * n_states of 2^31 - 1 or more");
+    const WireBlob blobs[3] = {{nm->part_bytes, nm->part_off, P}, {nm->node_bytes, nm->node_off, NX}, {nm->state_bytes, nm->state_off, M}};
+    for (const WireBlob& b : blobs) {
+        if (!b.off) return fail(BLANCE_ERR_BAD_ARG, "null offsets");
+        if (b.off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "name offsets must start at 0");
+        for (int64_t i = 0; i < b.n; i++)
+            if (b.off[i + 1] < b.off[i]) return fail(BLANCE_ERR_BAD_ARG, "name offsets not monotone");
+        if (b.off[b.n] > 0 && !b.bytes) return fail(BLANCE_ERR_BAD_ARG, "null name bytes");
+    }
+    std::vector<int32_t> slots[3], off32[3];
+    std::unique_ptr<blance_wire_dict> d(new blance_wire_dict());
+    d->owner = c;
+    for (int k = 0; k < 3; k++) {
+        d->n[k] = (int32_t)blobs[k].n;
+        const int e = wd_build_table(blobs[k], slots[k], d->mask[k], off32[k]);
+        if (e == 2) return fail(BLANCE_ERR_UNSUPPORTED, "names of 2^31 bytes or more");
+        if (e == 1 && k == 0) return fail(BLANCE_ERR_UNSUPPORTED, "two partitions with one name (the reference's map would keep one of them)");
+        if (e == 1) return fail(BLANCE_ERR_BAD_ARG, k == 1 ? "two nodes with one name" : "two states with one name");
+    }
+    HIPTRY(hipSetDevice(c->device));
+    Mover up(c, true);
+    c->stage.used = 0;                                   // (the stream is idle between calls)
+    int e = 0;
+    for (int k = 0; k < 3; k++) {
+        const size_t nb = (size_t)blobs[k].off[blobs[k].n];
+        if (d->slots[k].reserve(sizeof(int32_t) * slots[k].size()) || d->bytes[k].reserve(nb + 16) ||
+            d->off[k].reserve(sizeof(int32_t) * off32[k].size()))
+            return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        if ((e = up.copy(d->slots[k].p, slots[k].data(), sizeof(int32_t) * slots[k].size()))) return e;
+        if ((e = up.copy(d->bytes[k].p, blobs[k].bytes, nb))) return e;
+        if ((e = up.copy(d->off[k].p, off32[k].data(), sizeof(int32_t) * off32[k].size()))) return e;
+    }
+    if ((e = up.flush())) return e;
+    HIPTRY(stream_sync(c));                              // nothing of this frame is read after the call
+    HIPTRY(hipGetLastError());
+    c->wd_dicts.push_back(d.get());
+    *out = d.release();
+    return BLANCE_OK;
+}
+
+extern "C" int blance_wire_dict_create(blance_ctx* c, const blance_wire_names* nm, int32_t n_parts, int32_t n_nodes_ext,
+                                       int32_t n_states, blance_wire_dict** out) {
+    return guarded([&]() -> int {
+    if (!c || !nm || !out) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::mutex> g(c->mu);
+    rb_discard(c);
+    return settle(c, wire_dict_locked(c, nm, n_parts, n_nodes_ext, n_states, out));
+    });
+}
+
+extern "C" void blance_wire_dict_destroy(blance_ctx* c, blance_wire_dict* d) {
+    if (!c || !d) return;
+    std::lock_guard<std::mutex> g(c->mu);
+    auto it = std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d);
+    if (it == c->wd_dicts.end()) return;                 // not one of this context's
+    c->wd_dicts.erase(it);
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    delete d;
+}
+
+static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out) {
+    out->n_node_refs = out->n_parts_seen = 0;
+    out->refusal = 0; out->refusal_at = -1;
+    out->device_ms = out->total_ms = 0.0;
+    if (std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d) == c->wd_dicts.end())
+        return fail(BLANCE_ERR_BAD_ARG, "the dictionary is not one of this context's");
+    if (out->capacity < 0 || (!out->nodes && out->capacity > 0)) return fail(BLANCE_ERR_BAD_ARG, "nodes NULL with a capacity, or a negative capacity");
+    const bool count_only = !out->nodes && out->capacity == 0;
+    if (!count_only && (!out->part_kind || !out->off || !out->kind)) return fail(BLANCE_ERR_BAD_ARG, "part_kind, off or kind NULL");
+    if (len > (size_t)INT32_MAX) {                       // before anything is launched
+        out->refusal = kWdDocumentTooLong; out->refusal_at = 0;
+        return fail(BLANCE_ERR_UNSUPPORTED, "refused: a document of 2^31 bytes or more");
+    }
+    const int P = d->n[0], NX = d->n[1], M = d->n[2];
+    const int64_t PM = (int64_t)P * M;
+    HIPTRY(hipSetDevice(c->device));
+    hipStream_t sm = c->stream;
+    WireDecodeParams q;
+    memset(&q, 0, sizeof q);
+    q.len = (int32_t)len;
+    q.tile = c->wd_tile;
+    q.n_tiles = cdiv((int64_t)len, q.tile);
+    q.P = P; q.NX = NX; q.M = M; q.stage = c->wd_stage;
+    const size_t nt = (size_t)q.n_tiles;
+    enum { kDoc, kTb, kQbits, kQuotes, kDepth, kCount, kRec, kClaim, kPartKind, kKind, kOff, kNodes, kRefusal };
+    DevBuf* w = c->wd;
+    if (w[kDoc].reserve(len + 2 * kWdPad) || w[kTb].reserve(4 * (nt + 1)) || w[kQbits].reserve(nt * (size_t)q.tile / 8 + 16) ||
+        w[kQuotes].reserve(4 * (nt + 2)) || w[kDepth].reserve(4 * (nt + 2)) || w[kCount].reserve(4 * (nt + 2)) ||
+        w[kClaim].reserve(4 * ((size_t)P + 1)) || w[kPartKind].reserve((size_t)P + 1) || w[kKind].reserve((size_t)PM + 1) ||
+        w[kOff].reserve(4 * ((size_t)PM + 2)) || w[kRefusal].reserve(256))
+        return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+    q.doc = w[kDoc].as<unsigned char>();
+    q.tb = w[kTb].as<int32_t>(); q.qbits = w[kQbits].as<uint32_t>();
+    q.quotes = w[kQuotes].as<int32_t>(); q.depth = w[kDepth].as<int32_t>(); q.count = w[kCount].as<int32_t>();
+    q.claim = w[kClaim].as<int32_t>(); q.part_kind = w[kPartKind].as<uint8_t>(); q.kind = w[kKind].as<uint8_t>();
+    q.off = w[kOff].as<int32_t>(); q.refusal = w[kRefusal].as<unsigned long long>();
+    const blance_wire_dict& dd = *d;
+    WdTable* tabs[3] = {&q.part, &q.node, &q.state};
+    for (int k = 0; k < 3; k++)
+        *tabs[k] = WdTable{dd.slots[k].as<int32_t>(), dd.mask[k], dd.bytes[k].as<unsigned char>(), dd.off[k].as<int32_t>()};
+    int e = 0;
+    {
+        Mover up(c, true);
+        c->stage.used = 0;                               // (the stream is idle between calls)
+        if ((e = up.copy(w[kDoc].p, json, len))) return e;
+        if ((e = up.flush())) return e;
+    }
+    HIPTRY(hipMemsetAsync(w[kClaim].p, 0, 4 * ((size_t)P + 1), sm));
+    HIPTRY(hipMemsetAsync(w[kPartKind].p, 0, (size_t)P + 1, sm));
+    HIPTRY(hipMemsetAsync(w[kKind].p, 0, (size_t)PM + 1, sm));
+    HIPTRY(hipMemsetAsync(w[kOff].p, 0, 4 * ((size_t)PM + 2), sm));
+    HIPTRY(hipMemsetAsync(w[kRefusal].p, 0xFF, 8, sm));
+    HIPTRY(hipEventRecord(c->ev0, sm));
+    // stage 1: the record starts (a hint: k_wire_decode.h)
+    int32_t R = 0;
+    if (q.n_tiles > 0) {
+        const int wgs = cdiv(q.n_tiles, 256);
+        BLANCE_LAUNCH_NOSYNC(k_wd_tail, wgs, 256, 0, sm, q);
+        BLANCE_LAUNCH_NOSYNC(k_wd_quotes, wgs, 256, 0, sm, q);
+        SCANTRY(q.n_tiles + 1, q.quotes);
+        BLANCE_LAUNCH_NOSYNC(k_wd_walk<0>, wgs, 256, 0, sm, q);
+        SCANTRY(q.n_tiles + 1, q.depth);
+        BLANCE_LAUNCH_NOSYNC(k_wd_walk<1>, wgs, 256, 0, sm, q);
+        SCANTRY(q.n_tiles + 1, q.count);
+        HIPTRY(read_back(c, &R, q.count + q.n_tiles, sizeof R));
+        HIPTRY(stream_sync(c));
+        HIPTRY(hipGetLastError());
+        if (R < 0 || (size_t)R > len) return fail(BLANCE_ERR_DEVICE, "k_wd_walk: a record count outside the document");
+        if (w[kRec].reserve(4 * ((size_t)R + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        q.rec = w[kRec].as<int32_t>();
+        if (R > 0) BLANCE_LAUNCH_NOSYNC(k_wd_walk<2>, wgs, 256, 0, sm, q);
+    }
+    q.R = R;
+    // stage 2, pass 1: every record parsed strictly; kinds and list lengths
+    const int wgs2 = R > 0 ? cdiv(R, kWdRun) : 1;
+    BLANCE_LAUNCH(k_wd_parse<false>, wgs2, kWdRun, (size_t)q.stage, sm, q);
+    SCANTRY((int)(PM + 1), q.off);
+    HIPTRY(hipEventRecord(c->ev1, sm));                  // (recorded again behind pass 2)
+    unsigned long long refusal = 0;
+    int32_t total = 0;
+    HIPTRY(read_back(c, &refusal, q.refusal, sizeof refusal));
+    HIPTRY(read_back(c, &total, q.off + PM, sizeof total));
+    HIPTRY(stream_sync(c));
+    HIPTRY(hipGetLastError());
+    float ms = 0.f;
+    HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    out->device_ms = ms;                                 // stage 1 and pass 1: all there is of a count, a refusal, a capacity error
+    if (refusal != ~0ull) {
+        out->refusal = (int32_t)(refusal & 255u);
+        out->refusal_at = (int64_t)(refusal >> 8);
+        return fail(BLANCE_ERR_UNSUPPORTED, "refused: the document is outside what the device decodes (reason %s%ld: BLANCE_WIRE_REFUSED_*)",
+                    "", (long)out->refusal);             // (fail() formats a string, then a number)
+    }
+    if (total < 0) return fail(BLANCE_ERR_DEVICE, "k_wd_parse: the list lengths overflow");
+    out->n_node_refs = total;
+    out->n_parts_seen = R;
+    if (count_only) return BLANCE_OK;
+    if (out->capacity < (int64_t)total) return fail(BLANCE_ERR_CAPACITY, "the caller's nodes array is too small (see n_node_refs)");
+    // pass 2: the node ids
+    if (w[kNodes].reserve(4 * ((size_t)total + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+    q.nodes = w[kNodes].as<int32_t>();
+    if (total > 0) BLANCE_LAUNCH(k_wd_parse<true>, wgs2, kWdRun, (size_t)q.stage, sm, q);
+    HIPTRY(hipEventRecord(c->ev1, sm));
+    unsigned long long again = 0;
+    HIPTRY(read_back(c, &again, q.refusal, sizeof again));
+    HIPTRY(stream_sync(c));
+    HIPTRY(hipGetLastError());
+    if (again != ~0ull) return fail(BLANCE_ERR_DEVICE, "k_wd_parse: the two passes disagree");
+    {
+        Mover down(c, false);
+        c->stage.used = 0;
+        if ((e = down.copy(out->part_kind, q.part_kind, (size_t)P))) return e;
+        if ((e = down.copy(out->off, q.off, 4 * ((size_t)PM + 1)))) return e;
+        if ((e = down.copy(out->kind, q.kind, (size_t)PM))) return e;
+        if ((e = down.copy(out->nodes, q.nodes, 4 * (size_t)total))) return e;
+        if ((e = down.finish())) return e;
+    }
+    HIPTRY(stream_sync(c));
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    out->device_ms = ms;
+    return BLANCE_OK;
+}
+
+extern "C" int blance_wire_decode_device(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out) {
+    return guarded([&]() -> int {
+    if (!c || !d || !out || (!json && len)) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    rb_discard(c);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int st = settle(c, wire_decode_locked(c, d, json, len, out));
+    out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // whatever the status
+    return st;
     });
 }
 

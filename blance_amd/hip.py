@@ -19,7 +19,8 @@ EXPORTS = ["blance_abi_version", "blance_last_error", "blance_result_capacity", 
            "blance_plan_resident", "blance_download", "blance_calc_moves", "blance_plan_stats_get",
            "blance_comm_unique_id", "blance_comm_init_rccl", "blance_comm_set", "blance_comm_stats",
            "blance_is_emulated", "blance_host_alloc", "blance_host_free", "blance_comm_time_ms", "blance_host_trim",
-           "blance_plan_moves_capacity", "blance_plan_moves_get", "blance_plan_wire_names", "blance_plan_wire_get"]
+           "blance_plan_moves_capacity", "blance_plan_moves_get", "blance_plan_wire_names", "blance_plan_wire_get",
+           "blance_wire_dict_create", "blance_wire_dict_destroy", "blance_wire_decode_device"]
 
 _libs = {}
 
@@ -107,6 +108,14 @@ def load_library(path=None):
         lib.blance_plan_wire_names.argtypes = [C.c_void_p, C.POINTER(abi.WireNames)]
         lib.blance_plan_wire_get.restype = C.c_int
         lib.blance_plan_wire_get.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_double)]
+    if hasattr(lib, "blance_wire_decode_device"):            # likewise: Planner.wire_dict / decode_wire refuse without them
+        lib.blance_wire_dict_create.restype = C.c_int
+        lib.blance_wire_dict_create.argtypes = [C.c_void_p, C.POINTER(abi.WireNames), C.c_int32, C.c_int32, C.c_int32,
+                                                C.POINTER(C.c_void_p)]
+        lib.blance_wire_dict_destroy.restype = None
+        lib.blance_wire_dict_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        lib.blance_wire_decode_device.restype = C.c_int
+        lib.blance_wire_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(abi.WireLists)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
@@ -190,6 +199,38 @@ class HostArena:
 
     def close(self):
         """Kept for callers of the earlier interface: the blocks are owned by the arrays, nothing to release here."""
+
+
+def wire_names_struct(names, node_names, state_names):
+    """abi.WireNames of three lists of names (str, or bytes for names that are no valid UTF-8) and what keeps its arrays alive."""
+    import numpy as np
+    nm, keep = abi.WireNames(), []
+    for field, strs in (("part", names), ("node", node_names), ("state", state_names)):
+        raw = [x if isinstance(x, bytes) else x.encode("utf-8", "surrogatepass") for x in strs]
+        off = np.zeros(len(raw) + 1, dtype=np.int64)
+        if raw:
+            off[1:] = np.cumsum([len(x) for x in raw])
+        blob = b"".join(raw)
+        buf = C.create_string_buffer(blob, len(blob) + 1)
+        keep += [buf, off]
+        setattr(nm, field + "_bytes", C.cast(buf, C.c_void_p).value)
+        setattr(nm, field + "_off", off.ctypes.data)
+    return nm, keep
+
+
+class WireDict:
+    """A blance_wire_dict: the names a document is decoded against (Planner.wire_dict).  Owned by its planner's context:
+    close() destroys it early, closing the planner does at the latest."""
+
+    def __init__(self, planner, handle, part_names, node_names, state_names):
+        self.planner, self._h = planner, handle
+        self.part_names, self.node_names, self.state_names = list(part_names), list(node_names), list(state_names)
+        self.n_parts, self.n_nodes_ext, self.n_states = len(self.part_names), len(self.node_names), len(self.state_names)
+
+    def close(self):
+        if self._h and getattr(self.planner, "_h", None):
+            self.planner.lib.blance_wire_dict_destroy(self.planner._h, self._h)
+        self._h = None
 
 
 class Planner:
@@ -566,6 +607,70 @@ class Planner:
         out = new(max(int(capacity), 1), np.uint8)
         info = call(out.ctypes.data, int(capacity))
         return out[:info["need"]].tobytes(), info
+
+    def wire_dict(self, names, node_names=None, state_names=None):
+        """blance_wire_dict_create(): the dictionary decode_wire decodes against.  names: a problem (its part_names,
+        node_names, state_names), or the partition names with the two other lists beside them; str or bytes.  Independent of
+        the problem the planner holds; it lives until its close() or the planner's."""
+        if not hasattr(self.lib, "blance_wire_dict_create"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_wire_dict_create (build the current sources)")
+        if node_names is None and state_names is None:
+            names, node_names, state_names = names.part_names, names.node_names, names.state_names
+        nm, keep = wire_names_struct(names, node_names, state_names)
+        h = C.c_void_p()
+        self._check(self.lib.blance_wire_dict_create(self._h, C.byref(nm), len(names), len(node_names), len(state_names), C.byref(h)))
+        del keep
+        return WireDict(self, h, names, node_names, state_names)
+
+    def decode_wire(self, wdict, doc, count_only=False, capacity=None, arena=None):
+        """blance_wire_decode_device(): the PartitionMap document `doc` (bytes, or a uint8 numpy array -- one from a HostArena
+        is read by DMA where it lies) decoded on the device against `wdict`, into the layout of prev_* / assign_*.
+        capacity: entries of `nodes` (None: a count-only call first, then exactly n_node_refs -- two calls: the document
+        crosses the bus twice and the record split and the first parse run twice; a caller that decodes at the device's speed
+        passes a capacity it knows, or a bound such as len(doc) // 3); arena: a HostArena for the output arrays.  Returns a dict: part_kind [P], off [P*M + 1], kind [P*M], nodes [n_node_refs] (None each when
+        count_only or refused), n_node_refs, n_parts_seen, refusal (0: accepted, else abi.WIRE_REFUSED's code), refusal_at,
+        device_ms, total_ms.  A refusal is returned, not raised: the caller takes the host decoder
+        (planner.decode_partition_map does).  Every other error status raises; ERR_CAPACITY with the counters in `info`."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_wire_decode_device"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_wire_decode_device (build the current sources)")
+        if isinstance(doc, np.ndarray):
+            src = np.ascontiguousarray(doc).view(np.uint8).reshape(-1)
+            ptr, n = src.ctypes.data, int(src.size)
+        else:
+            src = bytes(doc)
+            ptr, n = C.cast(C.c_char_p(src), C.c_void_p).value, len(src)
+        P, M = wdict.n_parts, wdict.n_states
+
+        def call(arrays, cap):
+            wl = abi.WireLists()
+            if arrays is not None:
+                wl.part_kind, wl.off, wl.kind, wl.nodes = [a.ctypes.data for a in arrays]
+            wl.capacity = cap
+            st = self.lib.blance_wire_decode_device(self._h, wdict._h, ptr, n, C.byref(wl))
+            info = {"n_node_refs": int(wl.n_node_refs), "n_parts_seen": int(wl.n_parts_seen), "refusal": int(wl.refusal),
+                    "refusal_at": int(wl.refusal_at), "device_ms": float(wl.device_ms), "total_ms": float(wl.total_ms)}
+            if st != abi.OK and not (st == abi.ERR_UNSUPPORTED and wl.refusal != 0):
+                err = BlanceError(st, (self.lib.blance_last_error() or b"").decode())
+                err.info = info if st == abi.ERR_CAPACITY else None
+                raise err
+            return info
+
+        none = {"part_kind": None, "off": None, "kind": None, "nodes": None}
+        if count_only:
+            return dict(none, **call(None, 0))
+        if capacity is None:
+            first = call(None, 0)
+            if first["refusal"]:
+                return dict(none, **first)
+            capacity = first["n_node_refs"]
+        new = (lambda k, dt: np.empty(k, dtype=dt)) if arena is None else arena.empty
+        arrays = [new(max(P, 1), np.uint8), new(P * M + 1, np.int32), new(max(P * M, 1), np.uint8), new(max(int(capacity), 1), np.int32)]
+        info = call(arrays, int(capacity))
+        if info["refusal"]:
+            return dict(none, **info)
+        return dict({"part_kind": arrays[0][:P], "off": arrays[1], "kind": arrays[2][:P * M],
+                     "nodes": arrays[3][:info["n_node_refs"]]}, **info)
 
     def calc_moves(self, n_states, favor_min_nodes, beg_off, beg_nodes, end_off, end_nodes):
         """blance_calc_moves(): CalcPartitionMoves for every partition (CSR over

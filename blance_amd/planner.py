@@ -203,6 +203,76 @@ def _beg_other(fp, prevMap):
     return np.asarray(off, dtype=np.int32), np.asarray(nodes, dtype=np.int32)
 
 
+def lists_of_wire_map(wm, wdict):
+    """The host route to what Planner.decode_wire returns: a map the host decoder made (wire.decode) carried over from its
+    first-seen ids to the ids of the dictionary `wdict`, in the layout of prev_* / assign_* (part_kind [P], off [P*M + 1],
+    kind [P*M], nodes).  Also names_differ [P]: the partition's Name is not its key (the device refuses such a document).
+    Raises problem.Unsupported for what the arrays cannot hold: a nil map, a nil partition, a name outside the dictionary."""
+    import numpy as np
+    if wm.map_is_nil:
+        raise problem.Unsupported("the document is null (a nil PartitionMap)")
+    P, M = wdict.n_parts, wdict.n_states
+    ids = getattr(wdict, "_ids", None)
+    if ids is None:
+        as_bytes = lambda names: {(x if isinstance(x, bytes) else x.encode("utf-8", "surrogatepass")): i for i, x in enumerate(names)}   # noqa: E731
+        ids = wdict._ids = (as_bytes(wdict.part_names), as_bytes(wdict.node_names), as_bytes(wdict.state_names))
+
+    def carry(names, table, what):
+        try:
+            return np.asarray([table[x] for x in names], dtype=np.int64)
+        except KeyError as e:
+            raise problem.Unsupported("%s %r is not in the dictionary" % (what, e.args[0]))
+
+    keys = wm.keys()
+    pid = carry(keys, ids[0], "partition")
+    node_id = carry(wm.nodes(), ids[1], "node")
+    state_id = carry(wm.states(), ids[2], "state")
+    if (wm.part_kind == 0).any():
+        raise problem.Unsupported("a nil *Partition in the document")
+    part_kind = np.zeros(P, dtype=np.uint8)
+    part_kind[pid] = wm.part_kind
+    names_differ = np.zeros(P, dtype=bool)
+    names_differ[pid] = [k != n for k, n in zip(keys, wm.names())]
+    n_entries = len(wm.entry_state)
+    part_of = np.repeat(np.arange(len(keys)), np.diff(wm.part_off))
+    slot = pid[part_of] * M + state_id[wm.entry_state] if n_entries else np.zeros(0, dtype=np.int64)
+    lens_e = np.diff(wm.entry_off)
+    kind = np.zeros(P * M, dtype=np.uint8)
+    kind[slot] = wm.entry_kind
+    lens = np.zeros(P * M, dtype=np.int64)
+    lens[slot] = lens_e
+    off = np.zeros(P * M + 1, dtype=np.int32)
+    off[1:] = np.cumsum(lens)
+    order = np.argsort(slot, kind="stable")
+    ln = lens_e[order]
+    total = int(ln.sum())
+    begin = np.cumsum(ln) - ln
+    src = np.repeat(wm.entry_off[:-1][order] - begin, ln) + np.arange(total)
+    nodes = node_id[wm.entry_nodes[src]].astype(np.int32) if total else np.zeros(0, dtype=np.int32)
+    return {"part_kind": part_kind, "off": off, "kind": kind, "nodes": nodes, "names_differ": names_differ,
+            "n_node_refs": total, "n_parts_seen": len(keys)}
+
+
+def decode_partition_map(planner, wdict, doc):
+    """A PartitionMap document as the lists blance_problem takes for prev_* / assign_*: decoded on the device
+    (Planner.decode_wire); a document the device refuses -- it is outside the device's subset, or no valid document -- goes
+    to the host decoder (wire.decode, which raises wire.WireError for a syntax or type error) and lists_of_wire_map.  Returns
+    the arrays of decode_wire, names_differ, and route: "device" or "host" (then with the device's refusal).  The device is
+    asked twice, for the count and then for the lists (decode_wire with capacity=None): simple, not the fastest way in."""
+    import numpy as np
+    from . import wire
+    got = (planner or default_planner()).decode_wire(wdict, doc)
+    if not got["refusal"]:
+        return dict(got, names_differ=np.zeros(wdict.n_parts, dtype=bool), route="device")
+    wm = wire.decode(doc.tobytes() if hasattr(doc, "tobytes") else doc)
+    try:
+        out = lists_of_wire_map(wm, wdict)
+    finally:
+        wm.close()
+    return dict(out, refusal=got["refusal"], refusal_at=got["refusal_at"], device_ms=got["device_ms"],
+                total_ms=got["total_ms"], route="host")
+
+
 def PlanNextMap(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model,
                 modelStateConstraints=None, partitionWeights=None, stateStickiness=None, nodeWeights=None,
                 nodeHierarchy=None, hierarchyRules=None, planner=None):

@@ -365,6 +365,86 @@ int blance_plan_wire_names(blance_ctx* ctx, const blance_wire_names* names);
  * blance_plan_moves_get and blance_plan_resident behave after it as without it) and makes no collective. */
 int blance_plan_wire_get(blance_ctx* ctx, char* buf, size_t cap, size_t* need, double* device_ms);
 
+/* ---- a PartitionMap document decoded on the device (additive to ABI 6: look the symbols up before use) ----
+ * The way in that mirrors blance_plan_wire_get: json.Unmarshal(document, &PartitionMap{}) against a DICTIONARY of names
+ * given beforehand, straight into the id space and the layout blance_problem uses for prev_* and assign_* -- a caller points
+ * prev_off / prev_nodes / prev_kind at the output (part_in_prev[p] = part_kind[p] != BLANCE_LIST_ABSENT) and calls
+ * blance_upload.
+ *
+ * Exact or refused, never guessed.  BLANCE_OK only when the document is valid JSON of the shape in blance_wire.h AND lies
+ * inside the subset below; the result then equals what blance_wire_decode gives after mapping its names to the dictionary's
+ * ids.  Everything else is a REFUSAL: BLANCE_ERR_UNSUPPORTED, a reason code in `refusal`, the byte offset of the record or
+ * token that caused it in `refusal_at` (the smallest (offset, reason) of all there are), nothing written to the caller's
+ * arrays.  The caller then takes the host decoder, which reports syntax and type errors as before.  The device never
+ * accepts a document the host decoder rejects or decodes differently.
+ * Inside the subset: JSON whitespace anywhere between tokens; partitions, the two fields of a partition and the state keys
+ * in any order; strings with any valid escape (\" \\ \/ \b \f \n \r \t, \uXXXX incl. valid surrogate pairs), compared
+ * UNESCAPED with the raw names of the dictionary; bytes >= 0x80 that are well-formed UTF-8; nodesByState null or missing
+ * (both: BLANCE_LIST_NIL in part_kind); a state's list null, [] or a list of known node names, duplicates kept; partitions
+ * of the dictionary missing from the document; `{}`.  One limit of SIZE belongs to the subset, because one device thread
+ * parses one record: every record (a key, its value and the whitespace up to the next key) is shorter than 1 MiB, and so
+ * are the bytes in front of the first record and the whitespace behind the closing brace.  What is longer is refused
+ * (BLANCE_WIRE_REFUSED_RECORD_TOO_LONG, at the record's offset; at 0 for the bytes in front of the first record, at the
+ * last record's offset for the whitespace behind the document), and the whole document is shorter than 2^31 bytes.
+ * Refused (BLANCE_WIRE_REFUSED_*): see the codes.  The host decoder accepts some of these with Go's semantics (a repeated
+ * key replaces, a field matches case-insensitively, an unknown field is skipped, U+FFFD for bad UTF-8).
+ *
+ * The dictionary (device hash tables over the names and the raw names) is independent of whatever problem the context
+ * holds -- the call is made to BUILD the problem -- and survives blance_upload / blance_plan; it is owned by the context and
+ * goes with it at the latest.  n_parts / n_nodes_ext / n_states: the names' counts (names->*_off hold one more).  Errors:
+ * BLANCE_ERR_BAD_ARG for a NULL argument, a negative count, offsets that do not start at 0 or are not monotone, two states
+ * or two nodes with one name, n_parts * n_states of 2^31 - 1 or more; BLANCE_ERR_UNSUPPORTED for two partitions with one
+ * name and for a blob of 2^31 bytes or more.
+ *
+ * blance_wire_decode_device: `json` in blance_host_alloc memory is read by DMA where it lies, any other buffer through the
+ * context's staging buffer.  Count only: nodes == NULL and capacity == 0 -- n_node_refs and n_parts_seen are written and no
+ * array is (part_kind, off and kind may then be NULL too).  A capacity below n_node_refs: BLANCE_ERR_CAPACITY with
+ * n_node_refs and n_parts_seen written and no array touched.  BLANCE_ERR_BAD_ARG, nothing launched: a NULL ctx, dictionary,
+ * out or (with len > 0) json; a dictionary of another context; nodes NULL with capacity > 0 or capacity < 0; part_kind, off
+ * or kind NULL while nodes is given.  The call holds the context's lock and leaves the context as it found it:
+ * blance_plan_resident, blance_download, blance_plan_stats_get, blance_plan_moves_get and blance_plan_wire_get answer after
+ * it as without it.  It makes no collective. */
+#define BLANCE_WIRE_REFUSED_GRAMMAR             1  /* not JSON (also: a document that ends early)                       */
+#define BLANCE_WIRE_REFUSED_TYPE                2  /* a JSON value of another type than the shape has there             */
+#define BLANCE_WIRE_REFUSED_NULL_DOCUMENT       3  /* the document is `null` (a nil PartitionMap)                       */
+#define BLANCE_WIRE_REFUSED_UNKNOWN_PARTITION   4  /* a key that is not a partition name of the dictionary              */
+#define BLANCE_WIRE_REFUSED_UNKNOWN_STATE       5
+#define BLANCE_WIRE_REFUSED_UNKNOWN_NODE        6
+#define BLANCE_WIRE_REFUSED_REPEATED_PARTITION  7  /* offset: the second record with that key                           */
+#define BLANCE_WIRE_REFUSED_REPEATED_STATE      8
+#define BLANCE_WIRE_REFUSED_REPEATED_FIELD      9
+#define BLANCE_WIRE_REFUSED_UNKNOWN_FIELD      10  /* a field name that is not exactly name or nodesByState             */
+#define BLANCE_WIRE_REFUSED_NULL_PARTITION     11
+#define BLANCE_WIRE_REFUSED_NAME_MISSING       12  /* offset: the record                                                */
+#define BLANCE_WIRE_REFUSED_NAME_DIFFERS       13  /* name is not the key (or null)                                     */
+#define BLANCE_WIRE_REFUSED_NULL_ELEMENT       14  /* null inside a state's list                                        */
+#define BLANCE_WIRE_REFUSED_INVALID_UTF8       15
+#define BLANCE_WIRE_REFUSED_UNPAIRED_SURROGATE 16
+#define BLANCE_WIRE_REFUSED_CONTROL_CHARACTER  17  /* a raw byte below 0x20 inside a string                             */
+#define BLANCE_WIRE_REFUSED_RECORD_TOO_LONG    18  /* one partition's record (or the space around it) of 1 MiB or more  */
+#define BLANCE_WIRE_REFUSED_DOCUMENT_TOO_LONG  19  /* 2^31 bytes or more: refused before anything is launched           */
+
+typedef struct blance_wire_dict blance_wire_dict;   /* opaque; owned by the context it was made on */
+int  blance_wire_dict_create(blance_ctx* ctx, const blance_wire_names* names, int32_t n_parts, int32_t n_nodes_ext,
+                             int32_t n_states, blance_wire_dict** out);
+void blance_wire_dict_destroy(blance_ctx* ctx, blance_wire_dict* dict);
+
+typedef struct blance_wire_lists {
+    uint8_t* part_kind;   /* [P]  BLANCE_LIST_ABSENT: key not in the document; NIL: nil nodesByState; SET: a map */
+    int32_t* off;         /* [P*M + 1]  CSR over (p * M + state), as prev_off */
+    uint8_t* kind;        /* [P*M]      BLANCE_LIST_*, as prev_kind */
+    int32_t* nodes;       /* [capacity] node ids in list order, as prev_nodes */
+    int64_t  capacity;    /* in */
+    int64_t  n_node_refs, n_parts_seen;       /* out, also with BLANCE_ERR_CAPACITY */
+    int32_t  refusal;     /* out: BLANCE_WIRE_REFUSED_*, 0 when accepted */
+    int64_t  refusal_at;  /* out: byte offset, -1 when accepted */
+    double   device_ms, total_ms;             /* out: the kernels of the call (of a count, a refusal or a capacity error:
+                                                 the record split and the first parse; 0 when the call ends before that);
+                                                 the whole call incl. the copies, whatever the status */
+} blance_wire_lists;
+int blance_wire_decode_device(blance_ctx* ctx, const blance_wire_dict* dict, const char* json, size_t len,
+                              blance_wire_lists* out);
+
 /* ---- one plan on several GPUs (BASELINE.json config 4) ------------------------------------
  * The steps of a state pass that runs as region chains (one chain per hierarchy region)
  * shard over the ranks by region: every rank holds the whole problem (upload the same problem on
