@@ -141,7 +141,10 @@ __global__ void k_period_segments(int B, int cut, const int32_t* reg_off, int32_
 // verdict with the third segment -- behind `limit` if so, behind 2T if not -- and, if so, the counters behind the copied
 // stretch: d per full period on every live leaf, and the picks of the stretch's last, partial period one by one.  Those
 // are read from `out` of steps [T, 2T), which the second walk wrote and k_period_replicate leaves alone: this kernel may
-// run before it.  Everything here belongs to the region -- its leaves' counters, its chain's outputs, its words of pb --
+// run before it, each with the weight of its own record (word 1 of step T + j, which is step 2T + full * T + j's: the records
+// repeat) -- weights may differ inside a period while d is uniform (64 leaves taken in turn, 64 steps of weight 1 and 64 of
+// weight 2: d = 3), and the count does not rest on the pass order keeping a chain to one weight: k_pass_chain_blank takes the
+// weight per batch of steps, and the sort by weight is the caller's, not this kernel's.  Everything here belongs to the region -- its leaves' counters, its chain's outputs, its words of pb --
 // and the workgroup is the only one that touches it.  The workgroup loops over the leaves when there are more than threads.
 // (A leaf that is no candidate never moves: one that did refutes the region.  flags[kFlagEscaped]: a chain of the walks so
 // far had to escape -- it published nothing, the host will redo the whole pass with k_pass_chain from the saved counters:
@@ -189,13 +192,13 @@ __global__ void k_period_judge(int B, int s, int N, int NX, int OW, const int32_
         if (n >= 0 && n < N && alive[n]) cnt[s * NX + n] += d * full;
     }
     __syncthreads();
-    const int w0 = crec[(size_t)cbeg * kCW + 1];
     for (int j = tid; j < rest; j += (int)blockDim.x) {
         const int32_t* o = out + (size_t)(cbeg + T + j) * OW;
+        const int w = crec[(size_t)(cbeg + T + j) * kCW + 1];      // the step's own weight
         const int n_out = o[0] & 0xffff;
         for (int c = 0; c < n_out; c++) {
             const int n = o[1 + c];
-            if (n >= 0 && n < NX) atomicAdd(cnt + s * NX + n, w0);
+            if (n >= 0 && n < NX) atomicAdd(cnt + s * NX + n, w);
         }
     }
 }

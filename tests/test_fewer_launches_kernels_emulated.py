@@ -227,8 +227,8 @@ def test_period_judge(lib, threads, escaped):
             out[t * OW] = k | (3 << 16)              # (the kernel reads the low half of the word)
             out[t * OW + 1:t * OW + 1 + k] = rng.choice(nodes, size=k)
     crec = _i32(np.full(steps * CW, -1))
-    for rg in regions:
-        crec[rg["cbeg"] * CW + 1] = w0
+    for rg in regions:                               # (every record has its weight: the kernel counts a step with its own)
+        crec[rg["cbeg"] * CW + 1:rg["cend"] * CW:CW] = w0
     flags = np.zeros(CHAIN_FLAGS, dtype=np.int32)
     flags[FLAG_ESCAPED] = escaped
     want_cnt, want_pb = cnt.copy(), pb.copy()
