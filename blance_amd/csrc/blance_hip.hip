@@ -27,6 +27,7 @@
 #include "k_plan_wire.h"
 #include "k_wire_decode.h"
 #include "host/json_escape.hpp"
+#include "host/problem_facts.hpp"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
 #include "tu_seq.hip"
 #include "tu_tree.hip"
@@ -252,6 +253,7 @@ struct blance_wire_dict {
     DevBuf slots[3], bytes[3], off[3];
 };
 
+struct Mover;
 enum PassKind { kPassKernel = 0, kPassFlatBulk = 1, kPassBlank = 2, kPassStayTop = 3 };   // what ran a state pass (statistics)
 
 struct blance_ctx : CtxHandles {
@@ -279,18 +281,18 @@ struct blance_ctx : CtxHandles {
     // rounds only, when at least this many steps remain; k_stay_by_top checks the rest.  0: off (BLANCE_CHAIN_HANDOFF=0|<n>).
     int chain_handoff = kChainHandoffMin;
     DevBuf handoff;                 // [regions] chain index of the first step a region's walk did not do
-    bool no_stay_top = false;       // test knob (& 64): never k_stay_by_top
-    bool force_stay_top = false;    // test knob (& 128): try k_stay_by_top in every chain pass with NumPartitions > 0
-    bool periodic = true;           // an all-blank chain pass with periodic records walks two periods (k_period.h); off: & 256, or BLANCE_PERIODIC=0
+    bool no_stay_top = false;       // test knob (kKnobNoStayTop): never k_stay_by_top
+    bool force_stay_top = false;    // test knob (kKnobForceStayTop): try k_stay_by_top in every chain pass with NumPartitions > 0
+    bool periodic = true;           // an all-blank chain pass with periodic records walks two periods (k_period.h); off: kKnobNoPeriodic, or BLANCE_PERIODIC=0
     int periodic_cut = 0;           // test knob BLANCE_PERIODIC_CUT (k_period_segments)
     // the periodic pass behind a round robin takes its period from the upload, not from a search (k_period_find's known
-    // mode); off: & 65536, or BLANCE_PERIOD_KNOWN=0.  What the upload contributes:
+    // mode); off: kKnobNoPeriodKnown, or BLANCE_PERIOD_KNOWN=0.  What the upload contributes:
     bool period_known = true;
     uint32_t assign_kinds = 0;      // k_validate_parts: bit m -- some list to assign of state m is absent, bit 16 + m -- some is not
     bool cycle_order_stands = false; // sweep 1's second pass runs in the order of its first (one partitionSorter category in both)
     bool leaves_distinct = false;   // no two nodes share a leaf of the hierarchy
     // The chain pass behind a round robin takes its grouping by region and k_stay_by_top's work list from tables of the upload
-    // (k_cycle.h, RuleRegions::cyc), not from two counting sorts.  0: off (& 131072, or BLANCE_CYCLE_GROUP=0); 2: the test knob
+    // (k_cycle.h, RuleRegions::cyc), not from two counting sorts.  0: off (kKnobNoCycleGroup, or BLANCE_CYCLE_GROUP=0); 2: the test knob
     // BLANCE_CYCLE_GROUP=refute -- the kernel's check of the premise fails for step 0, the pass goes in order.
     int cycle_group = 1;
     int64_t cycle_group_epoch = -1; // the count of regroupings at which the grouping by region was taken from those tables (-1: it was not)
@@ -348,19 +350,19 @@ struct blance_ctx : CtxHandles {
     int chain_min_parts = 2048;
     int any_node_weight = 0;
     bool no_fast_keys = false;      // a chain left the packed keys' range during this pass
-    bool no_seq_spec = false;       // test knob (options.reserved[2] & 1): k_pass_seq without stay speculation
-    bool no_tree = false;           // test knob (& 2): flat passes never on k_pass_tree
-    bool tree_dense = false;        // test knob (& 4): k_pass_tree scores every node in every general step
-    bool tree_always = false;       // test knob (& 8): k_pass_tree even when a k_pass_seq workgroup size is forced
-    bool tree_long = false;         // test knob (& 16): k_pass_tree decodes the record in every general step
-    bool no_planes = false;         // test knob (& 32): the all-blank chain pass on k_pass_chain_blank, not k_pass_chain_planes
-    bool no_queue = false;          // test knob (& 512): flat passes with k <= 2 on k_pass_tree, never on k_pass_queue
-    bool queue_general = false;     // test knob (& 1024): k_pass_queue without its lean walk
-    bool queue_no_asm = false;      // test knob (& 4096): k_pass_queue's lean walk as compiled C++ only
-    bool queue_force_dense = false; // test knob (& 2048): every general step of k_pass_queue scores every node
-    bool queue_exact_rebuild = false; // test knob (& 8192): k_pass_queue's window always rebuilt by the exact selection
-    bool queue_bits_self = false;   // test knob (& 32768): k_pass_queue's walking wave copies the row bit maps itself (no helper)
-    bool shard_one_rank = false;    // test knob (& 16384): a communicator of ONE rank takes the sharded branch of a chain pass, so that
+    bool no_seq_spec = false;       // test knob (kKnobNoSeqSpec): k_pass_seq without stay speculation
+    bool no_tree = false;           // test knob (kKnobNoTree): flat passes never on k_pass_tree
+    bool tree_dense = false;        // test knob (kKnobTreeDense): k_pass_tree scores every node in every general step
+    bool tree_always = false;       // test knob (kKnobTreeAlways): k_pass_tree even when a k_pass_seq workgroup size is forced
+    bool tree_long = false;         // test knob (kKnobTreeLong): k_pass_tree decodes the record in every general step
+    bool no_planes = false;         // test knob (kKnobNoPlanes): the all-blank chain pass on k_pass_chain_blank, not k_pass_chain_planes
+    bool no_queue = false;          // test knob (kKnobNoQueue): flat passes with k <= 2 on k_pass_tree, never on k_pass_queue
+    bool queue_general = false;     // test knob (kKnobQueueGeneral): k_pass_queue without its lean walk
+    bool queue_no_asm = false;      // test knob (kKnobQueueNoAsm): k_pass_queue's lean walk as compiled C++ only
+    bool queue_force_dense = false; // test knob (kKnobQueueForceDense): every general step of k_pass_queue scores every node
+    bool queue_exact_rebuild = false; // test knob (kKnobQueueExactRebuild): k_pass_queue's window always rebuilt by the exact selection
+    bool queue_bits_self = false;   // test knob (kKnobQueueBitsSelf): k_pass_queue's walking wave copies the row bit maps itself (no helper)
+    bool shard_one_rank = false;    // test knob (kKnobShardOneRank): a communicator of ONE rank takes the sharded branch of a chain pass, so that
                                     // both collectives really execute (ncclAllReduce / ncclAllGather on a one-GPU box)
     DevBuf ntn_bits;                // k_pass_queue: one bit per nodeToNodeCounts entry, zeroed with the matrix
     bool bits_stale = false;        // another kernel bumped the matrix in this pass: k_ntn_bits before k_pass_queue goes on
@@ -380,6 +382,7 @@ struct blance_ctx : CtxHandles {
         bool cyc_ok = false;
         DevBuf cyc, cyc_reg_off, cyc_top_off;   // [n_alive][kCycWords], [n_regions + 1], [n_leaves + 1]
         std::vector<int32_t> h_cyc_reg_off;     // the host's copy of the chain offsets
+        int put(Mover& up, const RuleTables& t, int leaves);   // the analysis of host/problem_facts.hpp, onto the device
     };
     std::vector<RuleRegions> rule_regions;
     DevBuf leaf_node, regid, chain_order, bucket_counts, reg_off, cnt_save, crec;
@@ -568,6 +571,53 @@ extern "C" int blance_validate(const blance_problem* pb) {
     });
 }
 
+// The test knobs of blance_options::reserved[2] and the environment variables a context reads once, when it is made.
+// (BLANCE_NO_UNIFORM_CATEGORY is read by every upload, BLANCE_QUEUE_STATS at the end of every plan.)
+enum TestKnob : uint32_t {
+    kKnobNoSeqSpec = 1, kKnobNoTree = 2, kKnobTreeDense = 4, kKnobTreeAlways = 8, kKnobTreeLong = 16, kKnobNoPlanes = 32,
+    kKnobNoStayTop = 64, kKnobForceStayTop = 128, kKnobNoPeriodic = 256, kKnobNoQueue = 512, kKnobQueueGeneral = 1024,
+    kKnobQueueForceDense = 2048, kKnobQueueNoAsm = 4096, kKnobQueueExactRebuild = 8192, kKnobShardOneRank = 16384,
+    kKnobQueueBitsSelf = 32768, kKnobNoPeriodKnown = 65536, kKnobNoCycleGroup = 131072,
+};
+static void read_knobs(const blance_options* opt, blance_ctx* c) {
+    const uint32_t bits = opt ? (uint32_t)opt->reserved[2] : 0;
+    auto on = [bits](TestKnob k) { return (bits & k) != 0; };
+    auto env_int = [](const char* name, int* v) { const char* e = getenv(name); if (e) *v = atoi(e); return e != nullptr; };
+    auto clamp = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
+    int v = 0;
+    c->no_seq_spec = on(kKnobNoSeqSpec);
+    c->no_tree = on(kKnobNoTree);
+    c->tree_dense = on(kKnobTreeDense);
+    c->tree_always = on(kKnobTreeAlways);
+    c->tree_long = on(kKnobTreeLong);
+    c->no_planes = on(kKnobNoPlanes);
+    c->no_queue = on(kKnobNoQueue);
+    c->queue_general = on(kKnobQueueGeneral);
+    c->queue_force_dense = on(kKnobQueueForceDense);
+    c->queue_no_asm = on(kKnobQueueNoAsm);
+    c->queue_exact_rebuild = on(kKnobQueueExactRebuild);
+    c->shard_one_rank = on(kKnobShardOneRank);
+    c->queue_bits_self = on(kKnobQueueBitsSelf);
+    c->no_stay_top = on(kKnobNoStayTop);
+    c->force_stay_top = on(kKnobForceStayTop);
+    c->periodic = !on(kKnobNoPeriodic);
+    if (env_int("BLANCE_PERIODIC", &v)) c->periodic = v != 0;                  // BLANCE_PERIODIC=0: the way out
+    (void)env_int("BLANCE_PERIODIC_CUT", &c->periodic_cut);
+    c->period_known = !on(kKnobNoPeriodKnown);
+    if (env_int("BLANCE_PERIOD_KNOWN", &v)) c->period_known = v != 0;
+    c->cycle_group = on(kKnobNoCycleGroup) ? 0 : 1;
+    if (const char* cg = getenv("BLANCE_CYCLE_GROUP")) c->cycle_group = !strcmp(cg, "refute") ? 2 : atoi(cg) != 0;
+    c->trace = getenv("BLANCE_TRACE") != nullptr;
+    (void)env_int("BLANCE_CHAIN_WAVES", &c->chain_waves);
+    if (env_int("BLANCE_CHAIN_HANDOFF", &v)) c->chain_handoff = v > 0 ? v : 0;   // 0: the way out; n: hand off n steps or more
+    if (const char* sp = getenv("BLANCE_SPECULATE")) c->speculate = !strcmp(sp, "fail") ? 2 : atoi(sp) != 0;   // 0: every decision read back first
+    if (env_int("BLANCE_FUSED_TAIL", &v)) c->fused_tail = v != 0;               // BLANCE_FUSED_TAIL=0: the unfused tail
+    (void)env_int("BLANCE_DUMP_SWEEP", &c->dump_sweep);
+    if (env_int("BLANCE_WIRE_STAGE", &v)) c->wire_stage = clamp(v, kWireStageMin, kWireStageMax);
+    if (env_int("BLANCE_WIRE_IN_TILE", &v)) c->wd_tile = clamp(v & ~63, kWdTileMin, kWdTileMax);
+    if (env_int("BLANCE_WIRE_IN_STAGE", &v)) c->wd_stage = clamp(v & ~15, kWdStageMin, kWdStageMax);
+}
+
 extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     if (!out) return fail(BLANCE_ERR_BAD_ARG, "null out");
     *out = nullptr;
@@ -582,46 +632,7 @@ extern "C" int blance_ctx_create(const blance_options* opt, blance_ctx** out) {
     c->engine = opt ? opt->engine : BLANCE_ENGINE_AUTO;
     c->force_threads = opt ? opt->reserved[0] : 0;
     if (opt && opt->reserved[1] > 0) c->chain_min_parts = opt->reserved[1];
-    c->no_seq_spec = opt && (opt->reserved[2] & 1);
-    c->no_tree = opt && (opt->reserved[2] & 2);
-    c->tree_dense = opt && (opt->reserved[2] & 4);
-    c->tree_always = opt && (opt->reserved[2] & 8);
-    c->tree_long = opt && (opt->reserved[2] & 16);
-    c->no_planes = opt && (opt->reserved[2] & 32);
-    c->no_queue = opt && (opt->reserved[2] & 512);
-    c->queue_general = opt && (opt->reserved[2] & 1024);
-    c->queue_force_dense = opt && (opt->reserved[2] & 2048);
-    c->queue_no_asm = opt && (opt->reserved[2] & 4096);
-    c->queue_exact_rebuild = opt && (opt->reserved[2] & 8192);
-    c->shard_one_rank = opt && (opt->reserved[2] & 16384);
-    c->queue_bits_self = opt && (opt->reserved[2] & 32768);
-    c->no_stay_top = opt && (opt->reserved[2] & 64);
-    c->force_stay_top = opt && (opt->reserved[2] & 128);
-    c->periodic = !(opt && (opt->reserved[2] & 256));
-    if (const char* pe = getenv("BLANCE_PERIODIC")) c->periodic = atoi(pe) != 0;      // BLANCE_PERIODIC=0: the way out
-    if (const char* pc = getenv("BLANCE_PERIODIC_CUT")) c->periodic_cut = atoi(pc);
-    c->period_known = !(opt && (opt->reserved[2] & 65536));
-    if (const char* pk = getenv("BLANCE_PERIOD_KNOWN")) c->period_known = atoi(pk) != 0;
-    c->cycle_group = opt && (opt->reserved[2] & 131072) ? 0 : 1;
-    if (const char* cg = getenv("BLANCE_CYCLE_GROUP")) c->cycle_group = !strcmp(cg, "refute") ? 2 : atoi(cg) != 0;
-    c->trace = getenv("BLANCE_TRACE") != nullptr;
-    if (const char* cw = getenv("BLANCE_CHAIN_WAVES")) c->chain_waves = atoi(cw);
-    if (const char* ho = getenv("BLANCE_CHAIN_HANDOFF")) c->chain_handoff = atoi(ho) > 0 ? atoi(ho) : 0;   // 0: the way out; n: hand off n steps or more
-    if (const char* sp = getenv("BLANCE_SPECULATE")) c->speculate = !strcmp(sp, "fail") ? 2 : atoi(sp) != 0;   // 0: every decision read back first
-    if (const char* ft = getenv("BLANCE_FUSED_TAIL")) c->fused_tail = atoi(ft) != 0;      // BLANCE_FUSED_TAIL=0: the unfused tail
-    if (const char* ds = getenv("BLANCE_DUMP_SWEEP")) c->dump_sweep = atoi(ds);
-    if (const char* ws = getenv("BLANCE_WIRE_STAGE")) {
-        const int v = atoi(ws);
-        c->wire_stage = v < kWireStageMin ? kWireStageMin : v > kWireStageMax ? kWireStageMax : v;
-    }
-    if (const char* wt = getenv("BLANCE_WIRE_IN_TILE")) {
-        const int v = atoi(wt) & ~63;
-        c->wd_tile = v < kWdTileMin ? kWdTileMin : v > kWdTileMax ? kWdTileMax : v;
-    }
-    if (const char* wi = getenv("BLANCE_WIRE_IN_STAGE")) {
-        const int v = atoi(wi) & ~15;
-        c->wd_stage = v < kWdStageMin ? kWdStageMin : v > kWdStageMax ? kWdStageMax : v;
-    }
+    read_knobs(opt, c);
     if (hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
         hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreate(&c->side_go) != hipSuccess || hipEventCreate(&c->side_done) != hipSuccess) {
@@ -687,6 +698,24 @@ static int settle(blance_ctx* c, int st) {
         rb_discard(c);
     }
     return st;
+}
+
+// Every entry point that takes a context runs its body through here (all but create, destroy and the communicator's
+// setters, which enqueue nothing): one call at a time on a context, no read-back left over from the call before, and
+// never a return with copies in flight -- not with an error status, not behind an exception either.
+template <class F>
+static int enter(blance_ctx* c, F f) {
+    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> g(c->mu);
+        rb_discard(c);
+        try {
+            return settle(c, f());
+        } catch (...) {
+            (void)settle(c, BLANCE_ERR_DEVICE);
+            throw;                                   // (guarded names it)
+        }
+    });
 }
 
 // ---- host <-> device copies.  An array in page-locked memory (blance_host_alloc, or registered by the caller) is copied by
@@ -801,54 +830,50 @@ static int run_fill_copy(blance_ctx* c, FillCopyJob& j) {
     return 0;
 }
 
-static int upload_inner(blance_ctx* c, const blance_problem* pb);
-// copies may still be reading the caller's arrays (and the staging buffer) when an
-// error cuts the upload short: never return with copies in flight
-static int upload_locked(blance_ctx* c, const blance_problem* pb) {
-    rb_discard(c);                                   // (left behind by a call that ended in an exception)
-    return settle(c, upload_inner(c, pb));
+// The tables of one rule on their way to the device.  `t` (and the LeafTables n_leaves comes from) must outlive the next
+// up.flush(): a big array is only noted here and copied into the staging buffer there.  upload_rule_tables keeps that rule
+// for every vector of host/problem_facts.hpp; nothing else in the upload hands the Mover memory of a shorter life.
+int blance_ctx::RuleRegions::put(Mover& up, const RuleTables& t, int leaves) {
+    ok = t.ok;
+    n_regions = t.n_regions;
+    max_size = t.max_size;
+    n_leaves = leaves;
+    cls_run = t.cls_run;
+    n_stay_wgs = t.n_stay_wgs;
+    cyc_ok = t.cyc_ok;
+    if (cyc_ok) h_cyc_reg_off = t.cyc_reg_off;
+    struct { DevBuf* b; const std::vector<int32_t>* v; bool on; } rows[] = {
+        {&wg_region, &t.wg_region, ok}, {&wg_chunk, &t.wg_chunk, ok}, {&node_region, &t.node_region, ok},
+        {&reg_lo, &t.reg_lo, ok}, {&reg_hi, &t.reg_hi, ok}, {&leaf_cls, &t.leaf_cls, ok}, {&cls_size, &t.cls_size, ok},
+        {&cyc, &t.cyc, cyc_ok}, {&cyc_reg_off, &t.cyc_reg_off, cyc_ok}, {&cyc_top_off, &t.cyc_top_off, cyc_ok}};
+    for (auto& r : rows)
+        if (r.on && ::put(up, *r.b, r.v->data(), r.v->size())) return BLANCE_ERR_DEVICE;
+    return 0;
 }
 
-static int upload_inner(blance_ctx* c, const blance_problem* pb) {
-    int st = validate_head(pb);
-    if (st) return st;
-    HIPTRY(hipSetDevice(c->device));
-    c->uploaded = false;
-    c->planned = false;
-    c->wire_names = false;                           // (they were the names of the problem this one replaces)
-    c->h = *pb;
-    const int N = pb->n_nodes, NX = pb->n_nodes_ext, M = pb->n_states, P = pb->n_parts;
-    const int64_t PM = (int64_t)P * M;
-    c->state_priority.assign(pb->state_priority, pb->state_priority + M);
-    c->state_constraints.assign(pb->state_constraints, pb->state_constraints + M);
-    c->rule_off.assign(pb->rule_off, pb->rule_off + M + 1);
-    c->top_prio_strict = M > 0;
-    for (int m = 0; m < M; m++)
-        if (m != pb->top_state && pb->state_priority[m] <= pb->state_priority[pb->top_state]) c->top_prio_strict = false;
-    std::vector<uint8_t> alive((size_t)NX + 1, 0);
-    std::vector<int32_t> alive_ids, alive_rank((size_t)NX + 1, -1);      // the nodes of nodesNext by id, and a node's place among them
-    c->n_alive = 0;
-    c->any_removed = 0;
-    for (int n = 0; n < NX; n++) {
-        if (pb->node_removed[n]) c->any_removed = 1;
-        if (n < N && !pb->node_removed[n]) { alive[n] = 1; alive_rank[n] = c->n_alive++; alive_ids.push_back(n); }
-    }
-    alive_ids.push_back(-1);                                              // (never empty)
+// ---- blance_upload, step by step.  Copies may still be reading the caller's arrays (and the staging buffer) when an error
+// cuts a step short: enter() never returns with copies in flight.
 
-    Mover up(c, true);
+// what the device's half of the validation yields beside its verdict
+struct UploadSummary { PartsSummary ps; uint32_t assign_kinds; int64_t na; };
+
+static int upload_arrays(blance_ctx* c, const blance_problem* pb, const NodeFacts& nodes, Mover& up) {
+    const int NX = pb->n_nodes_ext, M = pb->n_states, P = pb->n_parts;
+    const int64_t PM = (int64_t)P * M;
     c->stage.used = 0;                               // (the stream is idle between calls)
     {   // staging space for everything that may be pageable, asked for once
         const size_t per_part = 4 + 4 + 1 + 1 + 1, per_pm = 4 + 1 + 4 + 1;
         const size_t want = (size_t)P * per_part + (size_t)(PM + 1) * per_pm + (size_t)NX * 32 + (size_t)pb->n_loads * 13 + ((size_t)4 << 20);
+        int st;
         if (c->stage.cap < want && (st = stage_grow(c, want))) return st;
     }
     PUT(node_removed, pb->node_removed, NX);
     PUT(node_added, pb->node_added, NX);
     PUT(node_weight, pb->node_weight, NX);
     PUT(node_has_weight, pb->node_has_weight, NX);
-    PUT(alive, alive.data(), NX);
-    PUT(alive_ids, alive_ids.data(), alive_ids.size());
-    PUT(alive_rank, alive_rank.data(), NX);
+    PUT(alive, nodes.alive.data(), NX);
+    PUT(alive_ids, nodes.alive_ids.data(), nodes.alive_ids.size());
+    PUT(alive_rank, nodes.alive_rank.data(), NX);
     PUT(node_leaf_pos, pb->node_leaf_pos, NX);
     RESERVE(zeros_nx, NX + 1);
     HIPTRY(hipMemsetAsync(c->zeros_nx.p, 0, (size_t)NX + 1, c->stream));
@@ -869,9 +894,15 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     PUT(state_has_stick, pb->state_has_stickiness, M);
     PUT(rule_inc, pb->rule_inc, pb->n_rules);
     PUT(rule_exc, pb->rule_exc, pb->n_rules);
-    if ((st = up.flush())) return st;
+    return up.flush();
+}
 
-    // ---- the O(P) checks of blance_validate and the sizes they yield, on the device (k_validate_parts)
+// The O(P) checks of blance_validate and the sizes they yield, on the device (k_validate_parts, k_validate_ids), the rest
+// of blance_validate on the host meanwhile; the lists' payloads go up between the two device checks.
+static int upload_validate(blance_ctx* c, const blance_problem* pb, Mover& up, UploadSummary* sum) {
+    const int NX = pb->n_nodes_ext, M = pb->n_states, P = pb->n_parts;
+    const int64_t PM = (int64_t)P * M;
+    int st;
     RESERVE(vres, 64);
     RESERVE(vseen, sizeof(uint32_t) * ((size_t)P / 32 + 2));
     HIPTRY(hipMemsetAsync(c->vres.p, 0, 64, c->stream));
@@ -902,29 +933,6 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     }
     // the lists' payloads: their lengths are the last offsets, which are sound now
     const int64_t na = pb->assign_off[PM], np = pb->prev_off[PM];
-    {
-        // partitionSorter's category (plan.go:542-561) is "0" only for partitions with nodes in nodesToRemove.  Without any:
-        // "2" for every partition when nodesToAdd == nil; "1" for every partition when nodesToAdd names no node.  A fresh
-        // plan (the partitions to assign hold nothing): "1" for every partition in the sweep's first state pass (nothing held,
-        // nothing in nodesToAdd), and -- when EVERY node of nodesNext is in nodesToAdd -- "2" for every partition in the later
-        // ones: the first pass gave each partition at least one node (slot 0 always finds a candidate among >= 1 nodes, by
-        // the rule or by the fallback of plan.go:216-218; nothing is excluded as "higher priority" yet) and that node is in
-        // nodesToAdd.  The category is computed from the LIVE lists, so it changes from pass to pass of a sweep.
-        bool any_added = false, all_alive_added = true, any_alive_added = false;
-        for (int n = 0; n < NX; n++) {
-            if (pb->node_added[n]) { any_added = true; if (n < N && !pb->node_removed[n]) any_alive_added = true; }
-            else if (n < N && !pb->node_removed[n]) all_alive_added = false;
-        }
-        // (A plan from nothing whose first pass gave every partition ONE node of nodesNext: the second pass's category is "2"
-        // where that node is in nodesToAdd, else "1" -- one category, and so the first pass's order again, when nodesToAdd is
-        // nil, names every node of nodesNext or names none; "0" needs a removed node.  Not a matter of the knob below: a
-        // stable partition by one category is the order it was given.)
-        c->cycle_order_stands = !c->any_removed && (pb->nodes_to_add_nil || all_alive_added || !any_alive_added);
-        const bool never = !c->any_removed && (pb->nodes_to_add_nil || !any_added);
-        c->uniform_first = never || (!c->any_removed && na == 0);
-        c->uniform_all = never || (!c->any_removed && na == 0 && all_alive_added && c->n_alive >= 1);
-        if (getenv("BLANCE_NO_UNIFORM_CATEGORY")) c->uniform_first = c->uniform_all = false;   // (tests: the partition kernels on such inputs too)
-    }
     PUT(a_nodes, pb->assign_nodes, na);
     PUT(p_nodes, pb->prev_nodes, np);
     if ((st = up.flush())) return st;
@@ -938,176 +946,75 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     if (vr[0] & kVErrPrevId) return fail(BLANCE_ERR_BAD_ARG, "prev node id out of range");
     if (vr[0] & kVErrOrder) return fail(BLANCE_ERR_BAD_ARG, "part_order is not a permutation");
     if (tail_a) { g_last_error = tail_a_text; return tail_a; }
-    PartsSummary ps;
-    {
-        long long r64[3];
-        memcpy(r64, vr + 4, sizeof r64);
-        ps.L = vr[1]; ps.fresh = vr[2]; ps.cap = r64[0]; ps.sumw = r64[1]; ps.aprev = r64[2];
-    }
-    if ((st = validate_tail_b(pb, ps))) return st;
+    long long r64[3];
+    memcpy(r64, vr + 4, sizeof r64);
+    sum->ps = PartsSummary{vr[1], vr[2], r64[0], r64[1], r64[2]};
+    sum->assign_kinds = (uint32_t)vr[10];
+    sum->na = na;
+    return validate_tail_b(pb, sum->ps);
+}
+
+// what the sweep driver's shortcuts rest on
+static void upload_facts(blance_ctx* c, const blance_problem* pb, const NodeFacts& nodes, const UploadSummary& sum) {
+    const int M = pb->n_states;
+    c->n_alive = nodes.n_alive;
+    c->any_removed = nodes.any_removed;
+    c->any_node_weight = nodes.any_node_weight;
+    const OrderFacts o = order_facts(*pb, nodes, sum.na);
+    c->top_prio_strict = o.top_prio_strict;
+    c->cycle_order_stands = o.cycle_order_stands;
+    c->uniform_first = o.uniform_first;
+    c->uniform_all = o.uniform_all;
+    if (getenv("BLANCE_NO_UNIFORM_CATEGORY")) c->uniform_first = c->uniform_all = false;   // (tests: the partition kernels on such inputs too)
     int L = 1;
     for (int m = 0; m < M; m++) if (pb->state_constraints[m] > L) L = pb->state_constraints[m];
-    if (ps.L > L) L = ps.L;
+    if (sum.ps.L > L) L = sum.ps.L;
     c->L = L;
-    c->np_later = pb->n_prev + (int)ps.fresh;              // plan.go:50
-    c->assign_empty = na == 0;
-    c->assign_kinds = (uint32_t)vr[10];
-    c->counts_start_zero = pb->n_loads == 0 && ps.aprev == 0;
-    c->out_capacity = ps.cap;
-
-    c->rule_regions.clear();
-    c->any_node_weight = 0;
+    c->np_later = pb->n_prev + (int)sum.ps.fresh;          // plan.go:50
+    c->assign_empty = sum.na == 0;
+    c->assign_kinds = sum.assign_kinds;
+    c->counts_start_zero = pb->n_loads == 0 && sum.ps.aprev == 0;
+    c->out_capacity = sum.ps.cap;
+    c->flat_chain_ok = pb->n_nodes_ext >= 1 && pb->n_nodes_ext <= 256 && L <= kChainOwn;   // wider: k_pass_seq is faster (measured)
     c->last_stays.assign((size_t)M, 0);
-    for (int n = 0; n < NX; n++) if (pb->node_has_weight[n]) c->any_node_weight = 1;
-    if (!pb->hierarchy_rules_nil) {
-        // leaf-interval table of every (rule, anchor): plan.go:723-734, :755-774
-        const int R = pb->n_rules;
-        std::vector<AnchorSet> tab((size_t)(R > 0 ? R : 1) * (NX + 1));
-        for (int r = 0; r < R; r++)
-            for (int a = 0; a <= NX; a++) {
-                int v = a == NX ? pb->vertex_empty : a;
-                int vi = v, ve = v;
-                for (int l = pb->rule_inc[r]; l > 0; l--) vi = pb->vertex_parent[vi];   // findAncestor
-                for (int l = pb->rule_exc[r]; l > 0; l--) ve = pb->vertex_parent[ve];
-                AnchorSet st;
-                st.alo = pb->vertex_leaf_lo[vi]; st.ahi = pb->vertex_leaf_hi[vi];
-                st.blo = pb->vertex_leaf_lo[ve]; st.bhi = pb->vertex_leaf_hi[ve];
-                tab[(size_t)r * (NX + 1) + a] = st;
-            }
-        PUT(anchors, tab.data(), tab.size());
-        int n_leaves = 1;
-        for (int v = 0; v < pb->n_vertices; v++) if (pb->vertex_leaf_hi[v] > n_leaves) n_leaves = pb->vertex_leaf_hi[v];
-        std::vector<int32_t> leaf_node((size_t)n_leaves, -1);
-        c->leaves_distinct = true;
-        for (int a = 0; a < NX; a++)
-            if (pb->node_leaf_pos[a] >= 0 && pb->node_leaf_pos[a] < n_leaves) {
-                if (leaf_node[pb->node_leaf_pos[a]] >= 0) c->leaves_distinct = false;
-                leaf_node[pb->node_leaf_pos[a]] = a;
-            }
-        PUT(leaf_node, leaf_node.data(), leaf_node.size());
-        // Does the rule cut the leaves into regions?  Every node whose leaf lies in
-        // a region must have exactly that region as its include set.
-        c->rule_regions.resize(R);
-        for (int r = 0; r < R; r++) {
-            blance_ctx::RuleRegions& rr = c->rule_regions[r];
-            const AnchorSet* t = &tab[(size_t)r * (NX + 1)];
-            std::vector<std::pair<int, int>> iv;
-            for (int a = 0; a < NX; a++) {
-                int lp = pb->node_leaf_pos[a];
-                if (lp >= 0 && t[a].alo <= lp && lp < t[a].ahi) iv.emplace_back(t[a].alo, t[a].ahi);
-            }
-            std::sort(iv.begin(), iv.end());
-            iv.erase(std::unique(iv.begin(), iv.end()), iv.end());
-            bool ok = iv.size() >= 2;
-            for (size_t i = 1; i < iv.size() && ok; i++) if (iv[i].first < iv[i - 1].second) ok = false;
-            std::vector<int32_t> node_region((size_t)NX, -1), rlo, rhi;
-            int max_size = 0;
-            if (ok) {
-                for (auto& x : iv) {
-                    rlo.push_back(x.first); rhi.push_back(x.second);
-                    if (x.second - x.first > max_size) max_size = x.second - x.first;
-                }
-                for (int a = 0; a < NX && ok; a++) {
-                    int lp = pb->node_leaf_pos[a];
-                    if (lp < 0) continue;
-                    size_t j = std::upper_bound(rlo.begin(), rlo.end(), lp) - rlo.begin();
-                    if (j == 0 || lp >= rhi[j - 1]) continue;
-                    if (t[a].alo != rlo[j - 1] || t[a].ahi != rhi[j - 1]) ok = false;
-                    node_region[a] = (int)j - 1;
-                }
-            }
-            if (max_size > kChainMaxLeaves) ok = false;
-            // Exclude classes: inside a region the anchors' exclude intervals must be
-            // pairwise disjoint (racks inside a zone), so "leaf is excluded by anchor a"
-            // is "leaf has a's class".  Intervals that cover the region get class -1.
-            std::vector<int32_t> leaf_cls((size_t)n_leaves, -1), cls_size((size_t)n_leaves, 0);
-            int cls_run = -1;
-            for (size_t g = 0; g < rlo.size() && ok; g++) {
-                std::vector<std::pair<int, int>> cl;
-                for (int lp = rlo[g]; lp < rhi[g]; lp++) {
-                    int a = leaf_node[lp];
-                    if (a < 0) continue;
-                    int bl = t[a].blo, bh = t[a].bhi;
-                    if (rlo[g] <= bl && bh <= rhi[g] && bh - bl < rhi[g] - rlo[g]) cl.emplace_back(bl, bh);
-                }
-                std::sort(cl.begin(), cl.end());
-                cl.erase(std::unique(cl.begin(), cl.end()), cl.end());
-                for (size_t i = 1; i < cl.size() && ok; i++) if (cl[i].first < cl[i - 1].second) ok = false;
-                for (size_t i = 0; i < cl.size() && ok; i++) {       // equal, aligned, power-of-two runs? (k_pass_chain_planes)
-                    const int sz = cl[i].second - cl[i].first;
-                    if (cls_run == -1) cls_run = sz;
-                    if (sz != cls_run || sz < 1 || sz > 64 || (sz & (sz - 1)) || (cl[i].first - rlo[g]) % sz) cls_run = 0;
-                    for (int lp = cl[i].first; lp < cl[i].second && cls_run > 0; lp++) if (leaf_node[lp] < 0) cls_run = 0;
-                }
-                for (size_t i = 0; i < cl.size() && ok; i++) cls_size[rlo[g] + i] = cl[i].second - cl[i].first;
-                for (int lp = rlo[g]; lp < rhi[g] && ok; lp++) {
-                    int a = leaf_node[lp];
-                    if (a < 0) continue;
-                    // the class whose interval holds this leaf must be the node's own exclude interval
-                    size_t j = std::upper_bound(cl.begin(), cl.end(), std::make_pair(lp, INT_MAX)) - cl.begin();
-                    if (j > 0 && lp < cl[j - 1].second) {
-                        if (t[a].blo != cl[j - 1].first || t[a].bhi != cl[j - 1].second) ok = false;
-                        leaf_cls[lp] = (int)j - 1;
-                    }
-                }
-            }
-            rr.ok = ok;
-            rr.n_regions = ok ? (int)rlo.size() : 0;
-            rr.max_size = max_size;
-            rr.n_leaves = n_leaves;
-            rr.cls_run = ok && cls_run > 0 ? cls_run : 0;
-            std::vector<int32_t> wg_region, wg_chunk;
-            if (ok)
-                for (size_t g = 0; g < rlo.size(); g++)
-                    for (int ch = 0; ch * 64 < rhi[g] - rlo[g]; ch++) { wg_region.push_back((int32_t)g); wg_chunk.push_back(ch); }
-            rr.n_stay_wgs = (int)wg_region.size();
-            if (ok) {
-                if (put(up, rr.wg_region, wg_region.data(), wg_region.size())) return BLANCE_ERR_DEVICE;
-                if (put(up, rr.wg_chunk, wg_chunk.data(), wg_chunk.size())) return BLANCE_ERR_DEVICE;
-                if (put(up, rr.node_region, node_region.data(), node_region.size())) return BLANCE_ERR_DEVICE;
-                if (put(up, rr.reg_lo, rlo.data(), rlo.size())) return BLANCE_ERR_DEVICE;
-                if (put(up, rr.reg_hi, rhi.data(), rhi.size())) return BLANCE_ERR_DEVICE;
-                if (put(up, rr.leaf_cls, leaf_cls.data(), leaf_cls.size())) return BLANCE_ERR_DEVICE;
-                if (put(up, rr.cls_size, cls_size.data(), cls_size.size())) return BLANCE_ERR_DEVICE;
-            }
-            // The tables of k_cycle.h.  Step j = s A + a of a round robin has top priority node alive_ids[a]: region r_a, rank
-            // q_a among the region's nodes of nodesNext, c_r of them in the region.  A region's chain has a step per full
-            // cycle and node, and one more for every node the last, partial cycle still reaches.
-            rr.cyc_ok = false;
-            std::vector<int32_t> cyc, cyc_top_off;
-            if (ok && c->leaves_distinct && c->n_alive >= 1) {
-                const int A = c->n_alive, B = (int)rlo.size(), full = P / A, part = P % A;
-                bool all_in = true;
-                for (int a = 0; a < A && all_in; a++) all_in = node_region[alive_ids[a]] >= 0;
-                if (all_in) {
-                    std::vector<int32_t> count((size_t)B, 0), last((size_t)B, 0), leaf_steps((size_t)n_leaves, 0);
-                    cyc.assign((size_t)A * kCycWords, 0);
-                    for (int a = 0; a < A; a++) {
-                        const int n = alive_ids[a], g = node_region[n];
-                        cyc[(size_t)a * kCycWords + kCycRegion] = g;
-                        cyc[(size_t)a * kCycWords + kCycRank] = count[g]++;
-                        cyc[(size_t)a * kCycWords + kCycLeaf] = pb->node_leaf_pos[n];
-                        if (a < part) last[g]++;
-                        leaf_steps[pb->node_leaf_pos[n]] = full + (a < part ? 1 : 0);
-                    }
-                    for (int a = 0; a < A; a++) cyc[(size_t)a * kCycWords + kCycCount] = count[cyc[(size_t)a * kCycWords + kCycRegion]];
-                    rr.h_cyc_reg_off.assign((size_t)B + 1, 0);
-                    for (int g = 0; g < B; g++) rr.h_cyc_reg_off[g + 1] = rr.h_cyc_reg_off[g] + full * count[g] + last[g];
-                    cyc_top_off.assign((size_t)n_leaves + 1, 0);
-                    for (int lp = 0; lp < n_leaves; lp++) cyc_top_off[lp + 1] = cyc_top_off[lp] + leaf_steps[lp];
-                    if (put(up, rr.cyc, cyc.data(), cyc.size())) return BLANCE_ERR_DEVICE;
-                    if (put(up, rr.cyc_reg_off, rr.h_cyc_reg_off.data(), rr.h_cyc_reg_off.size())) return BLANCE_ERR_DEVICE;
-                    if (put(up, rr.cyc_top_off, cyc_top_off.data(), cyc_top_off.size())) return BLANCE_ERR_DEVICE;
-                    rr.cyc_ok = true;
-                }
-            }
-            if ((st = up.flush())) return st;             // this rule's staging vectors go out of scope (their bytes are in the staging buffer)
-        }
-        if ((st = up.flush())) return st;                 // ... and the anchor / leaf tables
+}
+
+// the anchor and leaf tables and every rule's RuleRegions
+static int upload_rule_tables(blance_ctx* c, const blance_problem* pb, const NodeFacts& nodes, Mover& up) {
+    int st;
+    const LeafTables leaf = leaf_tables(*pb);
+    c->leaves_distinct = leaf.leaves_distinct;
+    PUT(anchors, leaf.anchors.data(), leaf.anchors.size());
+    PUT(leaf_node, leaf.leaf_node.data(), leaf.leaf_node.size());
+    c->rule_regions.resize(pb->n_rules);
+    for (int r = 0; r < pb->n_rules; r++) {
+        const RuleTables t = analyse_rule(*pb, leaf, nodes, r);
+        if ((st = c->rule_regions[r].put(up, t, leaf.n_leaves))) return st;
+        if ((st = up.flush())) return st;                 // before `t` goes
     }
+    return up.flush();                                    // ... and before `leaf` does
+}
+
+// the whole cluster as one region (flat single chain)
+static int upload_flat_chain_tables(blance_ctx* c, int NX, Mover& up) {
+    std::vector<int32_t> iota((size_t)NX + 1), zero((size_t)NX + 1, 0), one((size_t)NX + 1, 1);
+    for (int i = 0; i <= NX; i++) iota[i] = i;
+    int32_t lo0 = 0, hi0 = NX;
+    PUT(fl_iota, iota.data(), iota.size());
+    PUT(fl_zero, zero.data(), zero.size());
+    PUT(fl_one, one.data(), one.size());
+    PUT(fl_reglo, &lo0, 1);
+    PUT(fl_reghi, &hi0, 1);
+    return up.flush();                                    // before these locals go
+}
+
+static int upload_reserve(blance_ctx* c, const blance_problem* pb, Mover& up) {
+    const int N = pb->n_nodes, NX = pb->n_nodes_ext, M = pb->n_states, P = pb->n_parts, L = c->L;
+    const int64_t PM = (int64_t)P * M;
     const int RW = kRecHead + M * (1 + L);       // header + per-state lists
-    int kmax = 1;
+    int kmax = 1, maxB = 1;
     for (int m = 0; m < M; m++) if (pb->state_constraints[m] > kmax) kmax = pb->state_constraints[m];
+    for (auto& rr : c->rule_regions) if (rr.ok && rr.n_regions > maxB) maxB = rr.n_regions;
     RESERVE(live, sizeof(int32_t) * (size_t)(PM * L + 1));
     RESERVE(live_len, sizeof(int32_t) * (size_t)(PM + 1));
     RESERVE(live_kind, (size_t)PM + 1);
@@ -1128,53 +1035,65 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     RESERVE(warn_state, sizeof(int32_t) * (size_t)(PM + 1));
     RESERVE(scalars, sizeof(int32_t) * kScalWords);   // (blance_kernels.h: ScalarWord)
     RESERVE(ntn_bits, sizeof(uint32_t) * (queue_bits_words(NX) + 4));
-    {
-        int maxB = 1;
-        for (auto& rr : c->rule_regions) if (rr.ok && rr.n_regions > maxB) maxB = rr.n_regions;
-        RESERVE(regid, sizeof(int32_t) * ((size_t)P + 1));
-        RESERVE(chain_order, sizeof(int32_t) * ((size_t)P + 1));
-        RESERVE(chain_inv, sizeof(int32_t) * ((size_t)P + 1));
-        RESERVE(bucket_counts, sizeof(int32_t) * ((size_t)maxB * (cdiv(P, kPartChunk) + 1) + 1));
-        RESERVE(reg_off, sizeof(int32_t) * ((size_t)maxB + 2));
-        RESERVE(cnt_save, sizeof(int32_t) * (size_t)(M + 1) * (NX + 1));
-        if (maxB > 1) {
-            const size_t emax = (size_t)P * L + 1;
-            RESERVE(n_ev, sizeof(int32_t) * ((size_t)P + 2));
-            RESERVE(chain_oi, sizeof(int32_t) * ((size_t)P + 1));
-            RESERVE(ev_key, sizeof(int32_t) * emax);
-            RESERVE(ev_oi, sizeof(int32_t) * emax);
-            RESERVE(ev_leaf, sizeof(int32_t) * emax);
-            RESERVE(ev_w, sizeof(int32_t) * emax);
-            RESERVE(ev_perm, sizeof(int32_t) * emax);
-            RESERVE(ev_off, sizeof(int32_t) * ((size_t)maxB + 2));
-            RESERVE(ev_counts, sizeof(int32_t) * ((size_t)maxB * (cdiv((int64_t)emax, kPartChunk) + 1) + 1));
-        }
-        c->flat_chain_ok = NX >= 1 && NX <= 256 && L <= kChainOwn;   // wider: k_pass_seq is faster (measured)
-        if (maxB > 1 || c->flat_chain_ok) RESERVE(crec, sizeof(int32_t) * ((size_t)P * kCW + 64));
-        if (c->flat_chain_ok) {
-            std::vector<int32_t> iota((size_t)NX + 1), zero((size_t)NX + 1, 0), one((size_t)NX + 1, 1);
-            for (int i = 0; i <= NX; i++) iota[i] = i;
-            int32_t lo0 = 0, hi0 = NX;
-            PUT(fl_iota, iota.data(), iota.size());
-            PUT(fl_zero, zero.data(), zero.size());
-            PUT(fl_one, one.data(), one.size());
-            PUT(fl_reglo, &lo0, 1);
-            PUT(fl_reghi, &hi0, 1);
-            if ((st = up.flush())) return st;             // iota / zero / one / lo0 / hi0 are locals
-        }
-        RESERVE(f_tot, sizeof(int32_t) * ((size_t)NX + 1));
-        RESERVE(f_g, sizeof(double) * ((size_t)NX + 1));
-        RESERVE(f_top_g, sizeof(double) * kTopList);
-        RESERVE(f_top_n, sizeof(int32_t) * kTopList);
-        RESERVE(f_row_count, sizeof(int32_t) * ((size_t)NX + 2));
-        RESERVE(f_m, sizeof(int32_t) * ((size_t)N + 2));
-        RESERVE(f_moff, sizeof(int32_t) * ((size_t)N + 2));
-        RESERVE(f_keys_a, sizeof(unsigned long long) * (2 * (size_t)P + 4));      // fresh runs: up to 2 picks per step, + 1
-        RESERVE(f_keys_b, sizeof(unsigned long long) * (2 * (size_t)P + 4));
-        RESERVE(f_vals_a, sizeof(int32_t) * (2 * (size_t)P + 4));
-        RESERVE(f_vals_b, sizeof(int32_t) * (2 * (size_t)P + 4));
-        RESERVE(f_hist, sizeof(int32_t) * 256 * ((size_t)cdiv(2 * (int64_t)P + 4, kSortTile) + 1));
+    RESERVE(regid, sizeof(int32_t) * ((size_t)P + 1));
+    RESERVE(chain_order, sizeof(int32_t) * ((size_t)P + 1));
+    RESERVE(chain_inv, sizeof(int32_t) * ((size_t)P + 1));
+    RESERVE(bucket_counts, sizeof(int32_t) * ((size_t)maxB * (cdiv(P, kPartChunk) + 1) + 1));
+    RESERVE(reg_off, sizeof(int32_t) * ((size_t)maxB + 2));
+    RESERVE(cnt_save, sizeof(int32_t) * (size_t)(M + 1) * (NX + 1));
+    if (maxB > 1) {
+        const size_t emax = (size_t)P * L + 1;
+        RESERVE(n_ev, sizeof(int32_t) * ((size_t)P + 2));
+        RESERVE(chain_oi, sizeof(int32_t) * ((size_t)P + 1));
+        RESERVE(ev_key, sizeof(int32_t) * emax);
+        RESERVE(ev_oi, sizeof(int32_t) * emax);
+        RESERVE(ev_leaf, sizeof(int32_t) * emax);
+        RESERVE(ev_w, sizeof(int32_t) * emax);
+        RESERVE(ev_perm, sizeof(int32_t) * emax);
+        RESERVE(ev_off, sizeof(int32_t) * ((size_t)maxB + 2));
+        RESERVE(ev_counts, sizeof(int32_t) * ((size_t)maxB * (cdiv((int64_t)emax, kPartChunk) + 1) + 1));
     }
+    if (maxB > 1 || c->flat_chain_ok) RESERVE(crec, sizeof(int32_t) * ((size_t)P * kCW + 64));
+    if (c->flat_chain_ok) {
+        int st = upload_flat_chain_tables(c, NX, up);
+        if (st) return st;
+    }
+    RESERVE(f_tot, sizeof(int32_t) * ((size_t)NX + 1));
+    RESERVE(f_g, sizeof(double) * ((size_t)NX + 1));
+    RESERVE(f_top_g, sizeof(double) * kTopList);
+    RESERVE(f_top_n, sizeof(int32_t) * kTopList);
+    RESERVE(f_row_count, sizeof(int32_t) * ((size_t)NX + 2));
+    RESERVE(f_m, sizeof(int32_t) * ((size_t)N + 2));
+    RESERVE(f_moff, sizeof(int32_t) * ((size_t)N + 2));
+    RESERVE(f_keys_a, sizeof(unsigned long long) * (2 * (size_t)P + 4));      // fresh runs: up to 2 picks per step, + 1
+    RESERVE(f_keys_b, sizeof(unsigned long long) * (2 * (size_t)P + 4));
+    RESERVE(f_vals_a, sizeof(int32_t) * (2 * (size_t)P + 4));
+    RESERVE(f_vals_b, sizeof(int32_t) * (2 * (size_t)P + 4));
+    RESERVE(f_hist, sizeof(int32_t) * 256 * ((size_t)cdiv(2 * (int64_t)P + 4, kSortTile) + 1));
+    return 0;
+}
+
+static int upload_inner(blance_ctx* c, const blance_problem* pb) {
+    int st = validate_head(pb);
+    if (st) return st;
+    HIPTRY(hipSetDevice(c->device));
+    c->uploaded = false;
+    c->planned = false;
+    c->wire_names = false;                           // (they were the names of the problem this one replaces)
+    c->h = *pb;
+    const int M = pb->n_states;
+    c->state_priority.assign(pb->state_priority, pb->state_priority + M);
+    c->state_constraints.assign(pb->state_constraints, pb->state_constraints + M);
+    c->rule_off.assign(pb->rule_off, pb->rule_off + M + 1);
+    c->rule_regions.clear();
+    const NodeFacts nodes = node_facts(*pb);         // (copied from by every flush below: it lives to the end)
+    Mover up(c, true);
+    UploadSummary sum;
+    if ((st = upload_arrays(c, pb, nodes, up))) return st;
+    if ((st = upload_validate(c, pb, up, &sum))) return st;
+    upload_facts(c, pb, nodes, sum);
+    if (!pb->hierarchy_rules_nil && (st = upload_rule_tables(c, pb, nodes, up))) return st;
+    if ((st = upload_reserve(c, pb, up))) return st;
     if ((st = up.flush())) return st;
     HIPTRY(stream_sync(c));
     // the caller's arrays are not retained: drop the host pointers
@@ -1858,18 +1777,19 @@ extern "C" int blance_comm_set(blance_ctx* c, const blance_comm* comm) {
 }
 
 extern "C" int blance_comm_stats(blance_ctx* c, int64_t* calls, int64_t* words) {
-    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    if (calls) *calls = c->comm_calls;
-    if (words) *words = c->comm_bytes / 4;
-    return BLANCE_OK;
+    return enter(c, [&]() -> int {
+        if (calls) *calls = c->comm_calls;
+        if (words) *words = c->comm_bytes / 4;
+        return BLANCE_OK;
+    });
 }
 
 extern "C" int blance_comm_time_ms(blance_ctx* c, double* ms) {
-    if (!c || !ms) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    *ms = c->comm_ms;
-    return BLANCE_OK;
+    return enter(c, [&]() -> int {
+        if (!ms) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        *ms = c->comm_ms;
+        return BLANCE_OK;
+    });
 }
 
 static void comm_release(blance_ctx* c) {
@@ -3346,17 +3266,13 @@ static int calc_moves_locked(blance_ctx* c, const blance_moves_problem* pb, blan
     };
     int e;
     if ((e = up(boff, pb->beg_off, PS + 1)) || (e = up(bnod, pb->beg_nodes, (size_t)nb)) ||
-        (e = up(eoff, pb->end_off, PS + 1)) || (e = up(enod, pb->end_nodes, (size_t)ne))) {
-        (void)stream_sync(c);
+        (e = up(eoff, pb->end_off, PS + 1)) || (e = up(enod, pb->end_nodes, (size_t)ne)))
         return e;
-    }
     if (onode.reserve(sizeof(int32_t) * ((size_t)cap + 1)) || ostate.reserve(sizeof(int32_t) * ((size_t)cap + 1)) ||
         okind.reserve(sizeof(int32_t) * ((size_t)cap + 1)) || nmov.reserve(sizeof(int32_t) * ((size_t)P + 2)) ||
         cnode.reserve(sizeof(int32_t) * ((size_t)cap + 1)) || cstate.reserve(sizeof(int32_t) * ((size_t)cap + 1)) ||
-        ckind.reserve(sizeof(int32_t) * ((size_t)cap + 1))) {
-        (void)stream_sync(c);
+        ckind.reserve(sizeof(int32_t) * ((size_t)cap + 1)))
         return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-    }
     MovesParams q;
     q.P = P; q.M = M; q.favor_min_nodes = pb->favor_min_nodes;
     q.beg_off = boff.as<int32_t>(); q.beg_nodes = bnod.as<int32_t>();
@@ -3392,28 +3308,18 @@ static int calc_moves_locked(blance_ctx* c, const blance_moves_problem* pb, blan
 }
 
 extern "C" int blance_calc_moves(blance_ctx* c, const blance_moves_problem* pb, blance_moves_result* res) {
-    return guarded([&]() -> int {
-    if (!c || !pb || !res) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    return calc_moves_locked(c, pb, res);
+    return enter(c, [&]() -> int {
+        if (!pb || !res) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        return calc_moves_locked(c, pb, res);
     });
 }
 
 extern "C" int blance_upload(blance_ctx* c, const blance_problem* pb) {
-    return guarded([&]() -> int {
-    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    return upload_locked(c, pb);
-    });
+    return enter(c, [&]() -> int { return upload_inner(c, pb); });
 }
 
 extern "C" int blance_plan_resident(blance_ctx* c, blance_result* res) {
-    return guarded([&]() -> int {
-    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, plan_locked(c, res));
-    });
+    return enter(c, [&]() -> int { return plan_locked(c, res); });
 }
 
 // the statistics of the map the context holds (blance_plan_stats_get; a batch's single-path problems); *launches grows by
@@ -3453,8 +3359,9 @@ static int plan_stats_locked(blance_ctx* c, blance_plan_stats* st, int64_t* laun
         }
         BLANCE_LAUNCH(k_stats_reduce, M, 256, sizeof(long long) * 5 * 256 + 64, sm, N, NX, c->alive.as<uint8_t>(), load.as<int32_t>(), out.as<long long>());
         if (launches) *launches += n_launched;
-        HIPTRY(hipMemcpyAsync(host.data(), out.p, sizeof(long long) * (size_t)M * 5, hipMemcpyDeviceToHost, sm));
-        HIPTRY(hipMemcpyAsync(hun.data(), unmet.p, sizeof(long long) * 2 * (size_t)M, hipMemcpyDeviceToHost, sm));
+        // (into the context's read-back block, not into these locals: an error exit drops what is queued there)
+        HIPTRY(read_back(c, host.data(), out.p, sizeof(long long) * (size_t)M * 5));
+        HIPTRY(read_back(c, hun.data(), unmet.p, sizeof(long long) * 2 * (size_t)M));
         HIPTRY(stream_sync(c));
     }
     if (c->stats.iterations > 0) n_next = c->n_alive;
@@ -3473,10 +3380,9 @@ static int plan_stats_locked(blance_ctx* c, blance_plan_stats* st, int64_t* laun
 }
 
 extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
-    return guarded([&]() -> int {
-    if (!c || !st) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    return plan_stats_locked(c, st);
+    return enter(c, [&]() -> int {
+        if (!st) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        return plan_stats_locked(c, st);
     });
 }
 
@@ -3592,11 +3498,9 @@ extern "C" int64_t blance_plan_moves_capacity(const blance_problem* pb, const bl
 }
 
 extern "C" int blance_plan_moves_get(blance_ctx* c, blance_plan_moves* mv) {
-    return guarded([&]() -> int {
-    if (!c || !mv) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, plan_moves_locked(c, mv));
+    return enter(c, [&]() -> int {
+        if (!mv) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        return plan_moves_locked(c, mv);
     });
 }
 
@@ -3693,11 +3597,9 @@ static int wire_names_locked(blance_ctx* c, const blance_wire_names* nm) {
 }
 
 extern "C" int blance_plan_wire_names(blance_ctx* c, const blance_wire_names* nm) {
-    return guarded([&]() -> int {
-    if (!c || !nm) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, wire_names_locked(c, nm));
+    return enter(c, [&]() -> int {
+        if (!nm) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        return wire_names_locked(c, nm);
     });
 }
 
@@ -3772,11 +3674,9 @@ static int plan_wire_locked(blance_ctx* c, char* buf, size_t cap, size_t* need, 
 }
 
 extern "C" int blance_plan_wire_get(blance_ctx* c, char* buf, size_t cap, size_t* need, double* device_ms) {
-    return guarded([&]() -> int {
-    if (!c || !need || (!buf && cap)) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, plan_wire_locked(c, buf, cap, need, device_ms));
+    return enter(c, [&]() -> int {
+        if (!need || (!buf && cap)) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        return plan_wire_locked(c, buf, cap, need, device_ms);
     });
 }
 
@@ -3856,24 +3756,24 @@ static int wire_dict_locked(blance_ctx* c, const blance_wire_names* nm, int32_t 
 
 extern "C" int blance_wire_dict_create(blance_ctx* c, const blance_wire_names* nm, int32_t n_parts, int32_t n_nodes_ext,
                                        int32_t n_states, blance_wire_dict** out) {
-    return guarded([&]() -> int {
-    if (!c || !nm || !out) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    *out = nullptr;
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, wire_dict_locked(c, nm, n_parts, n_nodes_ext, n_states, out));
+    return enter(c, [&]() -> int {
+        if (!nm || !out) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        return wire_dict_locked(c, nm, n_parts, n_nodes_ext, n_states, out);
     });
 }
 
 extern "C" void blance_wire_dict_destroy(blance_ctx* c, blance_wire_dict* d) {
     if (!c || !d) return;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto it = std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d);
-    if (it == c->wd_dicts.end()) return;                 // not one of this context's
-    c->wd_dicts.erase(it);
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    delete d;
+    (void)enter(c, [&]() -> int {
+        auto it = std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d);
+        if (it == c->wd_dicts.end()) return BLANCE_OK;   // not one of this context's
+        c->wd_dicts.erase(it);
+        (void)hipSetDevice(c->device);
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+        delete d;
+        return BLANCE_OK;
+    });
 }
 
 static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out) {
@@ -4001,24 +3901,17 @@ static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const ch
 }
 
 extern "C" int blance_wire_decode_device(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out) {
-    return guarded([&]() -> int {
-    if (!c || !d || !out || (!json && len)) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    const auto t0 = std::chrono::steady_clock::now();
-    const int st = settle(c, wire_decode_locked(c, d, json, len, out));
-    out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // whatever the status
-    return st;
+    return enter(c, [&]() -> int {
+        if (!d || !out || (!json && len)) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        const auto t0 = std::chrono::steady_clock::now();
+        const int st = wire_decode_locked(c, d, json, len, out);
+        out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // whatever the status
+        return st;
     });
 }
 
 extern "C" int blance_download(blance_ctx* c, blance_result* res) {
-    return guarded([&]() -> int {
-    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, download_locked(c, res));
-    });
+    return enter(c, [&]() -> int { return download_locked(c, res); });
 }
 
 // upload, plan, download; total_ms is the device's time for all three
@@ -4028,9 +3921,9 @@ static int plan_whole_locked(blance_ctx* c, const blance_problem* pb, blance_res
     HIPTRY(hipEventCreate(&ev.a));
     HIPTRY(hipEventCreate(&ev.b));
     HIPTRY(hipEventRecord(ev.a, c->stream));
-    int st = upload_locked(c, pb);
-    if (!st) st = settle(c, plan_locked(c, res));
-    if (!st) st = settle(c, download_locked(c, res));
+    int st = upload_inner(c, pb);
+    if (!st) st = plan_locked(c, res);
+    if (!st) st = download_locked(c, res);
     if (st) return st;
     (void)hipEventRecord(ev.b, c->stream);
     (void)hipEventSynchronize(ev.b);
@@ -4041,11 +3934,9 @@ static int plan_whole_locked(blance_ctx* c, const blance_problem* pb, blance_res
 }
 
 extern "C" int blance_plan(blance_ctx* c, const blance_problem* pb, blance_result* res) {
-    return guarded([&]() -> int {
-    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
-    if (!res) return fail(BLANCE_ERR_BAD_ARG, "null result");
-    std::lock_guard<std::mutex> g(c->mu);
-    return plan_whole_locked(c, pb, res);
+    return enter(c, [&]() -> int {
+        if (!res) return fail(BLANCE_ERR_BAD_ARG, "null result");
+        return plan_whole_locked(c, pb, res);
     });
 }
 
@@ -4494,11 +4385,8 @@ extern "C" int blance_plan_batch_moves(blance_ctx* c, int32_t n, const blance_pr
 
 extern "C" int blance_plan_batch_stats(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
                                        blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_info* info) {
-    return guarded([&]() -> int {
-    if (!c) return fail(BLANCE_ERR_BAD_ARG, "null ctx");
-    if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
-    std::lock_guard<std::mutex> g(c->mu);
-    rb_discard(c);
-    return settle(c, plan_batch_locked(c, n, pbs, res, mvs, sts, info));
+    return enter(c, [&]() -> int {
+        if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
+        return plan_batch_locked(c, n, pbs, res, mvs, sts, info);
     });
 }

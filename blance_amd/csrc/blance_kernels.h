@@ -71,6 +71,10 @@ struct PassParams {
 constexpr int kChainOwn = 4, kChainHigh = 4, kChainLow = 4;
 constexpr int kChainStage = 256;                 // steps whose records / outputs one staging round of k_pass_chain holds in LDS
 constexpr int kChainMaxLeaves = 512;             // leaves of one region (one wave64, 8 leaves per lane)
+// k_cycle.h's table of the upload: per alive index a, four words -- its region r_a, its rank q_a among the region's nodes of
+// nodesNext, the global leaf of alive_ids[a], the region's count c_r of such nodes.
+constexpr int kCycWords = 4;
+constexpr int kCycRegion = 0, kCycRank = 1, kCycLeaf = 2, kCycCount = 3;
 constexpr int kCW = 24;
 constexpr int kCOwn = 7, kCHigh = 11, kCLow = 15, kCLowState = 19;
 

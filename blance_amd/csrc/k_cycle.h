@@ -11,9 +11,7 @@
 
 namespace blance {
 
-// Per alive index a, four words: its region r_a, its rank q_a, the global leaf of alive_ids[a], the region's count c_r.
-constexpr int kCycWords = 4;
-constexpr int kCycRegion = 0, kCycRank = 1, kCycLeaf = 2, kCycCount = 3;
+// (blance_kernels.h has the layout of the per-node table `cyc`: kCycWords, kCycRegion .. kCycCount.)
 
 // k_chain_classify + the grouping by region + k_invert in one launch, one thread per step of the pass order (and one more
 // for n_ev[P]).  The classification is k_chain_classify's, from the lists; the chain index comes from the EXPECTED node
