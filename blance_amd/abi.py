@@ -292,6 +292,12 @@ class PlanMoves(C.Structure):
                 ("out", MovesResult), ("n_moves", C.c_int64), ("n_by_kind", C.c_int64 * 4), ("n_parts_moved", C.c_int64)]
 
 
+class Adopt(C.Structure):
+    """blance_adopt of include/blance_hip.h (blance_plan_adopt): the node change of the call that adopts the planned map."""
+    _fields_ = [("node_removed", _u8p), ("node_added", _u8p), ("nodes_to_add_nil", C.c_int32),
+                ("keep_prev_only", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class WireNames(C.Structure):
     """blance_wire_names of include/blance_hip.h (blance_plan_wire_names): three byte blobs with n + 1 int64 offsets."""
     _fields_ = [("part_bytes", C.c_void_p), ("part_off", C.c_void_p), ("node_bytes", C.c_void_p), ("node_off", C.c_void_p),

@@ -26,6 +26,7 @@
 #include "k_plan_moves.h"
 #include "k_plan_wire.h"
 #include "k_wire_decode.h"
+#include "k_adopt.h"
 #include "host/json_escape.hpp"
 #include "host/problem_facts.hpp"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
@@ -408,6 +409,17 @@ struct blance_ctx : CtxHandles {
     DevBuf cnt, ntn, cat, order, chunk_counts, rec, out, warn_part, warn_state, scalars;
     DevBuf cnt_next;                // stateNodeCounts of the next sweep, counted by this sweep's k_sweep_tail (swapped with cnt)
     bool tail_counted = false;      // the last sweep's k_sweep_tail counted cnt_next and refreshed the kinds (plan.go:94, 418)
+    // blance_plan_adopt.  Host copies of the small arrays the upload's analysis reads (host/problem_facts.hpp:
+    // O(NX + VX + rules), never the lists), so that a node change is analysed again without the caller's problem; the two
+    // sums of blance_validate's load bound that an adoption leaves as they are; the summary block of k_adopt_len.
+    std::vector<uint8_t> h_node_has_weight;
+    std::vector<int32_t> h_node_weight, h_node_leaf_pos, h_vparent, h_vlo, h_vhi, h_rule_inc, h_rule_exc;
+    long long sum_abs_weight = 0;   // of the partitions' weights (k_validate_parts)
+    long long kept_load_abs = 0;    // of the load entries of partitions that are only in prevMap (load_first_sweep_only == 0)
+    // an adoption with keep_prev_only: the load entries stay where they are, k_count_loads skips the first-sweep-only ones
+    // in EVERY sweep (the adopted map replaced the keys they stood for)
+    bool loads_later_only = false;
+    DevBuf adopt_res;
     PlanStats stats;                         // of the last plan
     ~blance_ctx();
     std::vector<PassKind> pass_kind;         // of every pass so far in this plan (pass_events holds their begin / end pairs)
@@ -979,6 +991,24 @@ static void upload_facts(blance_ctx* c, const blance_problem* pb, const NodeFact
     c->last_stays.assign((size_t)M, 0);
 }
 
+// what blance_plan_adopt analyses a node change from (the problem has passed validation: the arrays are there)
+static void upload_keep_small(blance_ctx* c, const blance_problem* pb, const UploadSummary& sum) {
+    const int NX = pb->n_nodes_ext;
+    c->h_node_has_weight.assign(pb->node_has_weight, pb->node_has_weight + NX);
+    c->h_node_weight.assign(pb->node_weight, pb->node_weight + NX);
+    c->h_node_leaf_pos.assign(pb->node_leaf_pos, pb->node_leaf_pos + NX);
+    c->h_rule_inc.assign(pb->rule_inc, pb->rule_inc + pb->n_rules);
+    c->h_rule_exc.assign(pb->rule_exc, pb->rule_exc + pb->n_rules);
+    const int VX = pb->hierarchy_rules_nil ? 0 : pb->n_vertices;
+    c->h_vparent.assign(pb->vertex_parent, pb->vertex_parent + VX);
+    c->h_vlo.assign(pb->vertex_leaf_lo, pb->vertex_leaf_lo + VX);
+    c->h_vhi.assign(pb->vertex_leaf_hi, pb->vertex_leaf_hi + VX);
+    c->sum_abs_weight = sum.ps.sumw;
+    c->kept_load_abs = 0;
+    for (int i = 0; i < pb->n_loads; i++)
+        if (!pb->load_first_sweep_only[i]) c->kept_load_abs += pb->load_weight[i] < 0 ? -(long long)pb->load_weight[i] : pb->load_weight[i];
+}
+
 // the anchor and leaf tables and every rule's RuleRegions
 static int upload_rule_tables(blance_ctx* c, const blance_problem* pb, const NodeFacts& nodes, Mover& up) {
     int st;
@@ -1080,6 +1110,7 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     c->uploaded = false;
     c->planned = false;
     c->wire_names = false;                           // (they were the names of the problem this one replaces)
+    c->loads_later_only = false;
     c->h = *pb;
     const int M = pb->n_states;
     c->state_priority.assign(pb->state_priority, pb->state_priority + M);
@@ -1092,6 +1123,7 @@ static int upload_inner(blance_ctx* c, const blance_problem* pb) {
     if ((st = upload_arrays(c, pb, nodes, up))) return st;
     if ((st = upload_validate(c, pb, up, &sum))) return st;
     upload_facts(c, pb, nodes, sum);
+    upload_keep_small(c, pb, sum);
     if (!pb->hierarchy_rules_nil && (st = upload_rule_tables(c, pb, nodes, up))) return st;
     if ((st = upload_reserve(c, pb, up))) return st;
     if ((st = up.flush())) return st;
@@ -2741,7 +2773,7 @@ static int open_sweep(blance_ctx* c, PlanRun& pr, Sweep& sw) {
     }
     // stateNodeCounts = countStateNodes(prevMap), plan.go:94 (zeroed above)
     if (h.n_loads > 0) {
-        BLANCE_LAUNCH_NOSYNC(k_count_loads, cdiv(h.n_loads, 256), 256, 0, sm, h.n_loads, NX, sw.first ? 0 : 1,
+        BLANCE_LAUNCH_NOSYNC(k_count_loads, cdiv(h.n_loads, 256), 256, 0, sm, h.n_loads, NX, sw.first && !c->loads_later_only ? 0 : 1,
                              c->load_state.as<int32_t>(), c->load_node.as<int32_t>(),
                              c->load_weight.as<int32_t>(), c->load_first.as<uint8_t>(), c->cnt.as<int32_t>());
         pr.launches++;
@@ -3320,6 +3352,158 @@ extern "C" int blance_upload(blance_ctx* c, const blance_problem* pb) {
 
 extern "C" int blance_plan_resident(blance_ctx* c, blance_result* res) {
     return enter(c, [&]() -> int { return plan_locked(c, res); });
+}
+
+// ---- blance_plan_adopt: the planned map becomes assign_* and prev_* of the problem the context holds,
+// the node change is analysed again from the host's copies of the small arrays.  Everything that can refuse is decided
+// before the problem is touched: the argument checks at once, P''s share of blance_validate (validate_tail_b) from the
+// summary k_adopt_len leaves in a scratch buffer -- the call's one host round trip.
+static int adopt_locked(blance_ctx* c, const blance_adopt* ad) {
+    if (!c->planned) return fail(BLANCE_ERR_BAD_ARG, "nothing planned yet");
+    if (c->stats.iterations == 0) return fail(BLANCE_ERR_BAD_ARG, "the plan made no sweep (max_iterations <= 0): there is no map to adopt");
+    if (!ad->node_removed || !ad->node_added) return fail(BLANCE_ERR_BAD_ARG, "null array pointer");
+    for (int32_t r : ad->reserved) if (r) return fail(BLANCE_ERR_BAD_ARG, "blance_adopt::reserved must be zero");
+    if (comm_active(c) || c->rccl_comm || c->comm.allreduce_sum_i32 || c->comm.allgather_i32)
+        return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_adopt on a context with a communicator");
+    HIPTRY(hipSetDevice(c->device));
+    const blance_problem& h = c->h;
+    const int NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts;
+    const int64_t PM = (int64_t)P * M;
+    const bool keep = ad->keep_prev_only != 0;
+    hipStream_t sm = c->stream;
+    if (c->side_pending) { HIPTRY(hipStreamSynchronize(c->side)); c->side_pending = false; }
+
+    // P' as a blance_problem, but for its lists: the pure analysis reads nothing else
+    // (every array pointer of it is one of the context's copies, the call's two arrays, or NULL: c->h still carries the
+    // upload's pointers to the caller's lists and weights, which are gone)
+    blance_problem q = h;
+    q.state_stickiness = nullptr; q.state_has_stickiness = nullptr;
+    q.part_order = nullptr; q.part_weight = nullptr; q.part_has_weight = nullptr;
+    q.part_in_prev = nullptr; q.part_prev_never_equal = nullptr;
+    q.assign_off = nullptr; q.assign_nodes = nullptr; q.assign_kind = nullptr;
+    q.prev_off = nullptr; q.prev_nodes = nullptr; q.prev_kind = nullptr;
+    q.load_state = nullptr; q.load_node = nullptr; q.load_weight = nullptr; q.load_first_sweep_only = nullptr;
+    q.node_weight = c->h_node_weight.data();
+    q.state_priority = c->state_priority.data();
+    q.state_constraints = c->state_constraints.data();
+    q.rule_off = c->rule_off.data();
+    q.node_removed = ad->node_removed;
+    q.node_added = ad->node_added;
+    q.node_has_weight = c->h_node_has_weight.data();
+    q.node_leaf_pos = c->h_node_leaf_pos.data();
+    q.rule_inc = c->h_rule_inc.data();
+    q.rule_exc = c->h_rule_exc.data();
+    q.vertex_parent = c->h_vparent.data();
+    q.vertex_leaf_lo = c->h_vlo.data();
+    q.vertex_leaf_hi = c->h_vhi.data();
+    q.nodes_to_add_nil = ad->nodes_to_add_nil ? 1 : 0;
+    q.n_prev = keep ? c->np_later : P;                  // (np_later: the old n_prev + the partitions that were not in prevMap)
+    q.n_loads = keep ? h.n_loads : 0;
+
+    // the length-and-summary pass and the scan, into scratch (blance_download's offsets: nothing is planned after this call)
+    AdoptParams ap;
+    memset(&ap, 0, sizeof ap);
+    UploadSummary sum;
+    sum.ps = PartsSummary{0, 0, 0, c->sum_abs_weight, 0};
+    sum.assign_kinds = 0;
+    sum.na = 0;
+    if (PM > 0) {
+        const DevProblem d = result_problem(c);
+        RESERVE(dl_off, sizeof(int32_t) * ((size_t)PM + 2));
+        RESERVE(adopt_res, sizeof(int32_t) * kAdoptResWords);
+        ap.P = P; ap.M = M; ap.L = c->L; ap.weights_nil = h.partition_weights_nil;
+        for (int m = 0; m < M; m++) ap.k[m] = c->state_constraints[m];
+        ap.prv = d.live; ap.prv_len = d.live_len; ap.prv_kind = d.live_kind;
+        ap.part_weight = c->part_weight.as<int32_t>(); ap.part_has_weight = c->part_has_weight.as<uint8_t>();
+        ap.len = c->dl_off.as<int32_t>(); ap.res = c->adopt_res.as<int32_t>();
+        HIPTRY(hipMemsetAsync(ap.res, 0, sizeof(int32_t) * kAdoptResWords, sm));
+        const int wgs = cdiv(PM + 1, 256);
+        BLANCE_LAUNCH(k_adopt_len, wgs < kAdoptMaxWgs ? wgs : kAdoptMaxWgs, 256, 4 * 5 * sizeof(unsigned long long), sm, ap);
+        SCANTRY((int)PM + 1, ap.len);
+        int32_t vr[kAdoptResWords] = {0};
+        HIPTRY(read_back(c, vr, ap.res, sizeof vr));
+        HIPTRY(stream_sync(c));
+        HIPTRY(hipGetLastError());
+        long long r64[5];
+        memcpy(r64, vr + 4, sizeof r64);
+        sum.ps.L = vr[kAdoptResLongest];
+        sum.ps.cap = r64[kAdoptRes64Cap];
+        sum.ps.aprev = r64[kAdoptRes64Prev];
+        sum.assign_kinds = (uint32_t)vr[kAdoptResKinds];
+        sum.na = r64[kAdoptRes64Total];
+        if (sum.na > (long long)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "more than 2^31 list entries");
+    }
+    {   // validate_tail_b's load bound for P' (its other checks depend on sizes that do not change; L' <= L)
+        long long abs_load = sum.ps.aprev + (keep ? c->kept_load_abs : 0), ksum = 0;
+        for (int m = 0; m < M; m++) ksum += c->state_constraints[m] > 0 ? c->state_constraints[m] : 0;
+        abs_load += sum.ps.sumw * (ksum > 1 ? ksum : 1) * 2;
+        if (abs_load > 2147483647LL) return fail(BLANCE_ERR_UNSUPPORTED, "partition weights overflow the int32 load tables");
+    }
+
+    // from here on the problem is rewritten: a failure leaves the context without one, as a failed upload does
+    c->uploaded = false;
+    c->planned = false;
+    c->h.nodes_to_add_nil = q.nodes_to_add_nil;
+    c->h.n_prev = q.n_prev;
+    c->h.n_loads = q.n_loads;
+    c->loads_later_only = keep;
+    if (!keep) c->kept_load_abs = 0;                     // (the load entries are gone for every later adoption too)
+    const NodeFacts nodes = node_facts(q);               // (copied from by every flush below: it lives to the end)
+    Mover up(c, true);
+    c->stage.used = 0;                                   // (the stream is idle here)
+    int st;
+    PUT(node_removed, ad->node_removed, NX);
+    PUT(node_added, ad->node_added, NX);
+    PUT(alive, nodes.alive.data(), NX);
+    PUT(alive_ids, nodes.alive_ids.data(), nodes.alive_ids.size());
+    PUT(alive_rank, nodes.alive_rank.data(), NX);
+    if ((st = up.flush())) return st;
+    if (PM > 0) {
+        RESERVE(a_nodes, sizeof(int32_t) * (size_t)sum.na);
+        RESERVE(p_nodes, sizeof(int32_t) * (size_t)sum.na);
+        ap.a_off = c->a_off.as<int32_t>(); ap.a_nodes = c->a_nodes.as<int32_t>(); ap.a_kind = c->a_kind.as<uint8_t>();
+        ap.p_off = c->p_off.as<int32_t>(); ap.p_nodes = c->p_nodes.as<int32_t>(); ap.p_kind = c->p_kind.as<uint8_t>();
+        ap.part_in_prev = c->part_in_prev.as<uint8_t>(); ap.part_never_equal = c->part_never_equal.as<uint8_t>();
+        BLANCE_LAUNCH(k_adopt_write, cdiv(PM, kAdoptLists), kAdoptLists, adopt_write_lds(c->L), sm, ap);
+    } else if (P > 0) {                                  // (no states: no list, the flags alone)
+        HIPTRY(hipMemsetAsync(c->part_in_prev.p, 1, (size_t)P, sm));
+        HIPTRY(hipMemsetAsync(c->part_never_equal.p, 0, (size_t)P, sm));
+    }
+    // what the sweep driver's shortcuts rest on, as a fresh upload of P' decides it -- but for L, which stays the stride of
+    // the working state's rows (L' <= L; every buffer of upload_reserve is sized by it)
+    const int L = c->L;
+    const bool flat_chain_ok = c->flat_chain_ok;
+    upload_facts(c, &q, nodes, sum);
+    c->L = L;
+    c->flat_chain_ok = flat_chain_ok;
+    if (!q.hierarchy_rules_nil && (st = upload_rule_tables(c, &q, nodes, up))) return st;
+    if ((st = up.flush())) return st;
+    // the caches of the sweep driver that outlive a plan (plan_locked drops the rest when it starts)
+    c->h_reg_off.clear();
+    c->chain_group_state = -1;
+    c->chain_group_static = false;
+    c->top_group_state = -1;
+    c->group_epoch++;
+    c->cycle_group_epoch = -1;
+    c->top_group_epoch = -1;
+    c->tail_counted = false;
+    c->flags_clean = c->rowcount_clean = false;
+    c->pass_ntn_ready = false;
+    c->bits_stale = true;
+    c->no_fast_keys = false;
+    c->tops_moved = true;
+    c->top_gate = 0;
+    HIPTRY(stream_sync(c));                              // nothing of the caller's or of this frame is read after the call
+    HIPTRY(hipGetLastError());
+    c->uploaded = true;
+    return BLANCE_OK;
+}
+
+extern "C" int blance_plan_adopt(blance_ctx* c, const blance_adopt* ad) {
+    return enter(c, [&]() -> int {
+        if (!ad) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        return adopt_locked(c, ad);
+    });
 }
 
 // the statistics of the map the context holds (blance_plan_stats_get; a batch's single-path problems); *launches grows by

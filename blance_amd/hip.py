@@ -20,7 +20,7 @@ EXPORTS = ["blance_abi_version", "blance_last_error", "blance_result_capacity", 
            "blance_comm_unique_id", "blance_comm_init_rccl", "blance_comm_set", "blance_comm_stats",
            "blance_is_emulated", "blance_host_alloc", "blance_host_free", "blance_comm_time_ms", "blance_host_trim",
            "blance_plan_moves_capacity", "blance_plan_moves_get", "blance_plan_wire_names", "blance_plan_wire_get",
-           "blance_wire_dict_create", "blance_wire_dict_destroy", "blance_wire_decode_device"]
+           "blance_wire_dict_create", "blance_wire_dict_destroy", "blance_wire_decode_device", "blance_plan_adopt"]
 
 _libs = {}
 
@@ -116,6 +116,9 @@ def load_library(path=None):
         lib.blance_wire_dict_destroy.argtypes = [C.c_void_p, C.c_void_p]
         lib.blance_wire_decode_device.restype = C.c_int
         lib.blance_wire_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(abi.WireLists)]
+    if hasattr(lib, "blance_plan_adopt"):                    # likewise: Planner.adopt refuses without it
+        lib.blance_plan_adopt.restype = C.c_int
+        lib.blance_plan_adopt.argtypes = [C.c_void_p, C.POINTER(abi.Adopt)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
@@ -354,6 +357,7 @@ class Planner:
     def plan_into(self, fp, res):
         """blance_plan with the caller's result buffers (a FlatResult made for this problem shape) written again."""
         self._fp = fp
+        self._adopted = False
         self._check(self.lib.blance_plan(self._h, C.byref(fp.as_struct()), C.byref(res.struct)))
         return res
 
@@ -361,6 +365,7 @@ class Planner:
         """blance_plan(): host buffers in, host buffers out."""
         res = abi.FlatResult(fp)
         self._fp = fp
+        self._adopted = False
         self._check(self.lib.blance_plan(self._h, C.byref(fp.as_struct()), C.byref(res.struct)))
         return res
 
@@ -376,6 +381,7 @@ class Planner:
         pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
         rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
         info = abi.BatchInfo()
+        self._adopted = False
         self._check(self.lib.blance_plan_batch(self._h, n, pbs, rss, C.byref(info)))
         return results, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
@@ -442,6 +448,7 @@ class Planner:
         pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
         rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
         info = abi.BatchInfo()
+        self._adopted = False
         self._check(self.lib.blance_plan_batch_moves(self._h, n, pbs, rss,
                                                      ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
                                                      C.byref(info)))
@@ -480,6 +487,7 @@ class Planner:
         pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
         rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
         info = abi.BatchInfo()
+        self._adopted = False
         self._check(self.lib.blance_plan_batch_stats(self._h, n, pbs, rss,
                                                      mv_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
                                                      st_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.PlanStats))),
@@ -538,6 +546,9 @@ class Planner:
             fp = getattr(self, "_fp", None)
             if fp is None:
                 raise BlanceError(abi.ERR_BAD_ARG, "nothing planned yet")
+            if capacity is None and getattr(self, "_adopted", False):
+                # prevMap is an adopted plan: at most the uploaded problem's result capacity, like the new plan
+                capacity = 2 * fp.result_capacity()
             if capacity is None:
                 capacity = int(self.lib.blance_plan_moves_capacity(C.byref(fp.as_struct()), C.byref(mv)))
             new = (lambda n, dt: np.empty(n, dtype=dt)) if arena is None else arena.empty
@@ -692,7 +703,34 @@ class Planner:
 
     def upload(self, fp):
         self._fp = fp
+        self._adopted = False
         self._check(self.lib.blance_upload(self._h, C.byref(fp.as_struct())))
+
+    def adopt(self, node_removed=None, node_added=None, nodes_to_add_nil=True, keep_prev_only=False):
+        """blance_plan_adopt(): the map the last plan / plan_resident produced becomes prevMap and partitionsToAssign of the
+        problem this planner holds, where it lies on the device (problem.adopted_problem is the definition), with the node
+        change of the next call: node_removed / node_added [n_nodes_ext] (None: all zero).  plan_resident then plans it;
+        the names of set_wire_names and every WireDict stay valid.  The round loop:
+        adopt -> plan_resident -> plan_moves -> plan_wire."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_adopt"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_adopt (build the current sources)")
+        fp = getattr(self, "_fp", None)
+        if fp is None:
+            raise BlanceError(abi.ERR_BAD_ARG, "nothing planned yet")
+        NX = fp.scalars["n_nodes_ext"]
+        arrs = []
+        for a in (node_removed, node_added):
+            a = np.zeros(NX, dtype=np.uint8) if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+            if a.size != NX:
+                raise ValueError("node_removed / node_added: one byte per node name of the problem (%d)" % NX)
+            arrs.append(a if a.size else np.zeros(1, dtype=np.uint8))
+        ad = abi.Adopt()
+        ad.node_removed, ad.node_added = [a.ctypes.data_as(C.POINTER(C.c_uint8)) for a in arrs]
+        ad.nodes_to_add_nil = int(bool(nodes_to_add_nil))
+        ad.keep_prev_only = int(bool(keep_prev_only))
+        self._check(self.lib.blance_plan_adopt(self._h, C.byref(ad)))
+        self._adopted = True
 
     def plan_resident(self):
         """Run the whole planNextMapEx loop on the uploaded problem; returns the

@@ -408,6 +408,40 @@ def build_problem(prev_map, partitions_to_assign, nodes_all, nodes_to_remove, no
     return fp
 
 
+def adopted_problem(fp, res, node_removed=None, node_added=None, nodes_to_add_nil=True, keep_prev_only=False):
+    """The problem blance_plan_adopt leaves on a context (include/blance_hip.h), as arrays: the call
+    PlanNextMap(prevMap = partitionsToAssign = the plan `res` of `fp`, nodesToRemove / nodesToAdd as given, everything else
+    as in `fp`).  keep_prev_only: prevMap also keeps the partitions of fp's prevMap that are outside partitionsToAssign
+    (their load entries, load_first_sweep_only == 0); the entries that stood for keys of the partitions to assign outside
+    the model go either way -- the stored map replaces them (plan.go:49-52).  node_removed / node_added: [n_nodes_ext]
+    bytes, None: all zero."""
+    P, M, NX = int(fp.n_parts), int(fp.n_states), int(fp.n_nodes_ext)
+    fp2 = abi.FlatProblem()
+    fp2.scalars = dict(fp.scalars)
+    for name, a in fp.arrays.items():
+        fp2.set(name, a.copy())
+    fp2.node_names, fp2.state_names, fp2.part_names = fp.node_names, fp.state_names, fp.part_names
+    total = int(res.out_off[P * M]) if P * M else 0
+    for pre in ("assign", "prev"):
+        fp2.set(pre + "_off", np.asarray(res.out_off[:P * M + 1]) if P * M else [0])
+        fp2.set(pre + "_nodes", np.asarray(res.out_nodes[:total]))
+        fp2.set(pre + "_kind", np.asarray(res.out_kind[:P * M]))
+    fp2.set("part_in_prev", np.ones(P, dtype=np.uint8))
+    fp2.set("part_prev_never_equal", np.zeros(P, dtype=np.uint8))
+    fp2.set("node_removed", np.zeros(NX, dtype=np.uint8) if node_removed is None else np.asarray(node_removed, dtype=np.uint8))
+    fp2.set("node_added", np.zeros(NX, dtype=np.uint8) if node_added is None else np.asarray(node_added, dtype=np.uint8))
+    if len(fp2.node_removed) != NX or len(fp2.node_added) != NX:
+        raise ValueError("node_removed / node_added: one byte per node name")
+    stay = np.zeros(0, dtype=bool)
+    if keep_prev_only:
+        stay = np.asarray(fp.load_first_sweep_only[:int(fp.n_loads)]) == 0
+    for name in ("load_state", "load_node", "load_weight", "load_first_sweep_only"):
+        fp2.set(name, np.asarray(fp.arrays[name][:int(fp.n_loads)])[stay] if keep_prev_only else [])
+    n_prev = int(fp.n_prev) + int((np.asarray(fp.part_in_prev[:P]) == 0).sum()) if keep_prev_only else P
+    fp2.scalars.update(n_prev=n_prev, n_loads=int(stay.sum()), nodes_to_add_nil=int(bool(nodes_to_add_nil)))
+    return fp2
+
+
 def decode_result(fp, res):
     """Flat result -> ({name: {"name", "nodesByState"}}, {name: [warning strings]})."""
     M = fp.scalars["n_states"]

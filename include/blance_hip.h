@@ -445,6 +445,43 @@ typedef struct blance_wire_lists {
 int blance_wire_decode_device(blance_ctx* ctx, const blance_wire_dict* dict, const char* json, size_t len,
                               blance_wire_lists* out);
 
+/* ---- the planned map as the next call's prevMap (additive to ABI 6: look the symbol up before use) ----
+ * A planner used in a loop plans, a node leaves or joins, and it plans again with prevMap = partitionsToAssign = the
+ * map it just made.  blance_plan_adopt makes that hand-over where the map lies: no list is downloaded
+ * or uploaded.  Precondition: the context holds the map of its last blance_plan / blance_plan_resident
+ * (blance_plan_moves_get's precondition).  After a successful call the context holds, as if uploaded, the problem P':
+ *   - everything of the uploaded problem (sizes, model, stickiness, node and partition weights, part_order, hierarchy,
+ *     rules, booster, max_iterations), except:
+ *   - assign_* = prev_* = the planned map (out_off / out_nodes / out_kind of its download); part_in_prev = 1 and
+ *     part_prev_never_equal = 0 for every partition;
+ *   - node_removed, node_added, nodes_to_add_nil as given here;
+ *   - keep_prev_only == 0: n_prev = n_parts, n_loads = 0 (prevMap' is the planned map);
+ *     keep_prev_only == 1: prevMap' also keeps the old prevMap's partitions outside partitionsToAssign -- the load
+ *     entries with load_first_sweep_only == 0 stay, the others go (the stored map replaces them), n_prev = the old
+ *     n_prev + the partitions that had part_in_prev == 0.
+ * Nothing is planned yet then: blance_plan_resident plans P'; until it has, blance_download, blance_plan_stats_get,
+ * blance_plan_moves_get and blance_plan_wire_get refuse.  The names of blance_plan_wire_names and every blance_wire_dict
+ * stay valid (same partitions, nodes, states).  After the next plan blance_plan_moves_get gives the moves from the
+ * adopted map to the new one; its beg_other must be NULL (P' has no prevMap keys outside the model).  Result buffers
+ * sized for the uploaded problem still suffice: blance_result_capacity of P' is not above the uploaded problem's, and
+ * P' has at most that many prevMap entries (blance_plan_moves_capacity: twice that).
+ * Refused before anything is touched (the context stays as it was, blance_download still answers): BLANCE_ERR_BAD_ARG
+ * for nothing planned (also: after any blance_plan_batch*), a plan with iterations == 0, a NULL array (all that
+ * blance_validate refuses about node_removed / node_added: they are byte flags, any value is read as zero or not), a
+ * non-zero `reserved`; BLANCE_ERR_UNSUPPORTED while a communicator is set (blance_comm_set / blance_comm_init_rccl) -- adopting
+ * a plan sharded over ranks is deliberately not offered: every rank would have to adopt in step --, and for a P'
+ * blance_validate would refuse (partition weights overflowing the load tables).  A device failure part-way leaves
+ * the context without a problem, as a failed blance_upload does. */
+typedef struct blance_adopt {
+    const uint8_t* node_removed;    /* [n_nodes_ext] nodesToRemove of the NEXT call                 */
+    const uint8_t* node_added;      /* [n_nodes_ext] nodesToAdd of the next call                    */
+    int32_t        nodes_to_add_nil;
+    int32_t        keep_prev_only;  /* 0: prevMap' = nextMap.  1: prevMap' = nextMap plus the
+                                       partitions of the old prevMap outside partitionsToAssign   */
+    int32_t        reserved[4];     /* zero */
+} blance_adopt;
+int blance_plan_adopt(blance_ctx* ctx, const blance_adopt* ad);
+
 /* ---- one plan on several GPUs (BASELINE.json config 4) ------------------------------------
  * The steps of a state pass that runs as region chains (one chain per hierarchy region)
  * shard over the ranks by region: every rank holds the whole problem (upload the same problem on
