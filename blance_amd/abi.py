@@ -298,6 +298,21 @@ class Adopt(C.Structure):
                 ("keep_prev_only", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class WireAdopt(C.Structure):
+    """struct blance_wire_adopt of include/blance_hip.h (blance_wire_adopt): a PartitionMap document decoded on the device
+    becomes prevMap (assign_too: and partitionsToAssign) of the problem the context holds."""
+    _fields_ = [("dict", C.c_void_p), ("json", C.c_void_p), ("len", C.c_size_t), ("node_removed", _u8p), ("node_added", _u8p),
+                ("nodes_to_add_nil", C.c_int32), ("assign_too", C.c_int32), ("keep_prev_only", C.c_int32),
+                ("reserved", C.c_int32 * 4), ("refusal", C.c_int32), ("refusal_at", C.c_int64), ("n_node_refs", C.c_int64),
+                ("n_parts_seen", C.c_int64), ("result_capacity", C.c_int64), ("why", C.c_int32), ("why_at", C.c_int64),
+                ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+# BLANCE_WIRE_ADOPT_* of include/blance_hip.h: why blance_wire_adopt refused a document that decoded
+WIRE_ADOPT_WHYS = ("taken", "list_too_long", "partition_missing", "duplicate_node", "removed_without_prev", "load_overflow")
+WIRE_ADOPT = {name: code for code, name in enumerate(WIRE_ADOPT_WHYS)}
+
+
 class WireNames(C.Structure):
     """blance_wire_names of include/blance_hip.h (blance_plan_wire_names): three byte blobs with n + 1 int64 offsets."""
     _fields_ = [("part_bytes", C.c_void_p), ("part_off", C.c_void_p), ("node_bytes", C.c_void_p), ("node_off", C.c_void_p),

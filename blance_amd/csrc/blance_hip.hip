@@ -27,6 +27,7 @@
 #include "k_plan_wire.h"
 #include "k_wire_decode.h"
 #include "k_adopt.h"
+#include "k_wire_adopt.h"
 #include "host/json_escape.hpp"
 #include "host/problem_facts.hpp"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
@@ -420,6 +421,7 @@ struct blance_ctx : CtxHandles {
     // in EVERY sweep (the adopted map replaced the keys they stood for)
     bool loads_later_only = false;
     DevBuf adopt_res;
+    DevBuf wire_adopt_res;          // blance_wire_adopt: the summary block of k_wire_adopt_sum
     PlanStats stats;                         // of the last plan
     ~blance_ctx();
     std::vector<PassKind> pass_kind;         // of every pass so far in this plan (pass_events holds their begin / end pairs)
@@ -3354,6 +3356,99 @@ extern "C" int blance_plan_resident(blance_ctx* c, blance_result* res) {
     return enter(c, [&]() -> int { return plan_locked(c, res); });
 }
 
+// ---- what blance_plan_adopt and blance_wire_adopt share.
+// P' as a blance_problem, but for its lists, n_prev and n_loads: the pure analysis reads nothing else.  Every array pointer
+// of it is one of the context's copies, the call's two arrays, or NULL: c->h still carries the upload's pointers to the
+// caller's lists and weights, which are gone.
+static blance_problem adopt_shell(const blance_ctx* c, const uint8_t* node_removed, const uint8_t* node_added, int nodes_to_add_nil) {
+    blance_problem q = c->h;
+    q.state_stickiness = nullptr; q.state_has_stickiness = nullptr;
+    q.part_order = nullptr; q.part_weight = nullptr; q.part_has_weight = nullptr;
+    q.part_in_prev = nullptr; q.part_prev_never_equal = nullptr;
+    q.assign_off = nullptr; q.assign_nodes = nullptr; q.assign_kind = nullptr;
+    q.prev_off = nullptr; q.prev_nodes = nullptr; q.prev_kind = nullptr;
+    q.load_state = nullptr; q.load_node = nullptr; q.load_weight = nullptr; q.load_first_sweep_only = nullptr;
+    q.node_weight = c->h_node_weight.data();
+    q.state_priority = c->state_priority.data();
+    q.state_constraints = c->state_constraints.data();
+    q.rule_off = c->rule_off.data();
+    q.node_removed = node_removed;
+    q.node_added = node_added;
+    q.node_has_weight = c->h_node_has_weight.data();
+    q.node_leaf_pos = c->h_node_leaf_pos.data();
+    q.rule_inc = c->h_rule_inc.data();
+    q.rule_exc = c->h_rule_exc.data();
+    q.vertex_parent = c->h_vparent.data();
+    q.vertex_leaf_lo = c->h_vlo.data();
+    q.vertex_leaf_hi = c->h_vhi.data();
+    q.nodes_to_add_nil = nodes_to_add_nil ? 1 : 0;
+    return q;
+}
+
+// validate_tail_b's load bound for P' (its other checks depend on sizes that do not change; L' <= L)
+static bool adopt_load_overflows(const blance_ctx* c, const PartsSummary& ps, bool keep) {
+    long long abs_load = ps.aprev + (keep ? c->kept_load_abs : 0), ksum = 0;
+    for (int32_t k : c->state_constraints) ksum += k > 0 ? k : 0;
+    abs_load += ps.sumw * (ksum > 1 ? ksum : 1) * 2;
+    return abs_load > 2147483647LL;
+}
+
+// The second half of both: from here on the problem is rewritten, a failure leaves the context without one, as a failed
+// upload does.  q: adopt_shell's problem with n_prev and n_loads set; na / np: the entries a_nodes / p_nodes must hold (-1:
+// the buffer stays as it is); write_lists launches the kernel that writes the lists and the partitions' flags.
+template <class F>
+static int adopt_swap(blance_ctx* c, const blance_problem& q, const UploadSummary& sum, bool keep, int64_t na, int64_t np, F write_lists) {
+    const int NX = q.n_nodes_ext;
+    c->uploaded = false;
+    c->planned = false;
+    c->h.nodes_to_add_nil = q.nodes_to_add_nil;
+    c->h.n_prev = q.n_prev;
+    c->h.n_loads = q.n_loads;
+    c->loads_later_only = keep;
+    if (!keep) c->kept_load_abs = 0;                     // (the load entries are gone for every later adoption too)
+    const NodeFacts nodes = node_facts(q);               // (copied from by every flush below: it lives to the end)
+    Mover up(c, true);
+    c->stage.used = 0;                                   // (the stream is idle here)
+    int st;
+    PUT(node_removed, q.node_removed, NX);
+    PUT(node_added, q.node_added, NX);
+    PUT(alive, nodes.alive.data(), NX);
+    PUT(alive_ids, nodes.alive_ids.data(), nodes.alive_ids.size());
+    PUT(alive_rank, nodes.alive_rank.data(), NX);
+    if ((st = up.flush())) return st;
+    if (na >= 0) RESERVE(a_nodes, sizeof(int32_t) * (size_t)na);
+    if (np >= 0) RESERVE(p_nodes, sizeof(int32_t) * (size_t)np);
+    if ((st = write_lists())) return st;
+    // what the sweep driver's shortcuts rest on, as a fresh upload of P' decides it -- but for L, which stays the stride of
+    // the working state's rows (L' <= L; every buffer of upload_reserve is sized by it)
+    const int L = c->L;
+    const bool flat_chain_ok = c->flat_chain_ok;
+    upload_facts(c, &q, nodes, sum);
+    c->L = L;
+    c->flat_chain_ok = flat_chain_ok;
+    if (!q.hierarchy_rules_nil && (st = upload_rule_tables(c, &q, nodes, up))) return st;
+    if ((st = up.flush())) return st;
+    // the caches of the sweep driver that outlive a plan (plan_locked drops the rest when it starts)
+    c->h_reg_off.clear();
+    c->chain_group_state = -1;
+    c->chain_group_static = false;
+    c->top_group_state = -1;
+    c->group_epoch++;
+    c->cycle_group_epoch = -1;
+    c->top_group_epoch = -1;
+    c->tail_counted = false;
+    c->flags_clean = c->rowcount_clean = false;
+    c->pass_ntn_ready = false;
+    c->bits_stale = true;
+    c->no_fast_keys = false;
+    c->tops_moved = true;
+    c->top_gate = 0;
+    HIPTRY(stream_sync(c));                              // nothing of the caller's or of this frame is read after the call
+    HIPTRY(hipGetLastError());
+    c->uploaded = true;
+    return BLANCE_OK;
+}
+
 // ---- blance_plan_adopt: the planned map becomes assign_* and prev_* of the problem the context holds,
 // the node change is analysed again from the host's copies of the small arrays.  Everything that can refuse is decided
 // before the problem is touched: the argument checks at once, P''s share of blance_validate (validate_tail_b) from the
@@ -3367,36 +3462,13 @@ static int adopt_locked(blance_ctx* c, const blance_adopt* ad) {
         return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_adopt on a context with a communicator");
     HIPTRY(hipSetDevice(c->device));
     const blance_problem& h = c->h;
-    const int NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts;
+    const int M = h.n_states, P = h.n_parts;
     const int64_t PM = (int64_t)P * M;
     const bool keep = ad->keep_prev_only != 0;
     hipStream_t sm = c->stream;
     if (c->side_pending) { HIPTRY(hipStreamSynchronize(c->side)); c->side_pending = false; }
 
-    // P' as a blance_problem, but for its lists: the pure analysis reads nothing else
-    // (every array pointer of it is one of the context's copies, the call's two arrays, or NULL: c->h still carries the
-    // upload's pointers to the caller's lists and weights, which are gone)
-    blance_problem q = h;
-    q.state_stickiness = nullptr; q.state_has_stickiness = nullptr;
-    q.part_order = nullptr; q.part_weight = nullptr; q.part_has_weight = nullptr;
-    q.part_in_prev = nullptr; q.part_prev_never_equal = nullptr;
-    q.assign_off = nullptr; q.assign_nodes = nullptr; q.assign_kind = nullptr;
-    q.prev_off = nullptr; q.prev_nodes = nullptr; q.prev_kind = nullptr;
-    q.load_state = nullptr; q.load_node = nullptr; q.load_weight = nullptr; q.load_first_sweep_only = nullptr;
-    q.node_weight = c->h_node_weight.data();
-    q.state_priority = c->state_priority.data();
-    q.state_constraints = c->state_constraints.data();
-    q.rule_off = c->rule_off.data();
-    q.node_removed = ad->node_removed;
-    q.node_added = ad->node_added;
-    q.node_has_weight = c->h_node_has_weight.data();
-    q.node_leaf_pos = c->h_node_leaf_pos.data();
-    q.rule_inc = c->h_rule_inc.data();
-    q.rule_exc = c->h_rule_exc.data();
-    q.vertex_parent = c->h_vparent.data();
-    q.vertex_leaf_lo = c->h_vlo.data();
-    q.vertex_leaf_hi = c->h_vhi.data();
-    q.nodes_to_add_nil = ad->nodes_to_add_nil ? 1 : 0;
+    blance_problem q = adopt_shell(c, ad->node_removed, ad->node_added, ad->nodes_to_add_nil);
     q.n_prev = keep ? c->np_later : P;                  // (np_later: the old n_prev + the partitions that were not in prevMap)
     q.n_loads = keep ? h.n_loads : 0;
 
@@ -3433,70 +3505,20 @@ static int adopt_locked(blance_ctx* c, const blance_adopt* ad) {
         sum.na = r64[kAdoptRes64Total];
         if (sum.na > (long long)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "more than 2^31 list entries");
     }
-    {   // validate_tail_b's load bound for P' (its other checks depend on sizes that do not change; L' <= L)
-        long long abs_load = sum.ps.aprev + (keep ? c->kept_load_abs : 0), ksum = 0;
-        for (int m = 0; m < M; m++) ksum += c->state_constraints[m] > 0 ? c->state_constraints[m] : 0;
-        abs_load += sum.ps.sumw * (ksum > 1 ? ksum : 1) * 2;
-        if (abs_load > 2147483647LL) return fail(BLANCE_ERR_UNSUPPORTED, "partition weights overflow the int32 load tables");
-    }
+    if (adopt_load_overflows(c, sum.ps, keep)) return fail(BLANCE_ERR_UNSUPPORTED, "partition weights overflow the int32 load tables");
 
-    // from here on the problem is rewritten: a failure leaves the context without one, as a failed upload does
-    c->uploaded = false;
-    c->planned = false;
-    c->h.nodes_to_add_nil = q.nodes_to_add_nil;
-    c->h.n_prev = q.n_prev;
-    c->h.n_loads = q.n_loads;
-    c->loads_later_only = keep;
-    if (!keep) c->kept_load_abs = 0;                     // (the load entries are gone for every later adoption too)
-    const NodeFacts nodes = node_facts(q);               // (copied from by every flush below: it lives to the end)
-    Mover up(c, true);
-    c->stage.used = 0;                                   // (the stream is idle here)
-    int st;
-    PUT(node_removed, ad->node_removed, NX);
-    PUT(node_added, ad->node_added, NX);
-    PUT(alive, nodes.alive.data(), NX);
-    PUT(alive_ids, nodes.alive_ids.data(), nodes.alive_ids.size());
-    PUT(alive_rank, nodes.alive_rank.data(), NX);
-    if ((st = up.flush())) return st;
-    if (PM > 0) {
-        RESERVE(a_nodes, sizeof(int32_t) * (size_t)sum.na);
-        RESERVE(p_nodes, sizeof(int32_t) * (size_t)sum.na);
-        ap.a_off = c->a_off.as<int32_t>(); ap.a_nodes = c->a_nodes.as<int32_t>(); ap.a_kind = c->a_kind.as<uint8_t>();
-        ap.p_off = c->p_off.as<int32_t>(); ap.p_nodes = c->p_nodes.as<int32_t>(); ap.p_kind = c->p_kind.as<uint8_t>();
-        ap.part_in_prev = c->part_in_prev.as<uint8_t>(); ap.part_never_equal = c->part_never_equal.as<uint8_t>();
-        BLANCE_LAUNCH(k_adopt_write, cdiv(PM, kAdoptLists), kAdoptLists, adopt_write_lds(c->L), sm, ap);
-    } else if (P > 0) {                                  // (no states: no list, the flags alone)
-        HIPTRY(hipMemsetAsync(c->part_in_prev.p, 1, (size_t)P, sm));
-        HIPTRY(hipMemsetAsync(c->part_never_equal.p, 0, (size_t)P, sm));
-    }
-    // what the sweep driver's shortcuts rest on, as a fresh upload of P' decides it -- but for L, which stays the stride of
-    // the working state's rows (L' <= L; every buffer of upload_reserve is sized by it)
-    const int L = c->L;
-    const bool flat_chain_ok = c->flat_chain_ok;
-    upload_facts(c, &q, nodes, sum);
-    c->L = L;
-    c->flat_chain_ok = flat_chain_ok;
-    if (!q.hierarchy_rules_nil && (st = upload_rule_tables(c, &q, nodes, up))) return st;
-    if ((st = up.flush())) return st;
-    // the caches of the sweep driver that outlive a plan (plan_locked drops the rest when it starts)
-    c->h_reg_off.clear();
-    c->chain_group_state = -1;
-    c->chain_group_static = false;
-    c->top_group_state = -1;
-    c->group_epoch++;
-    c->cycle_group_epoch = -1;
-    c->top_group_epoch = -1;
-    c->tail_counted = false;
-    c->flags_clean = c->rowcount_clean = false;
-    c->pass_ntn_ready = false;
-    c->bits_stale = true;
-    c->no_fast_keys = false;
-    c->tops_moved = true;
-    c->top_gate = 0;
-    HIPTRY(stream_sync(c));                              // nothing of the caller's or of this frame is read after the call
-    HIPTRY(hipGetLastError());
-    c->uploaded = true;
-    return BLANCE_OK;
+    return adopt_swap(c, q, sum, keep, PM > 0 ? sum.na : -1, PM > 0 ? sum.na : -1, [&]() -> int {
+        if (PM > 0) {
+            ap.a_off = c->a_off.as<int32_t>(); ap.a_nodes = c->a_nodes.as<int32_t>(); ap.a_kind = c->a_kind.as<uint8_t>();
+            ap.p_off = c->p_off.as<int32_t>(); ap.p_nodes = c->p_nodes.as<int32_t>(); ap.p_kind = c->p_kind.as<uint8_t>();
+            ap.part_in_prev = c->part_in_prev.as<uint8_t>(); ap.part_never_equal = c->part_never_equal.as<uint8_t>();
+            BLANCE_LAUNCH(k_adopt_write, cdiv(PM, kAdoptLists), kAdoptLists, adopt_write_lds(c->L), sm, ap);
+        } else if (P > 0) {                                  // (no states: no list, the flags alone)
+            HIPTRY(hipMemsetAsync(c->part_in_prev.p, 1, (size_t)P, sm));
+            HIPTRY(hipMemsetAsync(c->part_never_equal.p, 0, (size_t)P, sm));
+        }
+        return BLANCE_OK;
+    });
 }
 
 extern "C" int blance_plan_adopt(blance_ctx* c, const blance_adopt* ad) {
@@ -3960,15 +3982,17 @@ extern "C" void blance_wire_dict_destroy(blance_ctx* c, blance_wire_dict* d) {
     });
 }
 
-static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out) {
+// The decoder's device part: the record split, both parse passes, the decoded CSR left in c->wd[] (kWdPartKind, kWdOff,
+// kWdKind, kWdNodes) -- blance_wire_decode_device downloads it from there, blance_wire_adopt makes it the problem's lists.
+// The counters, the refusal and the first pass's device_ms go to `out`; its arrays are not touched.  count_only: pass 1
+// alone; check_capacity: out->capacity below the entries ends the call before pass 2.  On BLANCE_OK behind pass 2 the
+// stream is idle and c->ev0 .. c->ev1 span the kernels.
+enum { kWdDoc, kWdTb, kWdQbits, kWdQuotes, kWdDepth, kWdCount, kWdRec, kWdClaim, kWdPartKind, kWdKind, kWdOff, kWdNodes, kWdRefusal };
+static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out,
+                                   bool count_only, bool check_capacity) {
     out->n_node_refs = out->n_parts_seen = 0;
     out->refusal = 0; out->refusal_at = -1;
     out->device_ms = out->total_ms = 0.0;
-    if (std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d) == c->wd_dicts.end())
-        return fail(BLANCE_ERR_BAD_ARG, "the dictionary is not one of this context's");
-    if (out->capacity < 0 || (!out->nodes && out->capacity > 0)) return fail(BLANCE_ERR_BAD_ARG, "nodes NULL with a capacity, or a negative capacity");
-    const bool count_only = !out->nodes && out->capacity == 0;
-    if (!count_only && (!out->part_kind || !out->off || !out->kind)) return fail(BLANCE_ERR_BAD_ARG, "part_kind, off or kind NULL");
     if (len > (size_t)INT32_MAX) {                       // before anything is launched
         out->refusal = kWdDocumentTooLong; out->refusal_at = 0;
         return fail(BLANCE_ERR_UNSUPPORTED, "refused: a document of 2^31 bytes or more");
@@ -3984,7 +4008,8 @@ static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const ch
     q.n_tiles = cdiv((int64_t)len, q.tile);
     q.P = P; q.NX = NX; q.M = M; q.stage = c->wd_stage;
     const size_t nt = (size_t)q.n_tiles;
-    enum { kDoc, kTb, kQbits, kQuotes, kDepth, kCount, kRec, kClaim, kPartKind, kKind, kOff, kNodes, kRefusal };
+    enum { kDoc = kWdDoc, kTb = kWdTb, kQbits = kWdQbits, kQuotes = kWdQuotes, kDepth = kWdDepth, kCount = kWdCount, kRec = kWdRec,
+           kClaim = kWdClaim, kPartKind = kWdPartKind, kKind = kWdKind, kOff = kWdOff, kNodes = kWdNodes, kRefusal = kWdRefusal };
     DevBuf* w = c->wd;
     if (w[kDoc].reserve(len + 2 * kWdPad) || w[kTb].reserve(4 * (nt + 1)) || w[kQbits].reserve(nt * (size_t)q.tile / 8 + 16) ||
         w[kQuotes].reserve(4 * (nt + 2)) || w[kDepth].reserve(4 * (nt + 2)) || w[kCount].reserve(4 * (nt + 2)) ||
@@ -4057,7 +4082,7 @@ static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const ch
     out->n_node_refs = total;
     out->n_parts_seen = R;
     if (count_only) return BLANCE_OK;
-    if (out->capacity < (int64_t)total) return fail(BLANCE_ERR_CAPACITY, "the caller's nodes array is too small (see n_node_refs)");
+    if (check_capacity && out->capacity < (int64_t)total) return fail(BLANCE_ERR_CAPACITY, "the caller's nodes array is too small (see n_node_refs)");
     // pass 2: the node ids
     if (w[kNodes].reserve(4 * ((size_t)total + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
     q.nodes = w[kNodes].as<int32_t>();
@@ -4068,17 +4093,35 @@ static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const ch
     HIPTRY(stream_sync(c));
     HIPTRY(hipGetLastError());
     if (again != ~0ull) return fail(BLANCE_ERR_DEVICE, "k_wd_parse: the two passes disagree");
-    {
+    return BLANCE_OK;
+}
+
+static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out) {
+    out->n_node_refs = out->n_parts_seen = 0;
+    out->refusal = 0; out->refusal_at = -1;
+    out->device_ms = out->total_ms = 0.0;
+    if (std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d) == c->wd_dicts.end())
+        return fail(BLANCE_ERR_BAD_ARG, "the dictionary is not one of this context's");
+    if (out->capacity < 0 || (!out->nodes && out->capacity > 0)) return fail(BLANCE_ERR_BAD_ARG, "nodes NULL with a capacity, or a negative capacity");
+    const bool count_only = !out->nodes && out->capacity == 0;
+    if (!count_only && (!out->part_kind || !out->off || !out->kind)) return fail(BLANCE_ERR_BAD_ARG, "part_kind, off or kind NULL");
+    int e = wire_decode_device_part(c, d, json, len, out, count_only, true);
+    if (e || count_only) return e;
+    const int P = d->n[0], M = d->n[2];
+    const int64_t PM = (int64_t)P * M;
+    const int64_t total = out->n_node_refs;
+    {   // the download
         Mover down(c, false);
         c->stage.used = 0;
-        if ((e = down.copy(out->part_kind, q.part_kind, (size_t)P))) return e;
-        if ((e = down.copy(out->off, q.off, 4 * ((size_t)PM + 1)))) return e;
-        if ((e = down.copy(out->kind, q.kind, (size_t)PM))) return e;
-        if ((e = down.copy(out->nodes, q.nodes, 4 * (size_t)total))) return e;
+        if ((e = down.copy(out->part_kind, c->wd[kWdPartKind].p, (size_t)P))) return e;
+        if ((e = down.copy(out->off, c->wd[kWdOff].p, 4 * ((size_t)PM + 1)))) return e;
+        if ((e = down.copy(out->kind, c->wd[kWdKind].p, (size_t)PM))) return e;
+        if ((e = down.copy(out->nodes, c->wd[kWdNodes].p, 4 * (size_t)total))) return e;
         if ((e = down.finish())) return e;
     }
     HIPTRY(stream_sync(c));
     HIPTRY(hipGetLastError());
+    float ms = 0.f;
     HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     out->device_ms = ms;
     return BLANCE_OK;
@@ -4090,6 +4133,127 @@ extern "C" int blance_wire_decode_device(blance_ctx* c, const blance_wire_dict* 
         const auto t0 = std::chrono::steady_clock::now();
         const int st = wire_decode_locked(c, d, json, len, out);
         out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // whatever the status
+        return st;
+    });
+}
+
+// ---- blance_wire_adopt: the decoder's device part, k_wire_adopt_sum with one more round trip for its
+// summary words, the refusals -- and only then adopt_swap, whose write kernel reads the decoded CSR where the decoder left it.
+static int wire_adopt_locked(blance_ctx* c, struct blance_wire_adopt* wa) {
+    wa->refusal = 0; wa->refusal_at = -1;
+    wa->n_node_refs = wa->n_parts_seen = wa->result_capacity = 0;
+    wa->why = 0; wa->why_at = -1;
+    wa->device_ms = wa->total_ms = 0.0;
+    const blance_wire_dict* d = wa->dict;
+    if (!d || (!wa->json && wa->len) || !wa->node_removed || !wa->node_added) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    for (int32_t r : wa->reserved) if (r) return fail(BLANCE_ERR_BAD_ARG, "blance_wire_adopt::reserved must be zero");
+    if (std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d) == c->wd_dicts.end())
+        return fail(BLANCE_ERR_BAD_ARG, "the dictionary is not one of this context's");
+    if (!c->uploaded) return fail(BLANCE_ERR_BAD_ARG, "the context holds no problem (blance_upload first)");
+    const blance_problem& h = c->h;
+    const int NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts;
+    if (d->n[0] != P || d->n[1] != NX || d->n[2] != M)
+        return fail(BLANCE_ERR_BAD_ARG, "the dictionary's sizes are not those of the problem the context holds");
+    if (comm_active(c) || c->rccl_comm || c->comm.allreduce_sum_i32 || c->comm.allgather_i32)
+        return fail(BLANCE_ERR_UNSUPPORTED, "blance_wire_adopt on a context with a communicator");
+    HIPTRY(hipSetDevice(c->device));
+    const int64_t PM = (int64_t)P * M;
+    const bool keep = wa->keep_prev_only != 0, assign_too = wa->assign_too != 0;
+    hipStream_t sm = c->stream;
+    if (c->side_pending) { HIPTRY(hipStreamSynchronize(c->side)); c->side_pending = false; }
+
+    blance_wire_lists wl;
+    memset(&wl, 0, sizeof wl);
+    int st = wire_decode_device_part(c, d, wa->json, wa->len, &wl, false, false);
+    wa->refusal = wl.refusal; wa->refusal_at = wl.refusal_at;
+    wa->n_node_refs = wl.n_node_refs; wa->n_parts_seen = wl.n_parts_seen;
+    wa->device_ms = wl.device_ms;
+    if (st) return st;
+    const int64_t total = wl.n_node_refs;
+
+    // the summary of the lists where they lie
+    WireAdoptParams ap;
+    memset(&ap, 0, sizeof ap);
+    ap.P = P; ap.M = M; ap.L = c->L; ap.weights_nil = h.partition_weights_nil; ap.assign_too = assign_too ? 1 : 0;
+    for (int m = 0; m < M; m++) ap.k[m] = c->state_constraints[m];
+    ap.part_kind = c->wd[kWdPartKind].as<uint8_t>(); ap.off = c->wd[kWdOff].as<int32_t>();
+    ap.kind = c->wd[kWdKind].as<uint8_t>(); ap.nodes = c->wd[kWdNodes].as<int32_t>();
+    ap.cur_a_off = c->a_off.as<int32_t>(); ap.cur_a_kind = c->a_kind.as<uint8_t>();
+    ap.part_weight = c->part_weight.as<int32_t>(); ap.part_has_weight = c->part_has_weight.as<uint8_t>();
+    RESERVE(wire_adopt_res, sizeof(int32_t) * kWireAdoptResWords);
+    ap.res = c->wire_adopt_res.as<int32_t>();
+    int32_t vr[kWireAdoptResWords] = {0};
+    vr[kWaResFirstLong] = vr[kWaResFirstMissing] = vr[kWaResFirstDup] = INT_MAX;
+    if (PM > 0 || P > 0) {
+        {
+            Mover up(c, true);
+            c->stage.used = 0;                           // (the stream is idle here)
+            if ((st = up.copy(ap.res, vr, sizeof vr))) return st;
+            if ((st = up.flush())) return st;
+        }
+        const int wgs = cdiv(PM > P ? PM : P, 256);
+        BLANCE_LAUNCH(k_wire_adopt_sum, wgs < kWireAdoptMaxWgs ? wgs : kWireAdoptMaxWgs, 256, 4 * 9 * sizeof(unsigned long long), sm, ap);
+        HIPTRY(hipEventRecord(c->ev1, sm));
+        HIPTRY(read_back(c, vr, ap.res, sizeof vr));
+        HIPTRY(stream_sync(c));
+        HIPTRY(hipGetLastError());
+        float ms = 0.f;
+        HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        wa->device_ms = ms;
+    }
+    long long r64[5];
+    memcpy(r64, vr + 4, sizeof r64);
+    UploadSummary sum;
+    sum.ps = PartsSummary{vr[kWaResLongest], vr[kWaResFresh], r64[kWaRes64Cap], c->sum_abs_weight, r64[kWaRes64Prev]};
+    sum.assign_kinds = (uint32_t)vr[kWaResKinds];
+    sum.na = r64[kWaRes64Total];
+
+    // the refusals: all of them before the problem is touched
+    auto refuse = [&](int why, int64_t at, const char* text) {
+        wa->why = why; wa->why_at = at;
+        return fail(BLANCE_ERR_UNSUPPORTED, "refused: %s (BLANCE_WIRE_ADOPT_* %ld)", text, (long)why);
+    };
+    bool any_removed = false, any_pass = false;
+    for (int n = 0; n < NX; n++) any_removed |= wa->node_removed[n] != 0;
+    for (int32_t k : c->state_constraints) any_pass |= k > 0;
+    if (vr[kWaResFirstLong] != INT_MAX)
+        return refuse(BLANCE_WIRE_ADOPT_LIST_TOO_LONG, vr[kWaResFirstLong], "a list longer than the uploaded problem's longest: upload again");
+    if (assign_too && vr[kWaResFirstMissing] != INT_MAX)
+        return refuse(BLANCE_WIRE_ADOPT_PARTITION_MISSING, vr[kWaResFirstMissing], "a partition to assign is not in the document");
+    if (assign_too && vr[kWaResFirstDup] != INT_MAX)
+        return refuse(BLANCE_WIRE_ADOPT_DUPLICATE_NODE, vr[kWaResFirstDup], "a node twice in a list to assign");
+    if (vr[kWaResFirstMissing] != INT_MAX && any_removed && any_pass)
+        return refuse(BLANCE_WIRE_ADOPT_REMOVED_WITHOUT_PREV, vr[kWaResFirstMissing],
+                      "nodesToRemove non-empty but a partition is missing from prevMap (plan.go:545)");
+    if (adopt_load_overflows(c, sum.ps, keep))
+        return refuse(BLANCE_WIRE_ADOPT_LOAD_OVERFLOW, -1, "partition weights overflow the int32 load tables");
+
+    blance_problem q = adopt_shell(c, wa->node_removed, wa->node_added, wa->nodes_to_add_nil);
+    q.n_prev = (int32_t)wl.n_parts_seen + (keep ? c->np_later - P : 0);   // (np_later - P: the old prevMap's keys outside partitionsToAssign)
+    q.n_loads = keep ? h.n_loads : 0;
+    ap.a_off = c->a_off.as<int32_t>(); ap.a_kind = c->a_kind.as<uint8_t>();
+    ap.p_off = c->p_off.as<int32_t>(); ap.p_kind = c->p_kind.as<uint8_t>();
+    ap.part_in_prev = c->part_in_prev.as<uint8_t>(); ap.part_never_equal = c->part_never_equal.as<uint8_t>();
+    st = adopt_swap(c, q, sum, keep, assign_too ? total : -1, total, [&]() -> int {
+        ap.a_nodes = c->a_nodes.as<int32_t>(); ap.p_nodes = c->p_nodes.as<int32_t>();
+        BLANCE_LAUNCH_NOSYNC(k_wire_adopt_write, wire_adopt_write_wgs(P, M, total), 256, 0, sm, ap);
+        HIPTRY(hipEventRecord(c->ev1, sm));
+        return BLANCE_OK;
+    });
+    if (st) return st;
+    float ms = 0.f;
+    HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    wa->device_ms = ms;
+    wa->result_capacity = sum.ps.cap;
+    return BLANCE_OK;
+}
+
+extern "C" int blance_wire_adopt(blance_ctx* c, struct blance_wire_adopt* wa) {
+    return enter(c, [&]() -> int {
+        if (!wa) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        const auto t0 = std::chrono::steady_clock::now();
+        const int st = wire_adopt_locked(c, wa);
+        wa->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();   // whatever the status
         return st;
     });
 }

@@ -20,7 +20,8 @@ EXPORTS = ["blance_abi_version", "blance_last_error", "blance_result_capacity", 
            "blance_comm_unique_id", "blance_comm_init_rccl", "blance_comm_set", "blance_comm_stats",
            "blance_is_emulated", "blance_host_alloc", "blance_host_free", "blance_comm_time_ms", "blance_host_trim",
            "blance_plan_moves_capacity", "blance_plan_moves_get", "blance_plan_wire_names", "blance_plan_wire_get",
-           "blance_wire_dict_create", "blance_wire_dict_destroy", "blance_wire_decode_device", "blance_plan_adopt"]
+           "blance_wire_dict_create", "blance_wire_dict_destroy", "blance_wire_decode_device", "blance_plan_adopt",
+           "blance_wire_adopt"]
 
 _libs = {}
 
@@ -119,6 +120,9 @@ def load_library(path=None):
     if hasattr(lib, "blance_plan_adopt"):                    # likewise: Planner.adopt refuses without it
         lib.blance_plan_adopt.restype = C.c_int
         lib.blance_plan_adopt.argtypes = [C.c_void_p, C.POINTER(abi.Adopt)]
+    if hasattr(lib, "blance_wire_adopt"):                    # likewise: Planner.adopt_wire refuses without it
+        lib.blance_wire_adopt.restype = C.c_int
+        lib.blance_wire_adopt.argtypes = [C.c_void_p, C.POINTER(abi.WireAdopt)]
     if lib.blance_abi_version() != abi.ABI_VERSION:
         raise ImportError("ABI version mismatch")
     _libs[path] = lib
@@ -234,6 +238,18 @@ class WireDict:
         if self._h and getattr(self.planner, "_h", None):
             self.planner.lib.blance_wire_dict_destroy(self.planner._h, self._h)
         self._h = None
+
+
+class _ResultShape:
+    """What abi.FlatResult reads of a problem, for the problem a planner holds after adopt_wire: the uploaded problem's sizes
+    and the result capacity blance_wire_adopt reported."""
+
+    def __init__(self, fp, capacity):
+        self.scalars = fp.scalars
+        self._capacity = capacity
+
+    def result_capacity(self):
+        return self._capacity
 
 
 class Planner:
@@ -358,6 +374,7 @@ class Planner:
         """blance_plan with the caller's result buffers (a FlatResult made for this problem shape) written again."""
         self._fp = fp
         self._adopted = False
+        self._wire_adopted = None
         self._check(self.lib.blance_plan(self._h, C.byref(fp.as_struct()), C.byref(res.struct)))
         return res
 
@@ -366,6 +383,7 @@ class Planner:
         res = abi.FlatResult(fp)
         self._fp = fp
         self._adopted = False
+        self._wire_adopted = None
         self._check(self.lib.blance_plan(self._h, C.byref(fp.as_struct()), C.byref(res.struct)))
         return res
 
@@ -382,6 +400,7 @@ class Planner:
         rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
         info = abi.BatchInfo()
         self._adopted = False
+        self._wire_adopted = None
         self._check(self.lib.blance_plan_batch(self._h, n, pbs, rss, C.byref(info)))
         return results, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
@@ -449,6 +468,7 @@ class Planner:
         rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
         info = abi.BatchInfo()
         self._adopted = False
+        self._wire_adopted = None
         self._check(self.lib.blance_plan_batch_moves(self._h, n, pbs, rss,
                                                      ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
                                                      C.byref(info)))
@@ -488,6 +508,7 @@ class Planner:
         rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
         info = abi.BatchInfo()
         self._adopted = False
+        self._wire_adopted = None
         self._check(self.lib.blance_plan_batch_stats(self._h, n, pbs, rss,
                                                      mv_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
                                                      st_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.PlanStats))),
@@ -546,6 +567,9 @@ class Planner:
             fp = getattr(self, "_fp", None)
             if fp is None:
                 raise BlanceError(abi.ERR_BAD_ARG, "nothing planned yet")
+            if capacity is None and getattr(self, "_wire_adopted", None) is not None:
+                # prevMap is an adopted document: its entries, and the new plan's at most the result capacity
+                capacity = sum(self._wire_adopted)
             if capacity is None and getattr(self, "_adopted", False):
                 # prevMap is an adopted plan: at most the uploaded problem's result capacity, like the new plan
                 capacity = 2 * fp.result_capacity()
@@ -704,6 +728,7 @@ class Planner:
     def upload(self, fp):
         self._fp = fp
         self._adopted = False
+        self._wire_adopted = None
         self._check(self.lib.blance_upload(self._h, C.byref(fp.as_struct())))
 
     def adopt(self, node_removed=None, node_added=None, nodes_to_add_nil=True, keep_prev_only=False):
@@ -731,6 +756,55 @@ class Planner:
         ad.keep_prev_only = int(bool(keep_prev_only))
         self._check(self.lib.blance_plan_adopt(self._h, C.byref(ad)))
         self._adopted = True
+        if getattr(self, "_wire_adopted", None) is not None:     # (an adopted plan is no larger than the capacity it was planned with)
+            self._wire_adopted = (self._wire_adopted[0], self._wire_adopted[0])
+
+    def adopt_wire(self, wdict, doc, node_removed=None, node_added=None, nodes_to_add_nil=True, assign_too=True,
+                   keep_prev_only=False):
+        """blance_wire_adopt(): the PartitionMap document `doc` (bytes, or a uint8 numpy array -- one from a HostArena is read
+        by DMA where it lies), decoded on the device against `wdict`, becomes prevMap -- and with assign_too the partitions to
+        assign -- of the problem this planner holds, where the decoder left it (problem.wire_adopted_problem is the
+        definition), with the node change of the next call.  Needs an uploaded problem, not a plan.  Returns a dict: refusal,
+        refusal_at (the document's own refusal, as decode_wire reports it), why, why_at (abi.WIRE_ADOPT: the document decoded
+        but the problem cannot be taken), n_node_refs, n_parts_seen, result_capacity, device_ms, total_ms, and adopted: True
+        when the planner now holds the new problem.  Both kinds of refusal are returned, not raised -- the planner is then as
+        it was; planner.adopt_partition_map is the switch to the host route.  Every other error status raises."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_wire_adopt"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_wire_adopt (build the current sources)")
+        fp = getattr(self, "_fp", None)
+        if fp is None:
+            raise BlanceError(abi.ERR_BAD_ARG, "nothing uploaded yet")
+        NX = fp.scalars["n_nodes_ext"]
+        arrs = []
+        for a in (node_removed, node_added):
+            a = np.zeros(NX, dtype=np.uint8) if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+            if a.size != NX:
+                raise ValueError("node_removed / node_added: one byte per node name of the problem (%d)" % NX)
+            arrs.append(a if a.size else np.zeros(1, dtype=np.uint8))
+        if isinstance(doc, np.ndarray):
+            src = np.ascontiguousarray(doc).view(np.uint8).reshape(-1)
+            ptr, n = src.ctypes.data, int(src.size)
+        else:
+            src = bytes(doc)
+            ptr, n = C.cast(C.c_char_p(src), C.c_void_p).value, len(src)
+        wa = abi.WireAdopt()
+        wa.dict, wa.json, wa.len = wdict._h, ptr, n
+        wa.node_removed, wa.node_added = [a.ctypes.data_as(C.POINTER(C.c_uint8)) for a in arrs]
+        wa.nodes_to_add_nil = int(bool(nodes_to_add_nil))
+        wa.assign_too = int(bool(assign_too))
+        wa.keep_prev_only = int(bool(keep_prev_only))
+        st = self.lib.blance_wire_adopt(self._h, C.byref(wa))
+        info = {name: getattr(wa, name) for name in ("refusal", "refusal_at", "why", "why_at", "n_node_refs", "n_parts_seen",
+                                                     "result_capacity", "device_ms", "total_ms")}
+        info["adopted"] = st == abi.OK
+        if st != abi.OK and not (st == abi.ERR_UNSUPPORTED and (wa.refusal != 0 or wa.why != 0)):
+            raise BlanceError(st, (self.lib.blance_last_error() or b"").decode())
+        if st == abi.OK:
+            self._adopted = True
+            # what download() and plan_moves size their arrays by: the new problem's result capacity and prevMap entries
+            self._wire_adopted = (int(wa.result_capacity), int(wa.n_node_refs))
+        return info
 
     def plan_resident(self):
         """Run the whole planNextMapEx loop on the uploaded problem; returns the
@@ -742,6 +816,9 @@ class Planner:
     def download(self, arena=None, into=None):
         """arena: a HostArena -- the result's arrays in page-locked memory (the device writes them by DMA); into: a FlatResult
         of an earlier download of the same problem shape, written again (no allocation)."""
-        res = into if into is not None else abi.FlatResult(self._fp, arena)
+        shape = self._fp
+        if into is None and getattr(self, "_wire_adopted", None) is not None:
+            shape = _ResultShape(self._fp, self._wire_adopted[0])
+        res = into if into is not None else abi.FlatResult(shape, arena)
         self._check(self.lib.blance_download(self._h, C.byref(res.struct)))
         return res

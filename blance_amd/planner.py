@@ -7,7 +7,7 @@ There is no CPU fallback in this package: inputs outside the device envelope
 raise problem.Unsupported / hip.BlanceError (the Go shim would call the Go
 planner there).
 """
-from . import hip, problem
+from . import abi, hip, problem
 
 MaxIterationsPerPlan = 10            # plan.go:21
 # plan.go:580: the hook that replaces the node sorter.  Anything but None (the default sorter) is a
@@ -271,6 +271,44 @@ def decode_partition_map(planner, wdict, doc):
         wm.close()
     return dict(out, refusal=got["refusal"], refusal_at=got["refusal_at"], device_ms=got["device_ms"],
                 total_ms=got["total_ms"], route="host")
+
+
+def adopt_partition_map(planner, wdict, doc, fp=None, node_removed=None, node_added=None, nodes_to_add_nil=True, assign_too=True,
+                        keep_prev_only=False, force_host=False):
+    """A PartitionMap document as the next call's prevMap (assign_too: and partitionsToAssign) of the problem `planner`
+    holds: on the device (Planner.adopt_wire).  A document the device refuses, or one with a list longer than the context's
+    rows hold, goes the host route: the host decoder (wire.decode, which raises wire.WireError for a syntax or type
+    error), problem.wire_adopted_problem of `fp` -- the problem the planner holds, as arrays; None: the one it uploaded
+    last, right only while nothing was adopted since -- and a fresh upload.  The other reasons (abi.WIRE_ADOPT: a missing
+    partition, a duplicate, a removal without prevMap, a load overflow) raise problem.Unsupported with .why / .why_at, on
+    either route.  force_host: the host route at once (tests).  Returns adopt_wire's dict with route ("device" / "host") and
+    problem (the host route's new problem, else None); plan_resident then plans."""
+    from . import wire
+    planner = planner or default_planner()
+    info = None
+    if not force_host:
+        info = planner.adopt_wire(wdict, doc, node_removed, node_added, nodes_to_add_nil, assign_too, keep_prev_only)
+        if info["adopted"]:
+            return dict(info, route="device", problem=None)
+        if not info["refusal"] and info["why"] != abi.WIRE_ADOPT["list_too_long"]:
+            e = problem.Unsupported("blance_wire_adopt refused: " + abi.WIRE_ADOPT_WHYS[info["why"]])
+            e.why, e.why_at = info["why"], info["why_at"]
+            raise e
+    fp = fp if fp is not None else getattr(planner, "_fp", None)
+    if fp is None:
+        raise ValueError("adopt_partition_map: no problem to adopt the document into")
+    wm = wire.decode(doc.tobytes() if hasattr(doc, "tobytes") else doc)
+    try:
+        lists = lists_of_wire_map(wm, wdict)
+    finally:
+        wm.close()
+    new = problem.wire_adopted_problem(fp, lists, node_removed, node_added, nodes_to_add_nil, assign_too, keep_prev_only,
+                                       row_stride=0xffff)      # (a fresh upload sizes its rows itself)
+    planner.upload(new)
+    out = {"refusal": 0, "refusal_at": -1, "why": 0, "why_at": -1, "device_ms": 0.0, "total_ms": 0.0}
+    out.update(info or {})
+    return dict(out, adopted=True, n_node_refs=lists["n_node_refs"], n_parts_seen=lists["n_parts_seen"],
+                result_capacity=new.result_capacity(), route="host", problem=new)
 
 
 def PlanNextMap(prevMap, partitionsToAssign, nodesAll, nodesToRemove, nodesToAdd, model,

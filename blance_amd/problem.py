@@ -442,6 +442,85 @@ def adopted_problem(fp, res, node_removed=None, node_added=None, nodes_to_add_ni
     return fp2
 
 
+def wire_adopted_problem(fp, lists, node_removed=None, node_added=None, nodes_to_add_nil=True, assign_too=True,
+                         keep_prev_only=False, row_stride=None):
+    """The problem blance_wire_adopt leaves on a context (include/blance_hip.h), as arrays: the call PlanNextMap(prevMap = the
+    decoded document `lists` -- part_kind [P], off [P*M + 1], kind [P*M], nodes, as Planner.decode_wire or
+    planner.lists_of_wire_map give them in fp's ids --, partitionsToAssign = the same with assign_too, else fp's;
+    nodesToRemove / nodesToAdd as given; everything else as in `fp`).  keep_prev_only: as in adopted_problem.
+    row_stride: the longest list the context's buffers hold (None: fp's own longest list or constraint, what an upload of fp
+    fixes; a caller that uploads the result afresh passes a bound nothing exceeds).  Raises Unsupported for the five `why`
+    cases of blance_wire_adopt (abi.WIRE_ADOPT), with the code in .why and the offender in .why_at."""
+    P, M, NX = int(fp.n_parts), int(fp.n_states), int(fp.n_nodes_ext)
+    part_kind = np.asarray(lists["part_kind"], dtype=np.uint8)[:P]
+    off = np.asarray(lists["off"], dtype=np.int64)[:P * M + 1] if P * M else np.zeros(1, dtype=np.int64)
+    kind = np.asarray(lists["kind"], dtype=np.uint8)[:P * M]
+    nodes = np.asarray(lists["nodes"], dtype=np.int32)[:int(off[-1])]
+    removed = np.zeros(NX, dtype=np.uint8) if node_removed is None else np.asarray(node_removed, dtype=np.uint8)
+    added = np.zeros(NX, dtype=np.uint8) if node_added is None else np.asarray(node_added, dtype=np.uint8)
+    if len(removed) != NX or len(added) != NX:
+        raise ValueError("node_removed / node_added: one byte per node name")
+    cons = np.asarray(fp.state_constraints[:M], dtype=np.int64)
+    if row_stride is None:
+        row_stride = max([1] + [int(k) for k in cons] + ([int(np.diff(fp.assign_off[:P * M + 1]).max()),
+                                                         int(np.diff(fp.prev_off[:P * M + 1]).max())] if P * M else []))
+
+    def refuse(why, at, text):
+        e = Unsupported(text)
+        e.why, e.why_at = abi.WIRE_ADOPT[why], int(at)
+        raise e
+
+    lens = np.diff(off)
+    absent = np.flatnonzero(part_kind == abi.LIST_ABSENT)
+    if (lens > row_stride).any():
+        refuse("list_too_long", np.flatnonzero(lens > row_stride)[0], "a list longer than the uploaded problem's longest: upload again")
+    if assign_too and absent.size:
+        refuse("partition_missing", absent[0], "a partition to assign is not in the document")
+    if assign_too:
+        for i in np.flatnonzero(lens >= 2):
+            lst = nodes[off[i]:off[i + 1]]
+            if len(np.unique(lst)) != len(lst):
+                refuse("duplicate_node", i, "a node twice in a list to assign")
+    if absent.size and removed.any() and (cons > 0).any():
+        refuse("removed_without_prev", absent[0], "nodesToRemove non-empty but a partition is not in prevMap (plan.go:545)")
+    w = np.ones(P, dtype=np.int64)
+    if not int(fp.partition_weights_nil):
+        w = np.where(np.asarray(fp.part_has_weight[:P]) != 0, np.abs(np.asarray(fp.part_weight[:P], dtype=np.int64)), 1)
+    stay = np.zeros(0, dtype=bool)
+    if keep_prev_only:
+        stay = np.asarray(fp.load_first_sweep_only[:int(fp.n_loads)]) == 0
+    per_part = (off[M::M] - off[:-1:M]) if P * M else np.zeros(P, dtype=np.int64)
+    abs_load = int((w * per_part)[part_kind != abi.LIST_ABSENT].sum())
+    abs_load += int(np.abs(np.asarray(fp.load_weight[:int(fp.n_loads)], dtype=np.int64)[stay]).sum()) if keep_prev_only else 0
+    abs_load += int(w.sum()) * max(1, int(np.maximum(cons, 0).sum())) * 2
+    if abs_load > INT32_MAX:
+        refuse("load_overflow", -1, "partition weights overflow the device's int32 load tables")
+
+    fp2 = abi.FlatProblem()
+    fp2.scalars = dict(fp.scalars)
+    for name, a in fp.arrays.items():
+        fp2.set(name, a.copy())
+    fp2.node_names, fp2.state_names, fp2.part_names = fp.node_names, fp.state_names, fp.part_names
+    for pre in ("prev", "assign") if assign_too else ("prev",):
+        fp2.set(pre + "_off", off if P * M else [0])
+        fp2.set(pre + "_nodes", nodes)
+        fp2.set(pre + "_kind", kind)
+    never = part_kind == abi.LIST_NIL
+    if lists.get("names_differ") is not None:             # (the host decoder's: a Name that is not the key never DeepEquals)
+        never = never | (np.asarray(lists["names_differ"], dtype=bool)[:P] & (part_kind != abi.LIST_ABSENT))
+    fp2.set("part_in_prev", (part_kind != abi.LIST_ABSENT).astype(np.uint8))
+    fp2.set("part_prev_never_equal", never.astype(np.uint8))
+    fp2.set("node_removed", removed)
+    fp2.set("node_added", added)
+    for name in ("load_state", "load_node", "load_weight", "load_first_sweep_only"):
+        fp2.set(name, np.asarray(fp.arrays[name][:int(fp.n_loads)])[stay] if keep_prev_only else [])
+    n_prev = int((part_kind != abi.LIST_ABSENT).sum())
+    if keep_prev_only:                                    # the old prevMap's keys outside partitionsToAssign
+        n_prev += int(fp.n_prev) - int((np.asarray(fp.part_in_prev[:P]) != 0).sum())
+    fp2.scalars.update(n_prev=n_prev, n_loads=int(stay.sum()), nodes_to_add_nil=int(bool(nodes_to_add_nil)))
+    return fp2
+
+
 def decode_result(fp, res):
     """Flat result -> ({name: {"name", "nodesByState"}}, {name: [warning strings]})."""
     M = fp.scalars["n_states"]

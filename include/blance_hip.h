@@ -482,6 +482,68 @@ typedef struct blance_adopt {
 } blance_adopt;
 int blance_plan_adopt(blance_ctx* ctx, const blance_adopt* ad);
 
+/* ---- a PartitionMap document as the next call's prevMap (additive to ABI 6: look the symbol up before use) ----
+ * blance_plan_adopt hands over the map this context planned.  A caller that reads the map the cluster really has -- a
+ * json.Marshal(PartitionMap) document, the planned one only when every move of the last round completed -- plans with
+ * prevMap = partitionsToAssign = that document.  blance_wire_adopt decodes it on the device as blance_wire_decode_device does
+ * and makes the decoded lists the lists of the problem the context holds, where they lie: per round only
+ * the document's bytes cross the bus.
+ * Precondition: the context holds an uploaded problem (a plan is not required: upload a skeleton once, then adopt
+ * documents) and has no communicator.  dict, json, len: as for blance_wire_decode_device; the dictionary's n_parts /
+ * n_nodes_ext / n_states equal the held problem's, and it is the caller's contract that its ids are the problem's ids.
+ * After a successful call the context holds, as if uploaded, the problem P': everything of the held problem, except
+ *   - prev_off / prev_nodes / prev_kind = the decoded lists; part_in_prev[p] = (part_kind[p] != BLANCE_LIST_ABSENT);
+ *     part_prev_never_equal[p] = (part_kind[p] == BLANCE_LIST_NIL) (a nil NodesByState never DeepEquals a result);
+ *   - assign_too == 1: assign_* = the same lists (prevMap' = partitionsToAssign' = the document);
+ *     assign_too == 0: assign_* stay as they are on the context, uploaded or adopted last;
+ *   - node_removed, node_added, nodes_to_add_nil as given here;
+ *   - n_prev = n_parts_seen, plus with keep_prev_only == 1 the old prevMap's keys outside partitionsToAssign;
+ *   - keep_prev_only == 1: the load entries with load_first_sweep_only == 0 stay, the others go; 0: n_loads = 0.
+ * Nothing is planned then: blance_plan_resident plans P'; until it has, the readers refuse as after blance_plan_adopt.
+ * Wire names and every blance_wire_dict stay valid.  After the next plan blance_plan_moves_get gives the moves from the
+ * document's map (beg_other NULL).  result_capacity is blance_result_capacity of P' (the sum of max(k, length) over its lists
+ * to assign): with assign_too it can exceed the uploaded problem's, size blance_result by it.
+ * Every refusal is decided before the problem is touched; after one blance_download, the three readers and
+ * blance_plan_resident answer as before the call.
+ *   1. the document's own: BLANCE_ERR_UNSUPPORTED, refusal / refusal_at exactly as blance_wire_decode_device gives them,
+ *      why == 0;
+ *   2. the document decoded but P' is no problem this context can take: BLANCE_ERR_UNSUPPORTED, refusal == 0, `why` one of
+ *      BLANCE_WIRE_ADOPT_* (the first of them in the order below), why_at the smallest offending p * n_states + state, or p;
+ *   3. BLANCE_ERR_BAD_ARG: a NULL argument, a dictionary of another context, no problem on the context, dictionary sizes
+ *      that differ from the problem's, a non-zero `reserved`; BLANCE_ERR_UNSUPPORTED with refusal == why == 0: a communicator.
+ * A device failure behind the refusals leaves the context without a problem, as a failed blance_upload does. */
+#define BLANCE_WIRE_ADOPT_LIST_TOO_LONG        1  /* a list longer than the row stride the upload fixed (the longest list or
+                                                     constraint of the uploaded problem): upload again.  why_at: p * M + state */
+#define BLANCE_WIRE_ADOPT_PARTITION_MISSING    2  /* assign_too and a partition of the dictionary is not in the document (the
+                                                     partitions to assign would change).  why_at: p                           */
+#define BLANCE_WIRE_ADOPT_DUPLICATE_NODE       3  /* assign_too and a node twice in one list (duplicates in a document that
+                                                     becomes prevMap only are kept).  why_at: p * M + state                   */
+#define BLANCE_WIRE_ADOPT_REMOVED_WITHOUT_PREV 4  /* a partition is not in the document, node_removed names a node and some
+                                                     state has constraints > 0: the reference panics (plan.go:545).  why_at: p */
+#define BLANCE_WIRE_ADOPT_LOAD_OVERFLOW        5  /* blance_validate's bound on the int32 load tables, for P'.  why_at: -1      */
+/* (no typedef: in C the function below would collide with it; write `struct blance_wire_adopt`) */
+struct blance_wire_adopt {
+    /* in */
+    const blance_wire_dict* dict;
+    const char*    json;
+    size_t         len;
+    const uint8_t* node_removed;    /* [n_nodes_ext] nodesToRemove of the next call */
+    const uint8_t* node_added;      /* [n_nodes_ext] nodesToAdd of the next call    */
+    int32_t        nodes_to_add_nil;
+    int32_t        assign_too;
+    int32_t        keep_prev_only;
+    int32_t        reserved[4];     /* zero */
+    /* out */
+    int32_t        refusal;         /* BLANCE_WIRE_REFUSED_*, 0 when the document decoded */
+    int64_t        refusal_at;      /* byte offset, -1 when it decoded */
+    int64_t        n_node_refs, n_parts_seen;
+    int64_t        result_capacity; /* of P' (written on success) */
+    int32_t        why;             /* BLANCE_WIRE_ADOPT_*, 0 when P' was taken */
+    int64_t        why_at;          /* -1 when why == 0 */
+    double         device_ms, total_ms;   /* the call's kernels (the decoder's, the summary, the write); the whole call */
+};
+int blance_wire_adopt(blance_ctx* ctx, struct blance_wire_adopt* wa);
+
 /* ---- one plan on several GPUs (BASELINE.json config 4) ------------------------------------
  * The steps of a state pass that runs as region chains (one chain per hierarchy region)
  * shard over the ranks by region: every rank holds the whole problem (upload the same problem on
