@@ -342,3 +342,16 @@ PLAN_STATS_DTYPE = np.dtype({
     "formats": [np.int32, np.int32] + [np.uint64] * len(PLAN_STATS_ARRAYS),
     "offsets": [getattr(PlanStats, f).offset for f in ("n_states", "n_nodes_next") + PLAN_STATS_ARRAYS],
     "itemsize": C.sizeof(PlanStats)})
+
+
+class BatchWire(C.Structure):
+    """blance_batch_wire of include/blance_batch.h (blance_plan_batch_wire): one problem's document request and buffer."""
+    _fields_ = [("names", C.c_void_p), ("buf", C.c_void_p), ("cap", C.c_size_t), ("need", C.c_size_t)]
+
+
+# blance_batch_wire as a numpy record (pointers as addresses): Planner.plan_batch_wire fills many at once
+BATCH_WIRE_DTYPE = np.dtype({
+    "names": ["names", "buf", "cap", "need"],
+    "formats": [np.uint64] * 4,
+    "offsets": [getattr(BatchWire, f).offset for f in ("names", "buf", "cap", "need")],
+    "itemsize": C.sizeof(BatchWire)})

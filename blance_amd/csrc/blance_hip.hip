@@ -396,6 +396,7 @@ struct blance_ctx : CtxHandles {
     DevBuf f_tot, f_g, f_top_g, f_top_n, f_row_count, f_m, f_moff, f_keys_a, f_keys_b, f_vals_a, f_vals_b, f_hist, f_comp;
     int64_t out_capacity = 0;
     DevBuf batch_in, batch_sc, batch_out;   // blance_plan_batch: descriptors + packed problems, working state, results
+    DevBuf batch_doc;                       // blance_plan_batch_wire: the documents of the batched problems, one after another
 
     // device: problem
     DevBuf node_removed, node_added, node_weight, node_has_weight, alive, zeros_nx, node_leaf_pos;
@@ -3761,11 +3762,16 @@ bool wire_escape(const WireBlob& b, const int32_t* order, const char* tail, std:
 }
 }  // namespace
 
-static int wire_names_locked(blance_ctx* c, const blance_wire_names* nm) {
-    if (!c->uploaded) return fail(BLANCE_ERR_BAD_ARG, "no problem on the context (blance_upload or blance_plan first)");
-    const blance_problem& h = c->h;
-    const WireBlob part{nm->part_bytes, nm->part_off, h.n_parts}, node{nm->node_bytes, nm->node_off, h.n_nodes_ext},
-        state{nm->state_bytes, nm->state_off, h.n_states};
+// What the document needs of the names alone, prepared on the host: the partitions' order, every string escaped.
+struct WirePrepared {
+    std::vector<int32_t> order, sorder, poff, noff, soff;
+    std::string pesc, nesc, sesc;
+};
+
+// pure host: the checks of the names and their prepared tables (blance_plan_wire_names and blance_batch_names_create)
+static int wire_prepare(const blance_wire_names* nm, int64_t n_parts, int64_t n_nodes_ext, int64_t n_states, WirePrepared& w) {
+    const WireBlob part{nm->part_bytes, nm->part_off, n_parts}, node{nm->node_bytes, nm->node_off, n_nodes_ext},
+        state{nm->state_bytes, nm->state_off, n_states};
     for (const WireBlob* b : {&part, &node, &state}) {
         if (!b->off) return fail(BLANCE_ERR_BAD_ARG, "null offsets");
         if (b->off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "name offsets must start at 0");
@@ -3773,33 +3779,47 @@ static int wire_names_locked(blance_ctx* c, const blance_wire_names* nm) {
             if (b->off[i + 1] < b->off[i]) return fail(BLANCE_ERR_BAD_ARG, "name offsets not monotone");
         if (b->off[b->n] > 0 && !b->bytes) return fail(BLANCE_ERR_BAD_ARG, "null name bytes");
     }
-    std::vector<int32_t> order, sorder, poff, noff, soff;
-    if (!wire_sort(state, sorder)) return fail(BLANCE_ERR_BAD_ARG, "two states with one name");
-    if (!wire_sort(part, order))
+    if (!wire_sort(state, w.sorder)) return fail(BLANCE_ERR_BAD_ARG, "two states with one name");
+    if (!wire_sort(part, w.order))
         return fail(BLANCE_ERR_UNSUPPORTED, "two partitions with one name (the reference's map would keep one of them)");
-    std::string pesc, nesc, sesc;
-    if (!wire_escape(part, order.data(), "", pesc, poff) || !wire_escape(node, nullptr, "", nesc, noff) ||
-        !wire_escape(state, sorder.data(), ":", sesc, soff))
+    if (!wire_escape(part, w.order.data(), "", w.pesc, w.poff) || !wire_escape(node, nullptr, "", w.nesc, w.noff) ||
+        !wire_escape(state, w.sorder.data(), ":", w.sesc, w.soff))
         return fail(BLANCE_ERR_UNSUPPORTED, "the escaped names take 2^31 bytes or more");
+    return BLANCE_OK;
+}
+
+// the eight prepared tables in the order of c->wire[0..7]: order, partitions' bytes and offsets, nodes', states', state_id
+struct WireTables { const void* p[8]; size_t bytes[8]; };
+
+static int wire_tables_upload_locked(blance_ctx* c, const WireTables& t) {
     HIPTRY(hipSetDevice(c->device));
     c->wire_names = false;                               // (the buffers are written again from here on)
-    struct Up { DevBuf& b; const void* src; size_t bytes; };
-    const Up ups[] = {{c->wire[0], order.data(), sizeof(int32_t) * order.size()}, {c->wire[1], pesc.data(), pesc.size()},
-                      {c->wire[2], poff.data(), sizeof(int32_t) * poff.size()},   {c->wire[3], nesc.data(), nesc.size()},
-                      {c->wire[4], noff.data(), sizeof(int32_t) * noff.size()},   {c->wire[5], sesc.data(), sesc.size()},
-                      {c->wire[6], soff.data(), sizeof(int32_t) * soff.size()},   {c->wire[7], sorder.data(), sizeof(int32_t) * sorder.size()}};
     Mover up(c, true);
     c->stage.used = 0;                                   // (the stream is idle between calls)
     int e = 0;
-    for (const Up& u : ups) {
-        if (u.b.reserve(u.bytes + 16)) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-        if ((e = up.copy(u.b.p, u.src, u.bytes))) return e;
+    for (int i = 0; i < 8; i++) {
+        if (c->wire[i].reserve(t.bytes[i] + 16)) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        if ((e = up.copy(c->wire[i].p, t.p[i], t.bytes[i]))) return e;
     }
     if ((e = up.flush())) return e;
     HIPTRY(stream_sync(c));                              // nothing of this frame is read after the call
     HIPTRY(hipGetLastError());
     c->wire_names = true;
     return BLANCE_OK;
+}
+
+static int wire_names_locked(blance_ctx* c, const blance_wire_names* nm) {
+    if (!c->uploaded) return fail(BLANCE_ERR_BAD_ARG, "no problem on the context (blance_upload or blance_plan first)");
+    const blance_problem& h = c->h;
+    WirePrepared w;
+    const int st = wire_prepare(nm, h.n_parts, h.n_nodes_ext, h.n_states, w);
+    if (st) return st;
+    const WireTables t{{w.order.data(), w.pesc.data(), w.poff.data(), w.nesc.data(), w.noff.data(), w.sesc.data(), w.soff.data(),
+                        w.sorder.data()},
+                       {sizeof(int32_t) * w.order.size(), w.pesc.size(), sizeof(int32_t) * w.poff.size(), w.nesc.size(),
+                        sizeof(int32_t) * w.noff.size(), w.sesc.size(), sizeof(int32_t) * w.soff.size(),
+                        sizeof(int32_t) * w.sorder.size()}};
+    return wire_tables_upload_locked(c, t);
 }
 
 extern "C" int blance_plan_wire_names(blance_ctx* c, const blance_wire_names* nm) {
@@ -4300,6 +4320,7 @@ struct BatchItem {
     int64_t in_words, sc_words, out_words;
     int mi = -1;        // its BatchMovesDesc, when the caller asks for its moves
     int si = -1;        // its BatchStatsDesc, when the caller asks for its statistics
+    int wi = -1;        // its BatchWireDesc, when the caller asks for its document
 };
 
 int batch_list_len(const blance_problem* pb) {
@@ -4483,6 +4504,74 @@ extern "C" int64_t blance_batch_moves_capacity(const blance_problem* pb, const b
     return cap;
 }
 
+// ---- the prepared names of one index (blance_batch_names): wire_prepare's tables as one block of int32
+// words, the block a batch copies behind a problem's packed input slice (k_batch_wire.h reads it through its header)
+struct blance_batch_names {
+    int32_t n_parts = 0, n_nodes_ext = 0, n_states = 0;
+    std::vector<int32_t> block;                          // kBatchNamesHdr word offsets, then the tables
+    size_t part_esc_bytes = 0, state_esc_bytes = 0;      // the sums of blance_batch_wire_capacity
+    int32_t node_esc_max = 0;                            // the longest escaped node name
+    WireTables tables;                                   // the same tables as c->wire[0..7] wants them (the single path)
+};
+
+extern "C" int blance_batch_names_create(const blance_wire_names* names, int32_t n_parts, int32_t n_nodes_ext, int32_t n_states,
+                                         blance_batch_names** out) {
+    return guarded([&]() -> int {
+        if (!names || !out) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        if (n_parts < 0 || n_nodes_ext < 0 || n_states < 0) return fail(BLANCE_ERR_BAD_ARG, "negative size");
+        WirePrepared w;
+        const int st = wire_prepare(names, n_parts, n_nodes_ext, n_states, w);
+        if (st) return st;
+        std::unique_ptr<blance_batch_names> nm(new blance_batch_names);
+        nm->n_parts = n_parts; nm->n_nodes_ext = n_nodes_ext; nm->n_states = n_states;
+        nm->part_esc_bytes = w.pesc.size();
+        nm->state_esc_bytes = w.sesc.size();
+        for (int32_t x = 0; x < n_nodes_ext; x++) nm->node_esc_max = std::max(nm->node_esc_max, w.noff[(size_t)x + 1] - w.noff[(size_t)x]);
+        // kNamesOrder .. kNamesStateEsc, each table at a multiple of 4 words
+        const void* src[8] = {w.order.data(), w.poff.data(), w.noff.data(), w.soff.data(), w.sorder.data(),
+                              w.pesc.data(), w.nesc.data(), w.sesc.data()};
+        const size_t bytes[8] = {sizeof(int32_t) * w.order.size(), sizeof(int32_t) * w.poff.size(), sizeof(int32_t) * w.noff.size(),
+                                 sizeof(int32_t) * w.soff.size(), sizeof(int32_t) * w.sorder.size(),
+                                 w.pesc.size(), w.nesc.size(), w.sesc.size()};
+        size_t words = kBatchNamesHdr, at[8];
+        for (int i = 0; i < 8; i++) { at[i] = words; words += (((bytes[i] + 3) / 4) + 3) & ~(size_t)3; }
+        if (words > (size_t)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "the escaped names take 2^31 bytes or more");
+        nm->block.assign(words, 0);
+        for (int i = 0; i < 8; i++) {
+            nm->block[(size_t)i] = (int32_t)at[i];
+            if (bytes[i]) memcpy(nm->block.data() + at[i], src[i], bytes[i]);
+        }
+        const int32_t* b = nm->block.data();
+        // (c->wire[0..7]: order, partitions' bytes, their offsets, nodes' bytes, offsets, states' bytes, offsets, state_id)
+        const int to_wire[8] = {kNamesOrder, kNamesPartEsc, kNamesPartOff, kNamesNodeEsc, kNamesNodeOff, kNamesStateEsc,
+                                kNamesStateOff, kNamesStateId};
+        for (int i = 0; i < 8; i++) { nm->tables.p[i] = b + at[to_wire[i]]; nm->tables.bytes[i] = bytes[to_wire[i]]; }
+        *out = nm.release();
+        return BLANCE_OK;
+    });
+}
+
+extern "C" void blance_batch_names_destroy(blance_batch_names* nm) { delete nm; }
+
+extern "C" size_t blance_batch_wire_capacity(const blance_problem* pb, const blance_batch_names* nm) {
+    if (!pb || !nm || pb->n_parts < 0 || pb->n_states < 0) return 0;
+    const size_t P = (size_t)pb->n_parts, M = (size_t)pb->n_states;
+    return 2 + 29 * P + 2 * nm->part_esc_bytes + P * (nm->state_esc_bytes + 5 * M) +
+           (size_t)blance_result_capacity(pb) * ((size_t)nm->node_esc_max + 1);
+}
+
+namespace {
+// the document request of one problem: the names object made for its sizes, the buffer, its capacity
+int batch_wire_check(const blance_problem* pb, const blance_batch_wire* wr) {
+    if (!wr->names || !wr->buf) return fail(BLANCE_ERR_BAD_ARG, "null names or null document buffer");
+    if (wr->names->n_parts != pb->n_parts || wr->names->n_nodes_ext != pb->n_nodes_ext || wr->names->n_states != pb->n_states)
+        return fail(BLANCE_ERR_BAD_ARG, "the names were made for other sizes than the problem's");
+    if (pb->max_iterations <= 0) return fail(BLANCE_ERR_BAD_ARG, "a document asked for a problem with max_iterations <= 0 (no map)");
+    if (wr->cap < blance_batch_wire_capacity(pb, wr->names)) return fail(BLANCE_ERR_CAPACITY, "document capacity too small");
+    return BLANCE_OK;
+}
+}  // namespace
+
 // the last error as that of problem i of a batch
 static int fail_problem(int st, int i) {
     const std::string why = g_last_error;
@@ -4490,13 +4579,15 @@ static int fail_problem(int st, int i) {
 }
 
 static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
-                             blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_info* info) {
+                             blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_wire* const* wrs,
+                             blance_batch_info* info) {
     const auto t_start = std::chrono::steady_clock::now();
     if (c->comm.n_ranks > 1 || c->rccl_comm) return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_batch on a context with a communicator");
     for (int i = 0; i < n; i++) {
         int st = batch_check(pbs[i], res[i]);
         if (!st && mvs && mvs[i]) st = batch_moves_check(pbs[i], mvs[i]);
         if (!st && sts && sts[i]) st = batch_stats_check(pbs[i], sts[i]);
+        if (!st && wrs && wrs[i]) st = batch_wire_check(pbs[i], wrs[i]);
         if (st) return fail_problem(st, i);
     }
     HIPTRY(hipSetDevice(c->device));
@@ -4509,7 +4600,9 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         for (int i = 0; i < n; i++) {
             BatchItem it;
             it.idx = i;
-            const bool in_env = batch_layout(pbs[i], it);
+            // (a document that may reach 2^31 bytes is the single path's to refuse: the batch's offsets are int32)
+            const bool in_env = batch_layout(pbs[i], it) &&
+                                !(wrs && wrs[i] && blance_batch_wire_capacity(pbs[i], wrs[i]->names) > (size_t)INT32_MAX);
             if (!in_env && cls == 64) fallback.push_back(i);
             if (in_env && it.threads == cls) items.push_back(it);
         }
@@ -4555,6 +4648,27 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         sds.push_back(sd);
     }
     const int ns = (int)sds.size();
+    // the documents of the batched problems that ask for them: the names block behind the input slice, the ranks' offsets
+    // in scratch, the length in the output slice; an empty map is written by the host
+    std::vector<BatchWireDesc> wds;
+    size_t doc_cap = 0;
+    for (int j = 0; j < nb && wrs; j++) {
+        BatchItem& it = items[j];
+        const blance_batch_wire* wr = wrs[it.idx];
+        if (!wr || it.d.P == 0) continue;
+        BatchWireDesc wd;
+        wd.desc = j;
+        wd.i_names = (int32_t)it.in_words;
+        it.in_words += (int64_t)wr->names->block.size();     // (a multiple of 4 words)
+        wd.s_len = (int32_t)it.sc_words;
+        it.sc_words += ((int64_t)it.d.P + 1 + 3) & ~3ll;
+        wd.o_total = (int32_t)it.out_words;
+        it.out_words += 4;
+        doc_cap += (blance_batch_wire_capacity(pbs[it.idx], wr->names) + 15) & ~(size_t)15;
+        it.wi = (int)wds.size();
+        wds.push_back(wd);
+    }
+    const int nw = (int)wds.size();
     int64_t launches = 0, steps = 0;
     double device_ms = 0.0;
     if (nb > 0) {
@@ -4570,7 +4684,8 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         }
         const size_t desc_bytes = ((sizeof(BatchDesc) * (size_t)nb) + 255) & ~(size_t)255;
         const size_t mdesc_bytes = ((sizeof(BatchMovesDesc) * (size_t)nm) + 255) & ~(size_t)255;
-        const size_t head_bytes = desc_bytes + mdesc_bytes + (((sizeof(BatchStatsDesc) * (size_t)ns) + 255) & ~(size_t)255);
+        const size_t sdesc_bytes = ((sizeof(BatchStatsDesc) * (size_t)ns) + 255) & ~(size_t)255;
+        const size_t head_bytes = desc_bytes + mdesc_bytes + sdesc_bytes + (((sizeof(BatchWireDesc) * (size_t)nw) + 255) & ~(size_t)255);
         const size_t in_bytes = head_bytes + sizeof(int32_t) * (size_t)in_words, out_bytes = sizeof(int32_t) * (size_t)out_words;
         struct Pinned { void* p = nullptr; ~Pinned() { pin_free(p); } } host;
         host.p = pin_alloc(in_bytes + out_bytes);
@@ -4592,11 +4707,17 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
                     memset(dst + md.i_ooff, 0, sizeof(int32_t) * ((size_t)P + 1));
                 }
             }
+            if (items[i].wi >= 0) {                      // the prepared names behind the input slice
+                const std::vector<int32_t>& blk = wrs[items[i].idx]->names->block;
+                memcpy((int32_t*)(h_in + head_bytes) + items[i].d.in_base + wds[items[i].wi].i_names, blk.data(), sizeof(int32_t) * blk.size());
+            }
         }
         if (nm > 0) memcpy(h_in + desc_bytes, mds.data(), sizeof(BatchMovesDesc) * (size_t)nm);
         if (ns > 0) memcpy(h_in + desc_bytes + mdesc_bytes, sds.data(), sizeof(BatchStatsDesc) * (size_t)ns);
-        if (c->batch_in.reserve(in_bytes) || c->batch_sc.reserve(sizeof(int32_t) * (size_t)sc_words + 256) ||
-            c->batch_out.reserve(out_bytes))
+        if (nw > 0) memcpy(h_in + desc_bytes + mdesc_bytes + sdesc_bytes, wds.data(), sizeof(BatchWireDesc) * (size_t)nw);
+        // (scratch: wire_total [nw] behind the problems' slices)
+        if (c->batch_in.reserve(in_bytes) || c->batch_sc.reserve(sizeof(int32_t) * ((size_t)sc_words + (size_t)nw) + 256) ||
+            c->batch_out.reserve(out_bytes) || (nw > 0 && c->batch_doc.reserve(doc_cap + 16)))
             return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
         HIPTRY(hipMemcpyAsync(c->batch_in.p, h_in, in_bytes, hipMemcpyHostToDevice, c->stream));
         BatchParams q;
@@ -4625,6 +4746,17 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             launch_batch_stats(c->stream, qs, ns, lds_stats);
             launches++;
         }
+        if (nw > 0) {
+            BatchWireParams qw;
+            qw.desc = q.desc;
+            qw.wdesc = (const BatchWireDesc*)(c->batch_in.as<char>() + desc_bytes + mdesc_bytes + sdesc_bytes);
+            qw.in = q.in; qw.sc = q.sc; qw.out = q.out;
+            qw.wire_total = q.sc + sc_words;
+            qw.doc = c->batch_doc.as<char>();
+            qw.stage = c->wire_stage;
+            launch_batch_wire(c->stream, qw, nw);
+            launches += 2;
+        }
         HIPTRY(hipGetLastError());
         HIPTRY(hipEventRecord(c->ev1, c->stream));
         HIPTRY(hipMemcpyAsync(h_out, c->batch_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -4636,6 +4768,29 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         for (const BatchItem& it : items) {
             const int32_t* o = h_out + it.d.out_base;
             if (o[5] != 1 || o[4] != 0) fallback.push_back(it.idx);
+        }
+        // the documents: their 16-rounded lengths summed as k_batch_wire_write summed them, one copy of exactly these bytes
+        struct Pinned docs;
+        std::vector<size_t> doc_base((size_t)nw, 0);
+        if (nw > 0) {
+            size_t doc_bytes = 0;
+            for (int w = 0; w < nw; w++) {
+                const BatchItem& it = items[wds[w].desc];
+                const int32_t* o = h_out + it.d.out_base;
+                doc_base[(size_t)w] = doc_bytes;
+                if (o[5] != 1 || o[4] != 0 || o[0] == 0) continue;
+                const size_t total = (size_t)(uint32_t)o[wds[w].o_total];
+                if (total > blance_batch_wire_capacity(pbs[it.idx], wrs[it.idx]->names))
+                    return fail_problem(fail(BLANCE_ERR_DEVICE, "k_batch_wire_size: a document longer than its bound"), it.idx);
+                doc_bytes += (total + 15) & ~(size_t)15;
+            }
+            if (doc_bytes > doc_cap) return fail(BLANCE_ERR_DEVICE, "k_batch_wire_size: the documents outgrow their buffer");
+            if (doc_bytes > 0) {
+                docs.p = pin_alloc(doc_bytes);
+                if (!docs.p) return fail(BLANCE_ERR_DEVICE, "page-locked staging block: hipHostMalloc failed");
+                HIPTRY(hipMemcpyAsync(docs.p, c->batch_doc.p, doc_bytes, hipMemcpyDeviceToHost, c->stream));
+                HIPTRY(stream_sync(c));
+            }
         }
         const double total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
         for (const BatchItem& it : items) {
@@ -4691,12 +4846,30 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
                     if (ps->rule_violations) ps->rule_violations[m] = v[1 + 6 * M + m];
                 }
             }
+            if (wrs && wrs[it.idx]) {                    // the document; an empty map is json.Marshal's "{}"
+                blance_batch_wire* wr = wrs[it.idx];
+                if (it.wi >= 0) {
+                    wr->need = (size_t)(uint32_t)o[wds[it.wi].o_total];
+                    if (wr->need) memcpy(wr->buf, (const char*)docs.p + doc_base[(size_t)it.wi], wr->need);
+                } else {
+                    wr->need = 2;
+                    memcpy(wr->buf, "{}", 2);
+                }
+            }
         }
     }
     const int n_fallback = (int)fallback.size();
     for (int i : fallback) {                             // the single-problem path: blance_plan
         int st = plan_whole_locked(c, pbs[i], res[i]);
         if (!st && sts && sts[i]) st = plan_stats_locked(c, sts[i], &launches);     // while the context still holds the plan
+        if (!st && wrs && wrs[i]) {                      // likewise: the path of blance_plan_wire_names / blance_plan_wire_get
+            st = wire_tables_upload_locked(c, wrs[i]->names->tables);
+            double wire_ms = 0.0;
+            if (!st) st = plan_wire_locked(c, wrs[i]->buf, wrs[i]->cap, &wrs[i]->need, &wire_ms);
+            if (!st && pbs[i]->n_parts > 0) launches += 2 + ((int64_t)pbs[i]->n_parts + 1 <= 4 * kScanTile ? 1 : 3);   // size, scan, write
+            device_ms += wire_ms;
+            c->wire_names = false;
+        }
         c->uploaded = c->planned = false;
         if (st) return fail_problem(st, i);
         launches += res[i]->kernel_launches;
@@ -4731,10 +4904,19 @@ extern "C" int blance_plan_batch_moves(blance_ctx* c, int32_t n, const blance_pr
     return blance_plan_batch_stats(c, n, pbs, res, mvs, nullptr, info);
 }
 
+extern "C" int blance_plan_batch_wire(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                                      blance_batch_moves* const* mvs, blance_plan_stats* const* sts,
+                                      blance_batch_wire* const* wrs, blance_batch_info* info) {
+    return enter(c, [&]() -> int {
+        if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
+        return plan_batch_locked(c, n, pbs, res, mvs, sts, wrs, info);
+    });
+}
+
 extern "C" int blance_plan_batch_stats(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
                                        blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_info* info) {
     return enter(c, [&]() -> int {
         if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
-        return plan_batch_locked(c, n, pbs, res, mvs, sts, info);
+        return plan_batch_locked(c, n, pbs, res, mvs, sts, nullptr, info);
     });
 }

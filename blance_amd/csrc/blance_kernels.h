@@ -308,4 +308,29 @@ struct BatchStatsParams {
     int32_t* out;
 };
 
+// The PartitionMap document of one batched problem (DESIGN.md §4.16 "k_batch_wire_size / k_batch_wire_write").  The names
+// block (a blance_batch_names' words, copied as they are) lies behind the problem's input slice: kBatchNamesHdr words with
+// the word offsets of its eight tables inside the block, then the tables.
+constexpr int kBatchWireThreads = 256;
+constexpr int kBatchNamesHdr = 8;         // order [P], part_off [P + 1] (by rank), node_off [NX + 1], state_off [M + 1],
+                                          // state_id [M], then the escaped bytes: partitions by rank, nodes by id, states
+enum { kNamesOrder = 0, kNamesPartOff, kNamesNodeOff, kNamesStateOff, kNamesStateId, kNamesPartEsc, kNamesNodeEsc, kNamesStateEsc };
+struct BatchWireDesc {
+    int32_t desc;                         // index of the problem's BatchDesc
+    int32_t i_names;                      // input slice: first word of the names block
+    int32_t s_len;                        // scratch slice: [P + 1] byte offsets of the ranks (k_batch_wire_size's scan)
+    int32_t o_total;                      // output slice: the document's length (one word of a region of four)
+};
+
+struct BatchWireParams {
+    const BatchDesc* desc;
+    const BatchWireDesc* wdesc;           // one workgroup each
+    const int32_t* in;
+    int32_t* sc;
+    int32_t* out;
+    int32_t* wire_total;                  // [nw] scratch: every document's length rounded up to 16 (0: problem skipped)
+    char* doc;                            // all documents, one after another at 16-byte aligned bases (k_batch_wire_write)
+    int32_t stage;                        // bytes of k_batch_wire_write's LDS stage
+};
+
 }  // namespace blance

@@ -55,4 +55,6 @@ void launch_batch_moves(hipStream_t stream, const BatchMovesParams& q, int n);
 // k_batch_stats (tu_batch.hip): the plan statistics of n batched problems, one workgroup each
 void launch_batch_stats(hipStream_t stream, const BatchStatsParams& q, int n, size_t lds);
 size_t batch_stats_lds(int M, int NX);               // dynamic LDS of one such workgroup
+// k_batch_wire_size, then k_batch_wire_write (tu_batch.hip): the PartitionMap documents of n batched problems, one workgroup each
+void launch_batch_wire(hipStream_t stream, const BatchWireParams& q, int n);
 }  // namespace blance

@@ -1,9 +1,10 @@
-// Translation unit of k_plan_batch, k_batch_moves and k_batch_stats: many small problems in one launch, and their launch
-// wrappers.
+// Translation unit of k_plan_batch, k_batch_moves, k_batch_stats and k_batch_wire_*: many small problems in one launch, and
+// their launch wrappers.
 #include "dev_prelude.h"
 #include "k_plan_batch.h"
 #include "k_batch_moves.h"
 #include "k_batch_stats.h"
+#include "k_batch_wire.h"
 
 namespace blance {
 
@@ -30,6 +31,14 @@ size_t batch_stats_lds(int M, int NX) {
 void launch_batch_stats(hipStream_t stream, const BatchStatsParams& q, int n, size_t lds) {
     if (n <= 0) return;
     BLANCE_LAUNCH(k_batch_stats, n, kBatchStatsThreads, lds, stream, q);
+}
+
+void launch_batch_wire(hipStream_t stream, const BatchWireParams& q0, int n) {
+    if (n <= 0) return;
+    BatchWireParams q = q0;                               // (the stage and the reduction words share 64 KB of LDS)
+    if ((size_t)q.stage > 64 * 1024 - kBatchWireRedLds) q.stage = (int32_t)(64 * 1024 - kBatchWireRedLds);
+    BLANCE_LAUNCH(k_batch_wire_size, n, kBatchWireThreads, kBatchWireSizeLds, stream, q);
+    BLANCE_LAUNCH(k_batch_wire_write, n, kBatchWireThreads, kBatchWireRedLds + (size_t)q.stage, stream, q);
 }
 
 }  // namespace blance

@@ -98,6 +98,18 @@ def load_library(path=None):
         lib.blance_plan_batch_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
                                                 C.POINTER(C.POINTER(abi.Result)), C.POINTER(C.POINTER(abi.BatchMoves)),
                                                 C.POINTER(C.POINTER(abi.PlanStats)), C.POINTER(abi.BatchInfo)]
+    if hasattr(lib, "blance_plan_batch_wire"):
+        lib.blance_batch_names_create.restype = C.c_int
+        lib.blance_batch_names_create.argtypes = [C.POINTER(abi.WireNames), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        lib.blance_batch_names_destroy.restype = None
+        lib.blance_batch_names_destroy.argtypes = [C.c_void_p]
+        lib.blance_batch_wire_capacity.restype = C.c_size_t
+        lib.blance_batch_wire_capacity.argtypes = [C.POINTER(abi.Problem), C.c_void_p]
+        lib.blance_plan_batch_wire.restype = C.c_int
+        lib.blance_plan_batch_wire.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
+                                               C.POINTER(C.POINTER(abi.Result)), C.POINTER(C.POINTER(abi.BatchMoves)),
+                                               C.POINTER(C.POINTER(abi.PlanStats)), C.POINTER(C.POINTER(abi.BatchWire)),
+                                               C.POINTER(abi.BatchInfo)]
     # declared in blance_hip.h, additive to ABI 6: an older library of the same version loads, Planner.plan_moves refuses
     if hasattr(lib, "blance_plan_moves_get"):
         lib.blance_plan_moves_get.restype = C.c_int
@@ -238,6 +250,26 @@ class WireDict:
         if self._h and getattr(self.planner, "_h", None):
             self.planner.lib.blance_wire_dict_destroy(self.planner._h, self._h)
         self._h = None
+
+
+class BatchNames:
+    """A blance_batch_names: the prepared names of one index for Planner.plan_batch_wire (Planner.batch_names).  Host memory
+    only, tied to no context: it may serve any number of calls and planners; close() / __del__ destroys it."""
+
+    def __init__(self, lib, handle, n_parts, n_nodes_ext, n_states):
+        self.lib, self._h = lib, handle
+        self.n_parts, self.n_nodes_ext, self.n_states = n_parts, n_nodes_ext, n_states
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.blance_batch_names_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _ResultShape:
@@ -474,6 +506,45 @@ class Planner:
                                                      C.byref(info)))
         return results, self._moves_unpack(state), {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
+    @staticmethod
+    def _stats_requests(fps, want):
+        """The statistics requests of a batch (want: one bool per problem).  Returns (the pointer array of the call, what
+        _stats_unpack needs -- it also keeps the buffers alive)."""
+        import numpy as np
+        n = len(fps)
+        # the requests as one numpy block viewed as blance_plan_stats[], the arrays of all problems in one int64 block: per
+        # problem seven slots of max(M, 1) values in the order of abi.PLAN_STATS_ARRAYS (nodes_used: int32 in its slot)
+        ask = [i for i in range(n) if want[i]]
+        M = np.array([fps[i].scalars["n_states"] for i in ask], dtype=np.int64)
+        slot = np.maximum(M, 1)
+        base = np.zeros(len(ask) + 1, np.int64)
+        base[1:] = np.cumsum(len(abi.PLAN_STATS_ARRAYS) * slot)
+        block = np.zeros(max(int(base[-1]), 1), dtype=np.int64)
+        req = np.zeros(max(len(ask), 1), dtype=abi.PLAN_STATS_DTYPE)
+        req["n_states"][:len(ask)] = M
+        for k, name in enumerate(abi.PLAN_STATS_ARRAYS):
+            req[name][:len(ask)] = block.ctypes.data + 8 * (base[:-1] + k * slot)
+        st_ptrs = np.zeros(max(n, 1), dtype=np.uint64)
+        st_ptrs[ask] = req.ctypes.data + req.itemsize * np.arange(len(ask), dtype=np.uint64)
+        return st_ptrs, (n, ask, M, slot, base, block, req)
+
+    @staticmethod
+    def _stats_unpack(state):
+        import numpy as np
+        n, ask, M, slot, base, block, req = state
+        out = [None] * n
+        block32 = block.view(np.int32)
+        n_next = req["n_nodes_next"].tolist()
+        starts, slots, ms = base.tolist(), slot.tolist(), M.tolist()
+        for j, i in enumerate(ask):
+            d = {}
+            for k, name in enumerate(abi.PLAN_STATS_ARRAYS):
+                at = starts[j] + k * slots[j]
+                d[name] = block32[2 * at:2 * at + ms[j]] if name == "nodes_used" else block[at:at + ms[j]]
+            d["n_nodes_next"] = n_next[j]
+            out[i] = d
+        return out
+
     def plan_batch_stats(self, fps, stats=True, favor_min_nodes=None, beg_other=None):
         """blance_plan_batch_stats(): plan_batch, and for each problem that asks the plan statistics of Planner.plan_stats
         from the same device call.  stats: one bool or one per problem; favor_min_nodes / beg_other as in plan_batch_moves,
@@ -490,20 +561,7 @@ class Planner:
         if len(want) != n:
             raise ValueError("stats: one bool or one per problem")
         mv_ptrs, mv_state = self._moves_requests(fps, results, favor_min_nodes, beg_other)
-        # the requests as one numpy block viewed as blance_plan_stats[], the arrays of all problems in one int64 block: per
-        # problem seven slots of max(M, 1) values in the order of abi.PLAN_STATS_ARRAYS (nodes_used: int32 in its slot)
-        ask = [i for i in range(n) if want[i]]
-        M = np.array([fps[i].scalars["n_states"] for i in ask], dtype=np.int64)
-        slot = np.maximum(M, 1)
-        base = np.zeros(len(ask) + 1, np.int64)
-        base[1:] = np.cumsum(len(abi.PLAN_STATS_ARRAYS) * slot)
-        block = np.zeros(max(int(base[-1]), 1), dtype=np.int64)
-        req = np.zeros(max(len(ask), 1), dtype=abi.PLAN_STATS_DTYPE)
-        req["n_states"][:len(ask)] = M
-        for k, name in enumerate(abi.PLAN_STATS_ARRAYS):
-            req[name][:len(ask)] = block.ctypes.data + 8 * (base[:-1] + k * slot)
-        st_ptrs = np.zeros(max(n, 1), dtype=np.uint64)
-        st_ptrs[ask] = req.ctypes.data + req.itemsize * np.arange(len(ask), dtype=np.uint64)
+        st_ptrs, st_state = self._stats_requests(fps, want)
         pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
         rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
         info = abi.BatchInfo()
@@ -513,18 +571,72 @@ class Planner:
                                                      mv_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
                                                      st_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.PlanStats))),
                                                      C.byref(info)))
-        out = [None] * n
-        block32 = block.view(np.int32)
-        n_next = req["n_nodes_next"].tolist()
-        starts, slots, ms = base.tolist(), slot.tolist(), M.tolist()
+        return (results, self._moves_unpack(mv_state), self._stats_unpack(st_state),
+                {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_})
+
+    def batch_names(self, names, node_names=None, state_names=None):
+        """blance_batch_names_create(): the prepared names of one index, for plan_batch_wire.  names: a problem (its
+        part_names, node_names, state_names), or the partition names with the two other lists beside them; str or bytes.
+        The names of an index do not change between rebalances: make the object once and keep it."""
+        if not hasattr(self.lib, "blance_plan_batch_wire"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_wire (build the current sources)")
+        if node_names is None and state_names is None:
+            names, node_names, state_names = names.part_names, names.node_names, names.state_names
+        nm, keep = wire_names_struct(names, node_names, state_names)
+        h = C.c_void_p()
+        self._check(self.lib.blance_batch_names_create(C.byref(nm), len(names), len(node_names), len(state_names), C.byref(h)))
+        del keep
+        return BatchNames(self.lib, h, len(names), len(node_names), len(state_names))
+
+    def plan_batch_wire(self, fps, names, stats=False, favor_min_nodes=None, beg_other=None):
+        """blance_plan_batch_wire(): plan_batch_stats, and for each problem with a names object its plan as
+        json.Marshal(PartitionMap) bytes from the same device call -- the bytes wire.encode makes of the decoded result.
+        names: one BatchNames per problem (Planner.batch_names), None: no document for that problem; stats /
+        favor_min_nodes / beg_other as in plan_batch_stats.  Returns ([FlatResult], [moves or None], [stats dict or None],
+        [bytes or None], info dict)."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_batch_wire"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_wire (build the current sources)")
+        fps = list(fps)
+        n = len(fps)
+        names = list(names)
+        if len(names) != n:
+            raise ValueError("names: one BatchNames or None per problem")
+        results = [abi.FlatResult(fp) for fp in fps]
+        structs = [fp.as_struct() for fp in fps]
+        want = list(stats) if isinstance(stats, (list, tuple)) else [stats] * n
+        if len(want) != n:
+            raise ValueError("stats: one bool or one per problem")
+        mv_ptrs, mv_state = self._moves_requests(fps, results, favor_min_nodes, beg_other)
+        st_ptrs, st_state = self._stats_requests(fps, want)
+        # the document requests as one numpy block viewed as blance_batch_wire[], all documents in one byte block
+        ask = [i for i in range(n) if names[i] is not None]
+        cap = np.array([self.lib.blance_batch_wire_capacity(C.byref(structs[i]), names[i]._h) for i in ask], dtype=np.int64)
+        base = np.zeros(len(ask) + 1, np.int64)
+        base[1:] = np.cumsum(cap)
+        docs_block = np.empty(max(int(base[-1]), 1), dtype=np.uint8)
+        wreq = np.zeros(max(len(ask), 1), dtype=abi.BATCH_WIRE_DTYPE)
+        wreq["names"][:len(ask)] = [names[i]._h.value for i in ask]
+        wreq["buf"][:len(ask)] = docs_block.ctypes.data + base[:-1]
+        wreq["cap"][:len(ask)] = cap
+        wr_ptrs = np.zeros(max(n, 1), dtype=np.uint64)
+        wr_ptrs[ask] = wreq.ctypes.data + wreq.itemsize * np.arange(len(ask), dtype=np.uint64)
+        pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
+        rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
+        info = abi.BatchInfo()
+        self._adopted = False
+        self._wire_adopted = None
+        self._check(self.lib.blance_plan_batch_wire(self._h, n, pbs, rss,
+                                                    mv_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
+                                                    st_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.PlanStats))),
+                                                    wr_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchWire))),
+                                                    C.byref(info)))
+        docs = [None] * n
+        need, starts = wreq["need"].tolist(), base.tolist()
         for j, i in enumerate(ask):
-            d = {}
-            for k, name in enumerate(abi.PLAN_STATS_ARRAYS):
-                at = starts[j] + k * slots[j]
-                d[name] = block32[2 * at:2 * at + ms[j]] if name == "nodes_used" else block[at:at + ms[j]]
-            d["n_nodes_next"] = n_next[j]
-            out[i] = d
-        return results, self._moves_unpack(mv_state), out, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
+            docs[i] = docs_block[starts[j]:starts[j] + need[j]].tobytes()
+        return (results, self._moves_unpack(mv_state), self._stats_unpack(st_state), docs,
+                {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_})
 
     def plan_stats(self, n_states):
         """Per-state load statistics of the map the last plan produced (blance_plan_stats_get):

@@ -185,6 +185,30 @@ def PlanNextMapExBatchStats(calls, planner=None):
     return out
 
 
+def PlanNextMapExBatchWire(calls, planner=None):
+    """PlanNextMapExBatch, and each plan as json.Marshal(PartitionMap) bytes from the same device call
+    (blance_plan_batch_wire): what a caller persists and ships.  Returns [(nextMap, warnings, document_bytes)] in call
+    order, with every call's write-back done as PlanNextMapEx does; a call whose plan returns no map
+    (MaxIterationsPerPlan <= 0) gets (None, None, None).  The names are prepared per call here; a caller that plans the
+    same indexes again keeps Planner.batch_names objects and calls Planner.plan_batch_wire itself."""
+    names = ("prevMap", "partitionsToAssign", "nodesAll", "nodesToRemove", "nodesToAdd", "model", "options", "booster")
+    args = [dict(c) if isinstance(c, dict) else dict(zip(names, c)) for c in calls]
+    fps = [_build_call(**a) for a in args]
+    pl = planner or default_planner()
+    prepared = [pl.batch_names(fp) if fp.max_iterations > 0 else None for fp in fps]
+    try:
+        results, _, _, docs, _ = pl.plan_batch_wire(fps, prepared)
+    finally:
+        for nm in prepared:
+            if nm is not None:
+                nm.close()
+    out = []
+    for fp, res, a, doc in zip(fps, results, args, docs):
+        nextMap, warnings = _finish_call(fp, res, a["prevMap"], a["partitionsToAssign"])
+        out.append((nextMap, warnings, doc if nextMap is not None else None))
+    return out
+
+
 def _beg_other(fp, prevMap):
     """prevMap's nodes under state keys outside the model, CSR over fp's partitions in its node id space (None if none)."""
     import numpy as np

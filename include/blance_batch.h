@@ -85,6 +85,53 @@ int blance_plan_batch_stats(blance_ctx* ctx, int32_t n, const blance_problem* co
                             blance_plan_stats* const* sts /* may be NULL; sts[i] may be NULL: no statistics for problem i */,
                             blance_batch_info* info /* may be NULL */);
 
+/* ---- the same batch, and each plan as PartitionMap JSON bytes ----------------
+ * The names of an index do not change between rebalances, so what depends on them alone is prepared once, on the
+ * host: the order of the partitions in the document (byte order of their names), every name in its escaped form, the
+ * states in the order of their names -- what blance_plan_wire_names prepares for the problem a context holds.  A
+ * blance_batch_names is host memory only, tied to no context and immutable: any number of calls, contexts and threads
+ * may use one at the same time, and two problems of one batch may share one.  names follows blance_plan_wire_names
+ * (strings of any bytes; n_parts / n_nodes_ext / n_states strings).  Refusals: BLANCE_ERR_BAD_ARG for a NULL, a negative
+ * size, offsets that do not start at 0 or are not monotone, two states with one name; BLANCE_ERR_UNSUPPORTED for two
+ * partitions with one name and for 2^31 escaped bytes or more. */
+typedef struct blance_batch_names blance_batch_names;
+int  blance_batch_names_create(const blance_wire_names* names, int32_t n_parts, int32_t n_nodes_ext, int32_t n_states,
+                               blance_batch_names** out);
+void blance_batch_names_destroy(blance_batch_names* nm);   /* NULL is fine */
+
+/* For every problem i with wrs[i] != NULL, wrs[i]->buf receives json.Marshal(PartitionMap) of the plan in res[i]: the
+ * bytes blance_wire_encode makes of that result, and the bytes blance_plan(ctx, pbs[i], res[i]) followed by
+ * blance_plan_wire_names and blance_plan_wire_get would return; need is the document's length, buf[need ..) is left
+ * untouched.  Batched problems get theirs from k_batch_wire_size and k_batch_wire_write in the same call (two launches
+ * after the plan launches whenever at least one batched problem asks: with moves, statistics and documents a fully
+ * batched call is at most 6 launches; the lengths come in the same download, the documents in one more copy of exactly
+ * their bytes); every other problem from the path of blance_plan_wire_get right after its plan.  An empty map
+ * (n_parts == 0) is "{}".  Every request is checked with its problem before anything runs (names or buf NULL, sizes of
+ * names that differ from the problem's, cap below blance_batch_wire_capacity(), max_iterations <= 0: PlanNextMapEx
+ * returns no map there): a refusal names the problem's index and writes no result, no moves, no statistics and no
+ * document.  mvs and sts follow blance_plan_batch_stats; wrs == NULL is exactly blance_plan_batch_stats.  Afterwards the
+ * context holds no problem and no names, as after every batch: blance_plan_wire_get answers BLANCE_ERR_BAD_ARG. */
+typedef struct blance_batch_wire {
+    const blance_batch_names* names;  /* in: sizes must equal the problem's n_parts / n_nodes_ext / n_states */
+    char*  buf;                       /* in: caller-owned, cap bytes */
+    size_t cap;                       /* in: >= blance_batch_wire_capacity(pb, names) */
+    size_t need;                      /* out: the document's length; buf[need ..) is left untouched */
+} blance_batch_wire;
+
+/* An upper bound on the document, known before the plan, from the sums a blance_batch_names keeps:
+ *   2 + 29 * P + 2 * (escaped partition bytes) + P * ((escaped "state": bytes) + 5 * M)
+ *     + blance_result_capacity(pb) * ((longest escaped node name) + 1)
+ * 29 = a partition's punctuation ( , or {   :{"name":   ,"nodesByState":{   }} ), 5 per (partition, state) = the comma
+ * and `null` (or the two brackets), + 1 per list entry = its comma, 2 = "{}" and the document's last brace.
+ * 0 when an argument is NULL. */
+size_t blance_batch_wire_capacity(const blance_problem* pb, const blance_batch_names* names);
+
+int blance_plan_batch_wire(blance_ctx* ctx, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                           blance_batch_moves* const* mvs /* may be NULL; mvs[i] may be NULL */,
+                           blance_plan_stats* const* sts /* may be NULL; sts[i] may be NULL */,
+                           blance_batch_wire* const* wrs /* may be NULL; wrs[i] may be NULL: no document for problem i */,
+                           blance_batch_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
