@@ -355,3 +355,14 @@ BATCH_WIRE_DTYPE = np.dtype({
     "formats": [np.uint64] * 4,
     "offsets": [getattr(BatchWire, f).offset for f in ("names", "buf", "cap", "need")],
     "itemsize": C.sizeof(BatchWire)})
+
+
+class BatchDoc(C.Structure):
+    """blance_batch_doc of include/blance_batch.h (blance_plan_batch_docs): one problem's prevMap document and its outcome."""
+    _fields_ = [("dict", C.c_void_p), ("json", C.c_void_p), ("len", C.c_size_t), ("assign_too", C.c_int32),
+                ("keep_prev_only", C.c_int32), ("reserved", C.c_int32 * 2), ("status", C.c_int32), ("refusal", C.c_int32),
+                ("refusal_at", C.c_int64), ("why", C.c_int32), ("why_at", C.c_int64), ("n_node_refs", C.c_int64),
+                ("n_parts_seen", C.c_int64)]
+
+
+BATCH_DOC_OUT = ("status", "refusal", "refusal_at", "why", "why_at", "n_node_refs", "n_parts_seen")

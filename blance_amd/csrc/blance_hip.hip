@@ -397,6 +397,7 @@ struct blance_ctx : CtxHandles {
     int64_t out_capacity = 0;
     DevBuf batch_in, batch_sc, batch_out;   // blance_plan_batch: descriptors + packed problems, working state, results
     DevBuf batch_doc;                       // blance_plan_batch_wire: the documents of the batched problems, one after another
+    DevBuf batch_doc_in, batch_doc_sum;     // blance_plan_batch_docs: the prevMap documents coming in, k_batch_decode's summary words
 
     // device: problem
     DevBuf node_removed, node_added, node_weight, node_has_weight, alive, zeros_nx, node_leaf_pos;
@@ -3938,7 +3939,17 @@ int wd_build_table(const WireBlob& b, std::vector<int32_t>& slots, uint32_t& mas
 }
 }  // namespace
 
-static int wire_dict_locked(blance_ctx* c, const blance_wire_names* nm, int32_t P, int32_t NX, int32_t M, blance_wire_dict** out) {
+// what a dictionary is made of on the host (blance_wire_dict_create and blance_batch_dict_create share it): per kind of name
+// wd_build_table's table and int32 offsets, and where the raw names lie (the caller's blobs, or a batch dictionary's block)
+struct WdHostTables {
+    int32_t n[3] = {0, 0, 0};
+    uint32_t mask[3] = {0, 0, 0};
+    std::vector<int32_t> slots[3], off32[3];
+    const void* bytes[3] = {nullptr, nullptr, nullptr};
+};
+
+// pure host: the checks of blance_wire_dict_create and the three tables
+static int wd_host_tables(const blance_wire_names* nm, int32_t P, int32_t NX, int32_t M, WdHostTables& t) {
     if (P < 0 || NX < 0 || M < 0) return fail(BLANCE_ERR_BAD_ARG, "negative count");
     if ((int64_t)P * M >= (int64_t)INT32_MAX) return fail(BLANCE_ERR_BAD_ARG, "n_parts * n_states of 2^31 - 1 or more");
     const WireBlob blobs[3] = {{nm->part_bytes, nm->part_off, P}, {nm->node_bytes, nm->node_off, NX}, {nm->state_bytes, nm->state_off, M}};
@@ -3949,28 +3960,34 @@ static int wire_dict_locked(blance_ctx* c, const blance_wire_names* nm, int32_t 
             if (b.off[i + 1] < b.off[i]) return fail(BLANCE_ERR_BAD_ARG, "name offsets not monotone");
         if (b.off[b.n] > 0 && !b.bytes) return fail(BLANCE_ERR_BAD_ARG, "null name bytes");
     }
-    std::vector<int32_t> slots[3], off32[3];
-    std::unique_ptr<blance_wire_dict> d(new blance_wire_dict());
-    d->owner = c;
     for (int k = 0; k < 3; k++) {
-        d->n[k] = (int32_t)blobs[k].n;
-        const int e = wd_build_table(blobs[k], slots[k], d->mask[k], off32[k]);
+        t.n[k] = (int32_t)blobs[k].n;
+        t.bytes[k] = blobs[k].bytes;
+        const int e = wd_build_table(blobs[k], t.slots[k], t.mask[k], t.off32[k]);
         if (e == 2) return fail(BLANCE_ERR_UNSUPPORTED, "names of 2^31 bytes or more");
         if (e == 1 && k == 0) return fail(BLANCE_ERR_UNSUPPORTED, "two partitions with one name (the reference's map would keep one of them)");
         if (e == 1) return fail(BLANCE_ERR_BAD_ARG, k == 1 ? "two nodes with one name" : "two states with one name");
     }
+    return BLANCE_OK;
+}
+
+// the tables as a dictionary of the context
+static int wire_dict_upload_locked(blance_ctx* c, const WdHostTables& t, blance_wire_dict** out) {
+    std::unique_ptr<blance_wire_dict> d(new blance_wire_dict());
+    d->owner = c;
+    for (int k = 0; k < 3; k++) { d->n[k] = t.n[k]; d->mask[k] = t.mask[k]; }
     HIPTRY(hipSetDevice(c->device));
     Mover up(c, true);
     c->stage.used = 0;                                   // (the stream is idle between calls)
     int e = 0;
     for (int k = 0; k < 3; k++) {
-        const size_t nb = (size_t)blobs[k].off[blobs[k].n];
-        if (d->slots[k].reserve(sizeof(int32_t) * slots[k].size()) || d->bytes[k].reserve(nb + 16) ||
-            d->off[k].reserve(sizeof(int32_t) * off32[k].size()))
+        const size_t nb = (size_t)t.off32[k][(size_t)t.n[k]];
+        if (d->slots[k].reserve(sizeof(int32_t) * t.slots[k].size()) || d->bytes[k].reserve(nb + 16) ||
+            d->off[k].reserve(sizeof(int32_t) * t.off32[k].size()))
             return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-        if ((e = up.copy(d->slots[k].p, slots[k].data(), sizeof(int32_t) * slots[k].size()))) return e;
-        if ((e = up.copy(d->bytes[k].p, blobs[k].bytes, nb))) return e;
-        if ((e = up.copy(d->off[k].p, off32[k].data(), sizeof(int32_t) * off32[k].size()))) return e;
+        if ((e = up.copy(d->slots[k].p, t.slots[k].data(), sizeof(int32_t) * t.slots[k].size()))) return e;
+        if ((e = up.copy(d->bytes[k].p, t.bytes[k], nb))) return e;
+        if ((e = up.copy(d->off[k].p, t.off32[k].data(), sizeof(int32_t) * t.off32[k].size()))) return e;
     }
     if ((e = up.flush())) return e;
     HIPTRY(stream_sync(c));                              // nothing of this frame is read after the call
@@ -3978,6 +3995,12 @@ static int wire_dict_locked(blance_ctx* c, const blance_wire_names* nm, int32_t 
     c->wd_dicts.push_back(d.get());
     *out = d.release();
     return BLANCE_OK;
+}
+
+static int wire_dict_locked(blance_ctx* c, const blance_wire_names* nm, int32_t P, int32_t NX, int32_t M, blance_wire_dict** out) {
+    WdHostTables t;
+    const int e = wd_host_tables(nm, P, NX, M, t);
+    return e ? e : wire_dict_upload_locked(c, t, out);
 }
 
 extern "C" int blance_wire_dict_create(blance_ctx* c, const blance_wire_names* nm, int32_t n_parts, int32_t n_nodes_ext,
@@ -4336,17 +4359,23 @@ int batch_list_len(const blance_problem* pb) {
     return L;
 }
 
-// the word layout of one problem's three slices (BatchDesc); false when the problem is outside the batched envelope
-bool batch_layout(const blance_problem* pb, BatchItem& it) {
+// the word layout of one problem's three slices (BatchDesc); false when the problem is outside the batched envelope.
+// doc_cap >= 0: a document problem (blance_plan_batch_docs) -- the row stride is kBatchMaxL, the output slice holds doc_cap
+// list entries (blance_batch_doc_bounds'), doc_loads load entries are packed; n_prev, fresh and cap are fixed after the decode
+bool batch_layout(const blance_problem* pb, BatchItem& it, int64_t doc_cap = -1, int doc_loads = 0) {
     const int N = pb->n_nodes, NX = pb->n_nodes_ext, M = pb->n_states, P = pb->n_parts;
     if (NX > kBatchMaxNX || P > kBatchMaxP || M > kMaxStates) return false;
-    const int L = batch_list_len(pb);
+    int L = batch_list_len(pb);
     if (L > kBatchMaxL) return false;
+    if (doc_cap >= 0) {
+        L = kBatchMaxL;
+        if (doc_cap > (int64_t)INT32_MAX / 2) return false;
+    }
     BatchDesc& d = it.d;
     memset(&d, 0, sizeof d);
     const int PM = P * M;
     d.N = N; d.NX = NX; d.M = M; d.P = P; d.L = L;
-    d.n_loads = pb->n_loads; d.n_rules = pb->hierarchy_rules_nil ? 0 : pb->n_rules;
+    d.n_loads = doc_cap >= 0 ? doc_loads : pb->n_loads; d.n_rules = pb->hierarchy_rules_nil ? 0 : pb->n_rules;
     d.max_iterations = pb->max_iterations; d.n_prev = pb->n_prev;
     for (int p = 0; p < P; p++) if (!pb->part_in_prev[p]) d.fresh++;
     for (int n = 0; n < NX; n++) {
@@ -4355,7 +4384,7 @@ bool batch_layout(const blance_problem* pb, BatchItem& it) {
     }
     d.weights_nil = pb->partition_weights_nil; d.add_nil = pb->nodes_to_add_nil; d.hier_nil = pb->hierarchy_rules_nil;
     d.booster_kind = pb->booster_kind; d.top_state = pb->top_state;
-    d.cap = (int32_t)blance_result_capacity(pb);
+    d.cap = (int32_t)(doc_cap >= 0 ? doc_cap : blance_result_capacity(pb));
     int passes = 0;
     for (int m = 0; m < M; m++) if (pb->state_constraints[m] > 0) passes++;
     d.wcap = P * passes;
@@ -4363,7 +4392,7 @@ bool batch_layout(const blance_problem* pb, BatchItem& it) {
     auto take = [&](int32_t& field, int64_t words) { field = o; o += (int32_t)((words + 3) & ~3ll); };
     take(d.i_state, 4 * M); take(d.i_rule_off, M + 1); take(d.i_node, 4 * (int64_t)NX); take(d.i_order, P);
     take(d.i_part, 2 * (int64_t)P); take(d.i_alist, (int64_t)PM * L); take(d.i_ahdr, PM); take(d.i_plist, (int64_t)PM * L);
-    take(d.i_phdr, PM); take(d.i_loads, 4 * (int64_t)pb->n_loads); take(d.i_anch, 4 * (int64_t)d.n_rules * (NX + 1));
+    take(d.i_phdr, PM); take(d.i_loads, 4 * (int64_t)d.n_loads); take(d.i_anch, 4 * (int64_t)d.n_rules * (NX + 1));
     it.in_words = o;
     o = 0;
     take(d.s_live, (int64_t)PM * L); take(d.s_lhdr, PM); take(d.s_prv, (int64_t)PM * L); take(d.s_phdr, PM);
@@ -4376,8 +4405,10 @@ bool batch_layout(const blance_problem* pb, BatchItem& it) {
     return true;
 }
 
-// the problem's input slice (BatchDesc) at dst
-void batch_pack(const blance_problem* pb, const BatchDesc& d, int32_t* dst) {
+// the problem's input slice (BatchDesc) at dst.  doc: a document problem -- 0: none; 1: prevMap's lists and headers are
+// k_batch_decode's to write; 2 (assign_too): the lists to assign as well; keep: its load entries that are not first sweep
+// only stay (d.n_loads of them), else none
+void batch_pack(const blance_problem* pb, const BatchDesc& d, int32_t* dst, int doc = 0, bool keep = false) {
     const int NX = d.NX, M = d.M, P = d.P, L = d.L, PM = P * M;
     for (int m = 0; m < M; m++) {
         int32_t* s = dst + d.i_state + 4 * m;
@@ -4399,13 +4430,18 @@ void batch_pack(const blance_problem* pb, const BatchDesc& d, int32_t* dst) {
     }
     for (int idx = 0; idx < PM; idx++) {
         const int a0 = pb->assign_off[idx], a1 = pb->assign_off[idx + 1], b0 = pb->prev_off[idx], b1 = pb->prev_off[idx + 1];
-        memcpy(dst + d.i_alist + (int64_t)idx * L, pb->assign_nodes + a0, sizeof(int32_t) * (size_t)(a1 - a0));
-        dst[d.i_ahdr + idx] = (a1 - a0) | (pb->assign_kind[idx] << 16);
-        memcpy(dst + d.i_plist + (int64_t)idx * L, pb->prev_nodes + b0, sizeof(int32_t) * (size_t)(b1 - b0));
-        dst[d.i_phdr + idx] = (b1 - b0) | (pb->prev_kind[idx] << 16);
+        if (doc < 2) {
+            memcpy(dst + d.i_alist + (int64_t)idx * L, pb->assign_nodes + a0, sizeof(int32_t) * (size_t)(a1 - a0));
+            dst[d.i_ahdr + idx] = (a1 - a0) | (pb->assign_kind[idx] << 16);
+        }
+        if (doc < 1) {
+            memcpy(dst + d.i_plist + (int64_t)idx * L, pb->prev_nodes + b0, sizeof(int32_t) * (size_t)(b1 - b0));
+            dst[d.i_phdr + idx] = (b1 - b0) | (pb->prev_kind[idx] << 16);
+        }
     }
-    for (int i = 0; i < d.n_loads; i++) {
-        int32_t* s = dst + d.i_loads + 4 * i;
+    for (int i = 0, at = 0; i < pb->n_loads && at < d.n_loads; i++) {
+        if (doc && !(keep && !pb->load_first_sweep_only[i])) continue;
+        int32_t* s = dst + d.i_loads + 4 * at++;
         s[0] = pb->load_state[i]; s[1] = pb->load_node[i]; s[2] = pb->load_weight[i]; s[3] = pb->load_first_sweep_only[i];
     }
     // leaf-interval table of every (rule, anchor), anchor NX = the "" vertex: plan.go:723-734, :755-774 (as blance_upload)
@@ -4422,8 +4458,8 @@ void batch_pack(const blance_problem* pb, const BatchDesc& d, int32_t* dst) {
         }
 }
 
-// the moves request of one problem: buffers, the beg_other CSR, the capacity
-int batch_moves_check(const blance_problem* pb, const blance_batch_moves* mv) {
+// the moves request of one problem: buffers, the beg_other CSR, the capacity (moves_cap >= 0: of a document problem)
+int batch_moves_check(const blance_problem* pb, const blance_batch_moves* mv, int64_t moves_cap = -1) {
     const blance_moves_result& o = mv->out;
     if (!o.op_off || !o.op_node || !o.op_state || !o.op_kind) return fail(BLANCE_ERR_BAD_ARG, "null moves buffers");
     if (!mv->beg_other_off != !mv->beg_other_nodes)
@@ -4438,7 +4474,7 @@ int batch_moves_check(const blance_problem* pb, const blance_batch_moves* mv) {
             if (mv->beg_other_nodes[j] < 0 || mv->beg_other_nodes[j] >= pb->n_nodes_ext)
                 return fail(BLANCE_ERR_BAD_ARG, "beg_other node id outside [0, n_nodes_ext)");
     }
-    if (o.capacity < blance_batch_moves_capacity(pb, mv)) return fail(BLANCE_ERR_CAPACITY, "moves capacity too small");
+    if (o.capacity < (moves_cap >= 0 ? moves_cap : blance_batch_moves_capacity(pb, mv))) return fail(BLANCE_ERR_CAPACITY, "moves capacity too small");
     return BLANCE_OK;
 }
 
@@ -4450,8 +4486,9 @@ int batch_stats_check(const blance_problem* pb, const blance_plan_stats* st) {
     return BLANCE_OK;
 }
 
-// every check blance_plan would make before it writes a result, and the result buffers' capacities
-int batch_check(const blance_problem* pb, const blance_result* r) {
+// every check blance_plan would make before it writes a result, and the result buffers' capacities (result_cap >= 0: of a
+// document problem)
+int batch_check(const blance_problem* pb, const blance_result* r, int64_t result_cap = -1) {
     int st = blance_validate(pb);
     if (st) return st;
     if (!r || !r->out_off || !r->out_nodes || !r->out_kind || !r->warn_part || !r->warn_state)
@@ -4459,7 +4496,7 @@ int batch_check(const blance_problem* pb, const blance_result* r) {
     if (pb->max_iterations > 0) {
         int passes = 0;
         for (int m = 0; m < pb->n_states; m++) if (pb->state_constraints[m] > 0) passes++;
-        if (r->out_capacity < blance_result_capacity(pb)) return fail(BLANCE_ERR_CAPACITY, "out_capacity too small");
+        if (r->out_capacity < (result_cap >= 0 ? result_cap : blance_result_capacity(pb))) return fail(BLANCE_ERR_CAPACITY, "out_capacity too small");
         if (r->warn_capacity < (int64_t)pb->n_parts * passes) return fail(BLANCE_ERR_CAPACITY, "warn_capacity too small");
     }
     return BLANCE_OK;
@@ -4560,14 +4597,82 @@ extern "C" size_t blance_batch_wire_capacity(const blance_problem* pb, const bla
            (size_t)blance_result_capacity(pb) * ((size_t)nm->node_esc_max + 1);
 }
 
+// blance_batch_wire_capacity's formula for a plan of at most result_cap list entries
+static size_t batch_wire_cap_of(const blance_problem* pb, const blance_batch_names* nm, int64_t result_cap) {
+    const size_t P = (size_t)pb->n_parts, M = (size_t)pb->n_states;
+    return 2 + 29 * P + 2 * nm->part_esc_bytes + P * (nm->state_esc_bytes + 5 * M) + (size_t)result_cap * ((size_t)nm->node_esc_max + 1);
+}
+
+// ---- the dictionary of one index for blance_plan_batch_docs (blance_batch_dict): wd_host_tables' tables
+// as one block of int32 words, the block a batch copies behind a problem's packed input slice (k_batch_decode.h reads it
+// through its header); `tables` is the same as blance_wire_dict_create wants it (the single path), its names in the block
+struct blance_batch_dict {
+    int32_t n_parts = 0, n_nodes_ext = 0, n_states = 0;
+    std::vector<int32_t> block;                          // kBatchDictHdr words, then per kind slots, offsets, raw bytes
+    WdHostTables tables;
+};
+
+extern "C" int blance_batch_dict_create(const blance_wire_names* names, int32_t n_parts, int32_t n_nodes_ext, int32_t n_states,
+                                        blance_batch_dict** out) {
+    return guarded([&]() -> int {
+        if (!names || !out) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        std::unique_ptr<blance_batch_dict> d(new blance_batch_dict);
+        WdHostTables& t = d->tables;
+        const int st = wd_host_tables(names, n_parts, n_nodes_ext, n_states, t);
+        if (st) return st;
+        d->n_parts = n_parts; d->n_nodes_ext = n_nodes_ext; d->n_states = n_states;
+        size_t words = kBatchDictHdr, at[3][3];
+        for (int k = 0; k < 3; k++) {
+            const size_t nb = (size_t)t.off32[k][(size_t)t.n[k]];
+            const size_t w[3] = {t.slots[k].size(), t.off32[k].size(), (nb + 3) / 4};
+            for (int j = 0; j < 3; j++) { at[k][j] = words; words += (w[j] + 3) & ~(size_t)3; }
+        }
+        if (words > (size_t)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "names of 2^31 bytes or more");
+        d->block.assign(words, 0);
+        int32_t* b = d->block.data();
+        for (int k = 0; k < 3; k++) {
+            const size_t nb = (size_t)t.off32[k][(size_t)t.n[k]];
+            b[4 * k] = (int32_t)at[k][0]; b[4 * k + 1] = (int32_t)t.mask[k]; b[4 * k + 2] = (int32_t)at[k][2]; b[4 * k + 3] = (int32_t)at[k][1];
+            b[12 + k] = t.n[k];
+            memcpy(b + at[k][0], t.slots[k].data(), sizeof(int32_t) * t.slots[k].size());
+            memcpy(b + at[k][1], t.off32[k].data(), sizeof(int32_t) * t.off32[k].size());
+            if (nb) memcpy(b + at[k][2], t.bytes[k], nb);
+            t.bytes[k] = b + at[k][2];                   // (the caller's blobs are gone after this call)
+        }
+        *out = d.release();
+        return BLANCE_OK;
+    });
+}
+
+extern "C" void blance_batch_dict_destroy(blance_batch_dict* d) { delete d; }
+
+extern "C" int blance_batch_doc_bounds(const blance_problem* pb, const blance_batch_doc* dc, const blance_batch_names* nm,
+                                       int64_t* result_cap, int64_t* moves_cap, size_t* wire_cap) {
+    if (!pb || !dc || !pb->state_constraints || pb->n_parts < 0 || pb->n_states < 0) return fail(BLANCE_ERR_BAD_ARG, "null argument");
+    const int64_t refs = (int64_t)(dc->len / 3);
+    int64_t rc = blance_result_capacity(pb);
+    if (dc->assign_too) {
+        int64_t ksum = 0;
+        for (int m = 0; m < pb->n_states; m++) ksum += pb->state_constraints[m] > 0 ? pb->state_constraints[m] : 0;
+        rc = (int64_t)pb->n_parts * ksum + refs;
+    }
+    if (result_cap) *result_cap = rc;
+    if (moves_cap) *moves_cap = refs + rc;
+    if (wire_cap) *wire_cap = nm ? batch_wire_cap_of(pb, nm, rc) : 0;
+    return BLANCE_OK;
+}
+
 namespace {
-// the document request of one problem: the names object made for its sizes, the buffer, its capacity
-int batch_wire_check(const blance_problem* pb, const blance_batch_wire* wr) {
+// the document request of one problem: the names object made for its sizes, the buffer, its capacity (result_cap >= 0: of a
+// document problem, blance_batch_doc_bounds' in place of blance_result_capacity)
+int batch_wire_check(const blance_problem* pb, const blance_batch_wire* wr, int64_t result_cap = -1) {
     if (!wr->names || !wr->buf) return fail(BLANCE_ERR_BAD_ARG, "null names or null document buffer");
     if (wr->names->n_parts != pb->n_parts || wr->names->n_nodes_ext != pb->n_nodes_ext || wr->names->n_states != pb->n_states)
         return fail(BLANCE_ERR_BAD_ARG, "the names were made for other sizes than the problem's");
     if (pb->max_iterations <= 0) return fail(BLANCE_ERR_BAD_ARG, "a document asked for a problem with max_iterations <= 0 (no map)");
-    if (wr->cap < blance_batch_wire_capacity(pb, wr->names)) return fail(BLANCE_ERR_CAPACITY, "document capacity too small");
+    const size_t need = result_cap >= 0 ? batch_wire_cap_of(pb, wr->names, result_cap) : blance_batch_wire_capacity(pb, wr->names);
+    if (wr->cap < need) return fail(BLANCE_ERR_CAPACITY, "document capacity too small");
     return BLANCE_OK;
 }
 }  // namespace
@@ -4578,31 +4683,150 @@ static int fail_problem(int st, int i) {
     return fail(st, "problem %s", (std::to_string(i) + ": " + why).c_str());
 }
 
+// the arguments of a document problem that refuse the whole call (blance_plan_batch_docs)
+static int batch_doc_check(const blance_problem* pb, const blance_batch_moves* mv, const blance_batch_doc* dc) {
+    if (!dc->dict || (!dc->json && dc->len)) return fail(BLANCE_ERR_BAD_ARG, "null dictionary or null document");
+    if (dc->dict->n_parts != pb->n_parts || dc->dict->n_nodes_ext != pb->n_nodes_ext || dc->dict->n_states != pb->n_states)
+        return fail(BLANCE_ERR_BAD_ARG, "the dictionary was made for other sizes than the problem's");
+    for (int32_t r : dc->reserved) if (r) return fail(BLANCE_ERR_BAD_ARG, "blance_batch_doc::reserved must be zero");
+    if (mv && mv->beg_other_off) return fail(BLANCE_ERR_BAD_ARG, "beg_other with a document: its prevMap has no keys outside the model");
+    if (pb->max_iterations <= 0) return fail(BLANCE_ERR_BAD_ARG, "a document for a problem with max_iterations <= 0 (no map)");
+    return BLANCE_OK;
+}
+
+// A document problem on the single path, from the original bytes: blance_upload(pb), a temporary dictionary of the context
+// made from the batch dictionary's tables, blance_wire_adopt, blance_plan_resident and the readers.  What the document
+// decides goes to dc (*planned stays false); any other failure is the call's.
+static int batch_doc_single(blance_ctx* c, const blance_problem* pb, blance_result* r, blance_batch_moves* mv, blance_plan_stats* ps,
+                            blance_batch_wire* wr, blance_batch_doc* dc, int64_t* launches, double* device_ms, bool* planned) {
+    *planned = false;
+    int st = upload_inner(c, pb);
+    if (st) return st;
+    blance_wire_dict* d = nullptr;
+    if ((st = wire_dict_upload_locked(c, dc->dict->tables, &d))) return st;
+    struct blance_wire_adopt wa;
+    memset(&wa, 0, sizeof wa);
+    wa.dict = d; wa.json = dc->json; wa.len = dc->len;
+    wa.node_removed = pb->node_removed; wa.node_added = pb->node_added; wa.nodes_to_add_nil = pb->nodes_to_add_nil;
+    wa.assign_too = dc->assign_too; wa.keep_prev_only = dc->keep_prev_only;
+    st = wire_adopt_locked(c, &wa);
+    c->wd_dicts.erase(std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d));
+    (void)hipStreamSynchronize(c->stream);
+    delete d;
+    dc->refusal = wa.refusal; dc->refusal_at = wa.refusal_at;
+    dc->why = wa.why; dc->why_at = wa.why_at;
+    dc->n_node_refs = wa.n_node_refs; dc->n_parts_seen = wa.n_parts_seen;
+    *device_ms += wa.device_ms;
+    if (st == BLANCE_ERR_UNSUPPORTED && (wa.refusal || wa.why)) {
+        dc->status = BLANCE_ERR_UNSUPPORTED;
+        return BLANCE_OK;
+    }
+    if (st) return st;
+    if ((st = plan_locked(c, r))) return st;
+    if ((st = download_locked(c, r))) return st;
+    *launches += r->kernel_launches;
+    *device_ms += r->device_ms;
+    if (ps && (st = plan_stats_locked(c, ps, launches))) return st;
+    if (wr) {
+        if ((st = wire_tables_upload_locked(c, wr->names->tables))) return st;
+        double wire_ms = 0.0;
+        st = plan_wire_locked(c, wr->buf, wr->cap, &wr->need, &wire_ms);
+        c->wire_names = false;
+        if (st) return st;
+        *device_ms += wire_ms;
+    }
+    if (mv) {                                            // blance_plan_moves_get's path: from the adopted prevMap where it lies
+        blance_plan_moves pm;
+        memset(&pm, 0, sizeof pm);
+        pm.favor_min_nodes = mv->favor_min_nodes;
+        pm.out = mv->out;
+        if ((st = plan_moves_locked(c, &pm))) return st;
+        mv->out.device_ms = pm.out.device_ms;
+        *device_ms += pm.out.device_ms;
+    }
+    *planned = true;
+    return BLANCE_OK;
+}
+
 static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
                              blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_wire* const* wrs,
-                             blance_batch_info* info) {
+                             blance_batch_info* info, blance_batch_doc* const* dcs = nullptr) {
     const auto t_start = std::chrono::steady_clock::now();
     if (c->comm.n_ranks > 1 || c->rccl_comm) return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_batch on a context with a communicator");
+    // a document problem's bounds (blance_batch_doc_bounds) stand for the capacities its skeleton would give; -1: no document
+    std::vector<int64_t> rcap((size_t)n, -1), mcap((size_t)n, -1);
+    auto doc_of = [&](int i) -> blance_batch_doc* { return dcs ? dcs[i] : nullptr; };
+    auto wire_cap_of = [&](int i) -> size_t {
+        return rcap[(size_t)i] >= 0 ? batch_wire_cap_of(pbs[i], wrs[i]->names, rcap[(size_t)i]) : blance_batch_wire_capacity(pbs[i], wrs[i]->names);
+    };
     for (int i = 0; i < n; i++) {
-        int st = batch_check(pbs[i], res[i]);
-        if (!st && mvs && mvs[i]) st = batch_moves_check(pbs[i], mvs[i]);
+        const blance_batch_doc* dc = doc_of(i);
+        int st = BLANCE_OK;
+        if (dc) {
+            st = blance_validate(pbs[i]);
+            if (!st) st = batch_doc_check(pbs[i], mvs ? mvs[i] : nullptr, dc);
+            if (!st) st = blance_batch_doc_bounds(pbs[i], dc, nullptr, &rcap[(size_t)i], &mcap[(size_t)i], nullptr);
+        }
+        if (!st) st = batch_check(pbs[i], res[i], rcap[(size_t)i]);
+        if (!st && mvs && mvs[i]) st = batch_moves_check(pbs[i], mvs[i], mcap[(size_t)i]);
         if (!st && sts && sts[i]) st = batch_stats_check(pbs[i], sts[i]);
-        if (!st && wrs && wrs[i]) st = batch_wire_check(pbs[i], wrs[i]);
+        if (!st && wrs && wrs[i]) st = batch_wire_check(pbs[i], wrs[i], rcap[(size_t)i]);
         if (st) return fail_problem(st, i);
     }
     HIPTRY(hipSetDevice(c->device));
     c->uploaded = false;                                 // the context holds no problem after a batch
     c->planned = false;
     c->wire_names = false;
+    // 0: no document; 1: a document, to be planned; 2: refused (in dcs[i]), nothing of problem i is written
+    std::vector<int8_t> dstate((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+        blance_batch_doc* dc = doc_of(i);
+        if (!dc) continue;
+        dc->status = BLANCE_OK;
+        dc->refusal = 0; dc->refusal_at = -1; dc->why = 0; dc->why_at = -1;
+        dc->n_node_refs = dc->n_parts_seen = 0;
+        dstate[(size_t)i] = 1;
+        if (dc->len > (size_t)INT32_MAX) {               // before anything is launched, as blance_wire_decode_device
+            dc->status = BLANCE_ERR_UNSUPPORTED;
+            dc->refusal = kWdDocumentTooLong; dc->refusal_at = 0;
+            dstate[(size_t)i] = 2;
+        }
+    }
+    auto kept_loads = [&](int i) {                       // the load entries keep_prev_only keeps
+        int kept = 0;
+        if (doc_of(i)->keep_prev_only)
+            for (int j = 0; j < pbs[i]->n_loads; j++) kept += !pbs[i]->load_first_sweep_only[j];
+        return kept;
+    };
+    constexpr size_t kBatchDocMaxLen = (size_t)1 << 28;  // (a longer document's record starts outgrow the int32 slice offsets)
+    // ... and all documents decoded in one call stay below 2^31 bytes (their scratch is twice that): the excess, in call
+    // order, goes the single path
+    constexpr size_t kBatchDocsMaxBytes = (size_t)1 << 31;
+    std::vector<uint8_t> doc_batched((size_t)n, 0);
+    {
+        size_t total = 0;
+        for (int i = 0; i < n; i++) {
+            if (dstate[(size_t)i] != 1) continue;
+            const size_t len = doc_of(i)->len;
+            if (len > kBatchDocMaxLen || total + len > kBatchDocsMaxBytes) continue;
+            BatchItem probe;
+            if (!batch_layout(pbs[i], probe, rcap[(size_t)i], kept_loads(i))) continue;
+            doc_batched[(size_t)i] = 1;
+            total += len;
+        }
+    }
     std::vector<BatchItem> items;
     std::vector<int> fallback;
     for (int cls : {64, 256})
         for (int i = 0; i < n; i++) {
+            if (dstate[(size_t)i] == 2) continue;
             BatchItem it;
             it.idx = i;
             // (a document that may reach 2^31 bytes is the single path's to refuse: the batch's offsets are int32)
-            const bool in_env = batch_layout(pbs[i], it) &&
-                                !(wrs && wrs[i] && blance_batch_wire_capacity(pbs[i], wrs[i]->names) > (size_t)INT32_MAX);
+            const bool doc = dstate[(size_t)i] == 1;
+            const bool in_env = (doc ? doc_batched[(size_t)i] && batch_layout(pbs[i], it, rcap[(size_t)i], kept_loads(i))
+                                     : batch_layout(pbs[i], it)) &&
+                                !(wrs && wrs[i] && wire_cap_of(i) > (size_t)INT32_MAX);
             if (!in_env && cls == 64) fallback.push_back(i);
             if (in_env && it.threads == cls) items.push_back(it);
         }
@@ -4624,7 +4848,7 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             for (int p = 0; p < d.P; p++) other_len = std::max(other_len, mv->beg_other_off[p + 1] - mv->beg_other_off[p]);
         }
         md.stride = std::min(2 * d.M * d.L + other_len, d.NX);   // >= the distinct nodes of a partition's two maps
-        md.cap = (int32_t)blance_batch_moves_capacity(pbs[it.idx], mv);
+        md.cap = (int32_t)(mcap[(size_t)it.idx] >= 0 ? mcap[(size_t)it.idx] : blance_batch_moves_capacity(pbs[it.idx], mv));
         auto take = [](int32_t& field, int64_t& words, int64_t n_words) { field = (int32_t)words; words += (n_words + 3) & ~3ll; };
         take(md.i_ooff, it.in_words, d.P + 1); take(md.i_onodes, it.in_words, n_other);
         take(md.s_cnt, it.sc_words, d.P); take(md.s_mv, it.sc_words, (int64_t)d.P * md.stride);
@@ -4664,11 +4888,38 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         it.sc_words += ((int64_t)it.d.P + 1 + 3) & ~3ll;
         wd.o_total = (int32_t)it.out_words;
         it.out_words += 4;
-        doc_cap += (blance_batch_wire_capacity(pbs[it.idx], wr->names) + 15) & ~(size_t)15;
+        doc_cap += (wire_cap_of(it.idx) + 15) & ~(size_t)15;
         it.wi = (int)wds.size();
         wds.push_back(wd);
     }
     const int nw = (int)wds.size();
+    // the prevMap documents of the batched problems that bring one: the dictionary block behind the input slice, the
+    // parser's claim / kinds / lengths and the record starts in scratch (one run of words: k_batch_decode zeroes up to s_rec)
+    std::vector<BatchDocDesc> dds;
+    std::vector<int> dd_item;
+    size_t docs_in_bytes = 0;
+    for (int j = 0; j < nb; j++) {
+        BatchItem& it = items[j];
+        if (dstate[(size_t)it.idx] != 1) continue;
+        const blance_batch_doc* dc = doc_of(it.idx);
+        BatchDocDesc dd;
+        memset(&dd, 0, sizeof dd);
+        dd.desc = j;
+        dd.len = (int32_t)dc->len;
+        dd.doc_base = (int64_t)docs_in_bytes;
+        docs_in_bytes += (dc->len + 15) & ~(size_t)15;
+        dd.assign_too = dc->assign_too ? 1 : 0;
+        dd.i_dict = (int32_t)it.in_words;
+        it.in_words += (int64_t)dc->dict->block.size();      // (a multiple of 4 words)
+        const int64_t P = it.d.P, PM = (int64_t)it.d.P * it.d.M;
+        auto take = [&](int32_t& field, int64_t n_words) { field = (int32_t)it.sc_words; it.sc_words += (n_words + 3) & ~3ll; };
+        take(dd.s_claim, P); take(dd.s_pkind, (P + 3) / 4); take(dd.s_kind, (PM + 3) / 4); take(dd.s_len, PM + 1);
+        dd.rec_cap = (int32_t)((dc->len + 1) / 2 + 1);
+        take(dd.s_rec, dd.rec_cap);
+        dd_item.push_back(j);
+        dds.push_back(dd);
+    }
+    const int nd = (int)dds.size();
     int64_t launches = 0, steps = 0;
     double device_ms = 0.0;
     if (nb > 0) {
@@ -4685,7 +4936,8 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         const size_t desc_bytes = ((sizeof(BatchDesc) * (size_t)nb) + 255) & ~(size_t)255;
         const size_t mdesc_bytes = ((sizeof(BatchMovesDesc) * (size_t)nm) + 255) & ~(size_t)255;
         const size_t sdesc_bytes = ((sizeof(BatchStatsDesc) * (size_t)ns) + 255) & ~(size_t)255;
-        const size_t head_bytes = desc_bytes + mdesc_bytes + sdesc_bytes + (((sizeof(BatchWireDesc) * (size_t)nw) + 255) & ~(size_t)255);
+        const size_t wdesc_bytes = ((sizeof(BatchWireDesc) * (size_t)nw) + 255) & ~(size_t)255;
+        const size_t head_bytes = desc_bytes + mdesc_bytes + sdesc_bytes + wdesc_bytes + (((sizeof(BatchDocDesc) * (size_t)nd) + 255) & ~(size_t)255);
         const size_t in_bytes = head_bytes + sizeof(int32_t) * (size_t)in_words, out_bytes = sizeof(int32_t) * (size_t)out_words;
         struct Pinned { void* p = nullptr; ~Pinned() { pin_free(p); } } host;
         host.p = pin_alloc(in_bytes + out_bytes);
@@ -4694,7 +4946,9 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         int32_t* h_out = (int32_t*)(h_in + in_bytes);
         for (int i = 0; i < nb; i++) {
             memcpy(h_in + sizeof(BatchDesc) * i, &items[i].d, sizeof(BatchDesc));
-            batch_pack(pbs[items[i].idx], items[i].d, (int32_t*)(h_in + head_bytes) + items[i].d.in_base);
+            const blance_batch_doc* dc = dstate[(size_t)items[i].idx] == 1 ? doc_of(items[i].idx) : nullptr;
+            batch_pack(pbs[items[i].idx], items[i].d, (int32_t*)(h_in + head_bytes) + items[i].d.in_base,
+                       dc ? (dc->assign_too ? 2 : 1) : 0, dc && dc->keep_prev_only);
             if (items[i].mi >= 0) {                      // beg_other behind the input slice
                 const BatchMovesDesc& md = mds[items[i].mi];
                 const blance_batch_moves* mv = mvs[items[i].idx];
@@ -4715,6 +4969,25 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         if (nm > 0) memcpy(h_in + desc_bytes, mds.data(), sizeof(BatchMovesDesc) * (size_t)nm);
         if (ns > 0) memcpy(h_in + desc_bytes + mdesc_bytes, sds.data(), sizeof(BatchStatsDesc) * (size_t)ns);
         if (nw > 0) memcpy(h_in + desc_bytes + mdesc_bytes + sdesc_bytes, wds.data(), sizeof(BatchWireDesc) * (size_t)nw);
+        // the documents in page-locked staging of their own, each at a 16-byte aligned base and padded to 16
+        struct Pinned h_docs, h_sum;
+        if (nd > 0) {
+            memcpy(h_in + desc_bytes + mdesc_bytes + sdesc_bytes + wdesc_bytes, dds.data(), sizeof(BatchDocDesc) * (size_t)nd);
+            h_docs.p = pin_alloc(docs_in_bytes + 16);
+            h_sum.p = pin_alloc(sizeof(int32_t) * kBdSumWords * (size_t)nd);
+            if (!h_docs.p || !h_sum.p) return fail(BLANCE_ERR_DEVICE, "page-locked staging block: hipHostMalloc failed");
+            for (int k = 0; k < nd; k++) {
+                const BatchItem& it = items[dd_item[(size_t)k]];
+                const blance_batch_doc* dc = doc_of(it.idx);
+                char* at = (char*)h_docs.p + dds[(size_t)k].doc_base;
+                if (dc->len) memcpy(at, dc->json, dc->len);
+                memset(at + dc->len, 0, ((dc->len + 15) & ~(size_t)15) - dc->len);
+                const std::vector<int32_t>& blk = dc->dict->block;
+                memcpy((int32_t*)(h_in + head_bytes) + it.d.in_base + dds[(size_t)k].i_dict, blk.data(), sizeof(int32_t) * blk.size());
+            }
+            if (c->batch_doc_in.reserve(docs_in_bytes + 16) || c->batch_doc_sum.reserve(sizeof(int32_t) * kBdSumWords * (size_t)nd))
+                return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        }
         // (scratch: wire_total [nw] behind the problems' slices)
         if (c->batch_in.reserve(in_bytes) || c->batch_sc.reserve(sizeof(int32_t) * ((size_t)sc_words + (size_t)nw) + 256) ||
             c->batch_out.reserve(out_bytes) || (nw > 0 && c->batch_doc.reserve(doc_cap + 16)))
@@ -4726,6 +4999,84 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         q.sc = c->batch_sc.as<int32_t>();
         q.out = c->batch_out.as<int32_t>();
         HIPTRY(hipEventRecord(c->ev0, c->stream));
+        if (nd > 0) {
+            // the documents: one launch, one round trip for the summary words, then what the host decides of them and the
+            // descriptors of the document problems again (n_prev, fresh, cap; skip for what is not planned here)
+            if (docs_in_bytes > 0) HIPTRY(hipMemcpyAsync(c->batch_doc_in.p, h_docs.p, docs_in_bytes, hipMemcpyHostToDevice, c->stream));
+            BatchDecodeParams qd;
+            qd.desc = q.desc;
+            qd.ddesc = (const BatchDocDesc*)(c->batch_in.as<char>() + desc_bytes + mdesc_bytes + sdesc_bytes + wdesc_bytes);
+            qd.in = (int32_t*)(c->batch_in.as<char>() + head_bytes);
+            qd.sc = q.sc;
+            qd.docs = c->batch_doc_in.as<unsigned char>();
+            qd.sum = c->batch_doc_sum.as<int32_t>();
+            qd.tile = c->wd_tile; qd.stage = c->wd_stage;
+            launch_batch_decode(c->stream, qd, nd);
+            launches++;
+            HIPTRY(hipGetLastError());
+            HIPTRY(hipMemcpyAsync(h_sum.p, c->batch_doc_sum.p, sizeof(int32_t) * kBdSumWords * (size_t)nd, hipMemcpyDeviceToHost, c->stream));
+            HIPTRY(stream_sync(c));
+            for (int k = 0; k < nd; k++) {
+                BatchItem& it = items[dd_item[(size_t)k]];
+                const blance_problem* pb = pbs[it.idx];
+                blance_batch_doc* dc = doc_of(it.idx);
+                const int32_t* v = (const int32_t*)h_sum.p + (size_t)k * kBdSumWords;
+                unsigned long long refusal, cap64, aprev;
+                memcpy(&refusal, v + kBdRefusal, 8); memcpy(&cap64, v + kBdCap, 8); memcpy(&aprev, v + kBdPrevLoad, 8);
+                const bool keep = dc->keep_prev_only != 0, assign_too = dc->assign_too != 0;
+                auto refuse = [&](int why, int64_t at) {
+                    dc->status = BLANCE_ERR_UNSUPPORTED; dc->why = why; dc->why_at = at;
+                    dstate[(size_t)it.idx] = 2;
+                    it.d.skip = 1;
+                };
+                if (refusal != ~0ull) {
+                    dc->status = BLANCE_ERR_UNSUPPORTED;
+                    dc->refusal = (int32_t)(refusal & 255u); dc->refusal_at = (int64_t)(refusal >> 8);
+                    dstate[(size_t)it.idx] = 2;
+                    it.d.skip = 1;
+                } else if (v[kBdRefs] < 0) {
+                    return fail_problem(fail(BLANCE_ERR_DEVICE, "k_batch_decode: the list lengths overflow"), it.idx);
+                } else if ((v[kBdLongest] > kBatchMaxL) != (v[kBdFirstLong] != INT_MAX)) {
+                    return fail_problem(fail(BLANCE_ERR_DEVICE, "k_batch_decode: the longest list and the first long list disagree"), it.idx);
+                } else if (v[kBdLongest] > kBatchMaxL) {     // a list longer than the batch's rows: the single path, from the bytes
+                    it.d.skip = 1;
+                    fallback.push_back(it.idx);
+                } else {
+                    dc->n_node_refs = v[kBdRefs]; dc->n_parts_seen = v[kBdRecords];
+                    bool any_removed = false, any_pass = false;
+                    long long ksum = 0, sumw = 0, kept_abs = 0;
+                    for (int x = 0; x < pb->n_nodes_ext; x++) any_removed |= pb->node_removed[x] != 0;
+                    for (int m = 0; m < pb->n_states; m++) { any_pass |= pb->state_constraints[m] > 0; ksum += pb->state_constraints[m] > 0 ? pb->state_constraints[m] : 0; }
+                    for (int p = 0; p < pb->n_parts; p++) {
+                        const long long w = (!pb->partition_weights_nil && pb->part_has_weight[p]) ? pb->part_weight[p] : 1;
+                        sumw += w < 0 ? -w : w;
+                    }
+                    int in_prev = 0;
+                    for (int p = 0; p < pb->n_parts; p++) in_prev += pb->part_in_prev[p] != 0;
+                    if (keep)
+                        for (int j = 0; j < pb->n_loads; j++)
+                            if (!pb->load_first_sweep_only[j]) kept_abs += pb->load_weight[j] < 0 ? -(long long)pb->load_weight[j] : pb->load_weight[j];
+                    const long long abs_load = (long long)aprev + kept_abs + sumw * (ksum > 1 ? ksum : 1) * 2;
+                    if (assign_too && v[kBdFirstMissing] != INT_MAX) refuse(BLANCE_WIRE_ADOPT_PARTITION_MISSING, v[kBdFirstMissing]);
+                    else if (assign_too && v[kBdFirstDup] != INT_MAX) refuse(BLANCE_WIRE_ADOPT_DUPLICATE_NODE, v[kBdFirstDup]);
+                    else if (v[kBdFirstMissing] != INT_MAX && any_removed && any_pass) refuse(BLANCE_WIRE_ADOPT_REMOVED_WITHOUT_PREV, v[kBdFirstMissing]);
+                    else if (abs_load > 2147483647LL) refuse(BLANCE_WIRE_ADOPT_LOAD_OVERFLOW, -1);
+                    else {
+                        it.d.n_prev = v[kBdRecords] + (keep ? pb->n_prev - in_prev : 0);
+                        it.d.fresh = v[kBdFresh];
+                        if (assign_too) {
+                            if (cap64 > (unsigned long long)rcap[(size_t)it.idx])
+                                return fail_problem(fail(BLANCE_ERR_DEVICE, "k_batch_decode: a result capacity above its bound"), it.idx);
+                            it.d.cap = (int32_t)cap64;
+                        } else {
+                            it.d.cap = (int32_t)blance_result_capacity(pb);
+                        }
+                    }
+                }
+                memcpy(h_in + sizeof(BatchDesc) * (size_t)dd_item[(size_t)k], &it.d, sizeof(BatchDesc));
+            }
+            HIPTRY(hipMemcpyAsync(c->batch_in.p, h_in, sizeof(BatchDesc) * (size_t)nb, hipMemcpyHostToDevice, c->stream));
+        }
         q.first = 0;
         if (n64 > 0) { launch_plan_batch(c->stream, q, 64, n64, lds64); launches++; }
         q.first = n64;
@@ -4767,7 +5118,7 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         // a problem the kernel could not finish exactly (an interval budget of the hierarchy fold) goes the single path
         for (const BatchItem& it : items) {
             const int32_t* o = h_out + it.d.out_base;
-            if (o[5] != 1 || o[4] != 0) fallback.push_back(it.idx);
+            if (!it.d.skip && (o[5] != 1 || o[4] != 0)) fallback.push_back(it.idx);
         }
         // the documents: their 16-rounded lengths summed as k_batch_wire_write summed them, one copy of exactly these bytes
         struct Pinned docs;
@@ -4780,7 +5131,7 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
                 doc_base[(size_t)w] = doc_bytes;
                 if (o[5] != 1 || o[4] != 0 || o[0] == 0) continue;
                 const size_t total = (size_t)(uint32_t)o[wds[w].o_total];
-                if (total > blance_batch_wire_capacity(pbs[it.idx], wrs[it.idx]->names))
+                if (total > wire_cap_of(it.idx))
                     return fail_problem(fail(BLANCE_ERR_DEVICE, "k_batch_wire_size: a document longer than its bound"), it.idx);
                 doc_bytes += (total + 15) & ~(size_t)15;
             }
@@ -4858,8 +5209,19 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
             }
         }
     }
-    const int n_fallback = (int)fallback.size();
+    int n_fallback = (int)fallback.size(), n_refused_single = 0;
     for (int i : fallback) {                             // the single-problem path: blance_plan
+        if (dstate[(size_t)i] == 1) {                    // ... of a document problem: upload, adopt the document, plan resident
+            bool planned = false;
+            const int st = batch_doc_single(c, pbs[i], res[i], mvs ? mvs[i] : nullptr, sts ? sts[i] : nullptr, wrs ? wrs[i] : nullptr,
+                                            doc_of(i), &launches, &device_ms, &planned);
+            c->uploaded = c->planned = false;
+            c->wire_names = false;
+            if (st) return fail_problem(st, i);
+            if (planned) steps += res[i]->steps_total;
+            else { dstate[(size_t)i] = 2; n_refused_single++; }
+            continue;
+        }
         int st = plan_whole_locked(c, pbs[i], res[i]);
         if (!st && sts && sts[i]) st = plan_stats_locked(c, sts[i], &launches);     // while the context still holds the plan
         if (!st && wrs && wrs[i]) {                      // likewise: the path of blance_plan_wire_names / blance_plan_wire_get
@@ -4882,9 +5244,12 @@ static int plan_batch_locked(blance_ctx* c, int32_t n, const blance_problem* con
         }
     }
     for (int i = 0; i < n && mvs; i++)
-        if (mvs[i]) mvs[i]->out.device_ms = device_ms;
+        if (mvs[i] && dstate[(size_t)i] != 2) mvs[i]->out.device_ms = device_ms;
     if (info) {
-        info->n_batched = nb - (n_fallback - (n - nb));
+        int n_planned = 0;                               // (a refused document's problem is in neither count)
+        for (int i = 0; i < n; i++) n_planned += dstate[(size_t)i] != 2;
+        n_fallback -= n_refused_single;
+        info->n_batched = n_planned - n_fallback;
         info->n_fallback = n_fallback;
         info->kernel_launches = launches;
         info->steps_total = steps;
@@ -4910,6 +5275,15 @@ extern "C" int blance_plan_batch_wire(blance_ctx* c, int32_t n, const blance_pro
     return enter(c, [&]() -> int {
         if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
         return plan_batch_locked(c, n, pbs, res, mvs, sts, wrs, info);
+    });
+}
+
+extern "C" int blance_plan_batch_docs(blance_ctx* c, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                                      blance_batch_moves* const* mvs, blance_plan_stats* const* sts, blance_batch_wire* const* wrs,
+                                      blance_batch_doc* const* dcs, blance_batch_info* info) {
+    return enter(c, [&]() -> int {
+        if (n < 0 || (n > 0 && (!pbs || !res))) return fail(BLANCE_ERR_BAD_ARG, "negative count or null arrays");
+        return plan_batch_locked(c, n, pbs, res, mvs, sts, wrs, info, dcs);
     });
 }
 

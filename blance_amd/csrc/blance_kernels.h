@@ -264,6 +264,8 @@ struct BatchDesc {
     int32_t s_live, s_lhdr, s_prv, s_phdr, s_pflag, s_order, s_cat, s_ntn;
     // output slice: header [kBatchHdr], out_off [P*M + 1], out_kind [P*M], out_nodes [cap], warn_part [wcap], warn_state [wcap]
     int32_t o_off, o_kind, o_nodes, o_wp, o_ws;
+    // blance_plan_batch_docs: the problem's document was refused or goes the single path -- k_plan_batch marks it not done
+    int32_t skip;
 };
 
 struct BatchParams {
@@ -320,6 +322,38 @@ struct BatchWireDesc {
     int32_t i_names;                      // input slice: first word of the names block
     int32_t s_len;                        // scratch slice: [P + 1] byte offsets of the ranks (k_batch_wire_size's scan)
     int32_t o_total;                      // output slice: the document's length (one word of a region of four)
+};
+
+// The prevMap document of one batched problem (DESIGN.md §4.17 "k_batch_decode").  The dictionary block (a
+// blance_batch_dict's words, copied as they are) lies behind the problem's input slice: kBatchDictHdr words, per kind of
+// name (partitions, nodes, states) four -- slots (word offset in the block), mask, the raw bytes (word offset), their
+// int32 offsets (word offset) --, then the three counts; then the tables, each at a multiple of 4 words.
+constexpr int kBatchDecodeThreads = 256;
+constexpr int kBatchDictHdr = 16;
+constexpr int kBatchDecodeLdsHead = 4096;                   // scan and reduction words in front of the parse stage
+// summary words of one document (k_batch_decode's place-and-sum), int32 unless said otherwise
+enum { kBdRefusal = 0 /* 64 bit: all ones, or offset << 8 | reason */, kBdRecords = 2, kBdRefs = 3, kBdLongest = 4, kBdFresh = 5,
+       kBdFirstMissing = 6, kBdFirstDup = 7, kBdFirstLong = 8, kBdCap = 10 /* 64 bit */, kBdPrevLoad = 12 /* 64 bit */,
+       kBdSumWords = 16 };
+struct BatchDocDesc {
+    int32_t desc;                         // index of the problem's BatchDesc
+    int32_t len;                          // the document's bytes
+    int64_t doc_base;                     // its first byte in BatchDecodeParams::docs (a multiple of 16)
+    int32_t i_dict;                       // input slice: first word of the dictionary block
+    int32_t assign_too;
+    // scratch slice: claim [P], the partitions' kinds [P] (bytes), the lists' kinds [P*M] (bytes), their lengths [P*M + 1],
+    // the record starts [rec_cap]
+    int32_t s_claim, s_pkind, s_kind, s_len, s_rec, rec_cap;
+};
+
+struct BatchDecodeParams {
+    const BatchDesc* desc;
+    const BatchDocDesc* ddesc;            // one workgroup each
+    int32_t* in;                          // (the decoded lists go into the problems' input slices)
+    int32_t* sc;
+    const unsigned char* docs;            // all documents, each at a 16-byte aligned base, padded to 16
+    int32_t* sum;                         // [n][kBdSumWords]
+    int32_t tile, stage;                  // bytes of a thread's tile of the record split; bytes of the parse stage in LDS
 };
 
 struct BatchWireParams {

@@ -57,4 +57,6 @@ void launch_batch_stats(hipStream_t stream, const BatchStatsParams& q, int n, si
 size_t batch_stats_lds(int M, int NX);               // dynamic LDS of one such workgroup
 // k_batch_wire_size, then k_batch_wire_write (tu_batch.hip): the PartitionMap documents of n batched problems, one workgroup each
 void launch_batch_wire(hipStream_t stream, const BatchWireParams& q, int n);
+// k_batch_decode (tu_batch.hip): the prevMap documents of n batched problems, one workgroup each
+void launch_batch_decode(hipStream_t stream, const BatchDecodeParams& q, int n);
 }  // namespace blance

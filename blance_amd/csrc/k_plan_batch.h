@@ -19,6 +19,10 @@ __global__ __launch_bounds__(T) void k_plan_batch(BatchParams bp) {
     const int32_t* in = bp.in + D.in_base;
     int32_t* sc = bp.sc + D.sc_base;
     int32_t* out = bp.out + D.out_base;
+    if (D.skip) {                                  // blance_plan_batch_docs: its document was refused or goes the single path
+        if (tid == 0) { out[4] = 0; out[5] = 0; }  // (not done: the kernels behind this one leave it alone; uniform exit)
+        return;
+    }
     const int32_t* st = in + D.i_state;
     const int32_t* rule_off = in + D.i_rule_off;
     const int32_t* node = in + D.i_node;

@@ -73,7 +73,10 @@ struct WireDecodeParams {
     uint8_t* part_kind;                                      // [P] zeroed
     uint8_t* kind;                                           // [P * M] zeroed
     int32_t* off;                                            // [P * M + 1] zeroed: lengths, then (scanned) offsets
-    int32_t* nodes;                                          // [off[P * M]]
+    int32_t* nodes;                                          // [off[P * M]]; with row > 0: [P * M][row]
+    int32_t row;                                             // 0: nodes is the CSR of off.  > 0 (k_batch_decode.h): list idx owns the
+                                                             // row nodes[idx * row ..), the FIRST pass writes its first `row` ids
+                                                             // beside the lengths, off stays lengths and there is no second pass
     unsigned long long* refusal;                             // all ones: min over the refusals of offset << 8 | reason
 };
 
@@ -92,11 +95,14 @@ __device__ inline unsigned long long wd_atomic_min(unsigned long long* p, unsign
 #endif
 
 // ---- stage 1 --------------------------------------------------------------------------------------------------------------
+// (BLANCE_WD_NO_KERNELS: a second translation unit of the device build takes the parser alone; the kernels are this file's
+// once per library)
 
 // the 16 bytes at doc + b (b a multiple of 16) as four words; byte k is (w[k >> 2] >> 8 * (k & 3)) & 255
 #define WD_LOAD16(w, doc, b) const int4 w##_v = *(const int4*)((doc) + (b)); \
     const uint32_t w[4] = {(uint32_t)w##_v.x, (uint32_t)w##_v.y, (uint32_t)w##_v.z, (uint32_t)w##_v.w}
 
+#ifndef BLANCE_WD_NO_KERNELS
 __global__ __launch_bounds__(256) void k_wd_tail(WireDecodeParams q) {
     const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (t >= q.n_tiles) return;
@@ -183,6 +189,8 @@ __global__ __launch_bounds__(256) void k_wd_walk(WireDecodeParams q) {
         if (t == q.n_tiles - 1) q.count[q.n_tiles] = 0;
     }
 }
+
+#endif  // BLANCE_WD_NO_KERNELS
 
 // ---- stage 2 --------------------------------------------------------------------------------------------------------------
 
@@ -382,7 +390,9 @@ __device__ inline bool wd_list(WdParse& P, long long idx, int* kind_out, int* le
     *kind_out = kListSet;
     P.ws();
     if (P.get(P.p) == ']') { P.p++; return true; }
-    const int room = WRITE ? q.off[idx + 1] - q.off[idx] : 0;
+    const bool rows = q.row > 0;
+    const int room = rows ? q.row : WRITE ? q.off[idx + 1] - q.off[idx] : 0;
+    int32_t* dst = rows ? q.nodes + idx * q.row : WRITE ? q.nodes + q.off[idx] : nullptr;
     int n = 0;
     for (;;) {
         P.ws();
@@ -394,7 +404,7 @@ __device__ inline bool wd_list(WdParse& P, long long idx, int* kind_out, int* le
         if (!wd_string(P, &h, &len)) return false;
         const int x = wd_lookup(P, q.node, e0, h, len);
         if (x < 0) return P.fail(kWdUnknownNode, e0);
-        if (WRITE && n < room) q.nodes[q.off[idx] + n] = x;
+        if (n < room) dst[n] = x;
         n++;
         P.ws();
         c = P.get(P.p);
@@ -564,6 +574,7 @@ __device__ inline bool wd_empty_document(WdParse& P) {
     return true;
 }
 
+#ifndef BLANCE_WD_NO_KERNELS
 template <bool WRITE>
 __global__ __launch_bounds__(kWdRun) void k_wd_parse(WireDecodeParams q) {
     BLANCE_DYN_LDS(lds);
@@ -599,5 +610,6 @@ __global__ __launch_bounds__(kWdRun) void k_wd_parse(WireDecodeParams q) {
     }
     if (!ok) wd_atomic_min(q.refusal, ((unsigned long long)P.where << 8) | (unsigned long long)P.reason);
 }
+#endif  // BLANCE_WD_NO_KERNELS
 
 }  // namespace blance

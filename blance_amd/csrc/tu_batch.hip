@@ -1,10 +1,11 @@
-// Translation unit of k_plan_batch, k_batch_moves, k_batch_stats and k_batch_wire_*: many small problems in one launch, and
-// their launch wrappers.
+// Translation unit of k_plan_batch, k_batch_moves, k_batch_stats, k_batch_wire_* and k_batch_decode: many small problems in
+// one launch, and their launch wrappers.
 #include "dev_prelude.h"
 #include "k_plan_batch.h"
 #include "k_batch_moves.h"
 #include "k_batch_stats.h"
 #include "k_batch_wire.h"
+#include "k_batch_decode.h"
 
 namespace blance {
 
@@ -39,6 +40,13 @@ void launch_batch_wire(hipStream_t stream, const BatchWireParams& q0, int n) {
     if ((size_t)q.stage > 64 * 1024 - kBatchWireRedLds) q.stage = (int32_t)(64 * 1024 - kBatchWireRedLds);
     BLANCE_LAUNCH(k_batch_wire_size, n, kBatchWireThreads, kBatchWireSizeLds, stream, q);
     BLANCE_LAUNCH(k_batch_wire_write, n, kBatchWireThreads, kBatchWireRedLds + (size_t)q.stage, stream, q);
+}
+
+void launch_batch_decode(hipStream_t stream, const BatchDecodeParams& q0, int n) {
+    if (n <= 0) return;
+    BatchDecodeParams q = q0;                             // (the stage and the scan words share 64 KB of LDS)
+    if ((size_t)q.stage > 64 * 1024 - (size_t)kBatchDecodeLdsHead) q.stage = (int32_t)(64 * 1024 - kBatchDecodeLdsHead);
+    BLANCE_LAUNCH(k_batch_decode, n, kBatchDecodeThreads, (size_t)kBatchDecodeLdsHead + (size_t)q.stage, stream, q);
 }
 
 }  // namespace blance

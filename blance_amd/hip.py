@@ -110,6 +110,19 @@ def load_library(path=None):
                                                C.POINTER(C.POINTER(abi.Result)), C.POINTER(C.POINTER(abi.BatchMoves)),
                                                C.POINTER(C.POINTER(abi.PlanStats)), C.POINTER(C.POINTER(abi.BatchWire)),
                                                C.POINTER(abi.BatchInfo)]
+    if hasattr(lib, "blance_plan_batch_docs"):
+        lib.blance_batch_dict_create.restype = C.c_int
+        lib.blance_batch_dict_create.argtypes = [C.POINTER(abi.WireNames), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        lib.blance_batch_dict_destroy.restype = None
+        lib.blance_batch_dict_destroy.argtypes = [C.c_void_p]
+        lib.blance_batch_doc_bounds.restype = C.c_int
+        lib.blance_batch_doc_bounds.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.BatchDoc), C.c_void_p, C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]
+        lib.blance_plan_batch_docs.restype = C.c_int
+        lib.blance_plan_batch_docs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(abi.Problem)),
+                                               C.POINTER(C.POINTER(abi.Result)), C.POINTER(C.POINTER(abi.BatchMoves)),
+                                               C.POINTER(C.POINTER(abi.PlanStats)), C.POINTER(C.POINTER(abi.BatchWire)),
+                                               C.POINTER(C.POINTER(abi.BatchDoc)), C.POINTER(abi.BatchInfo)]
     # declared in blance_hip.h, additive to ABI 6: an older library of the same version loads, Planner.plan_moves refuses
     if hasattr(lib, "blance_plan_moves_get"):
         lib.blance_plan_moves_get.restype = C.c_int
@@ -263,6 +276,28 @@ class BatchNames:
     def close(self):
         if getattr(self, "_h", None):
             self.lib.blance_batch_names_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchDict:
+    """A blance_batch_dict: the names the documents of one index are decoded against in Planner.plan_batch_docs
+    (Planner.batch_dict).  Host memory only, tied to no context: it may serve any number of calls and planners; close() /
+    __del__ destroys it."""
+
+    def __init__(self, lib, handle, part_names, node_names, state_names):
+        self.lib, self._h = lib, handle
+        self.part_names, self.node_names, self.state_names = list(part_names), list(node_names), list(state_names)
+        self.n_parts, self.n_nodes_ext, self.n_states = len(self.part_names), len(self.node_names), len(self.state_names)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.blance_batch_dict_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -436,9 +471,10 @@ class Planner:
         self._check(self.lib.blance_plan_batch(self._h, n, pbs, rss, C.byref(info)))
         return results, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_}
 
-    def _moves_requests(self, fps, results, favor_min_nodes, beg_other):
+    def _moves_requests(self, fps, results, favor_min_nodes, beg_other, caps=None):
         """The moves requests of a batch as one numpy block viewed as blance_batch_moves[], the moves of all problems in one
         block: per problem op_off [P + 1], then op_node, op_state, op_kind [capacity] (no per-array ctypes conversions).
+        caps: {problem index: capacity} where it is not the problem's own (a document problem's bound).
         Returns (the pointer array of the call, what _moves_unpack needs -- it also keeps the buffers alive)."""
         import numpy as np
         n = len(fps)
@@ -451,6 +487,9 @@ class Planner:
         # = blance_batch_moves_capacity: prevMap entries + keys outside the model + blance_result_capacity
         cap = np.array([fps[i].arrays["prev_off"][-1] for i in ask], dtype=np.int64) + \
             np.array([results[i].struct.out_capacity for i in ask], dtype=np.int64)
+        for j, i in enumerate(ask):
+            if caps and i in caps:
+                cap[j] = caps[i]
         req["favor_min_nodes"][:len(ask)] = [bool(favor[i]) for i in ask]
         for j, i in enumerate(ask):
             if other[i] is not None:
@@ -637,6 +676,127 @@ class Planner:
             docs[i] = docs_block[starts[j]:starts[j] + need[j]].tobytes()
         return (results, self._moves_unpack(mv_state), self._stats_unpack(st_state), docs,
                 {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_})
+
+    def batch_dict(self, names, node_names=None, state_names=None):
+        """blance_batch_dict_create(): the dictionary of one index, for plan_batch_docs.  names: a problem (its part_names,
+        node_names, state_names), or the partition names with the two other lists beside them; str or bytes.  The ids of
+        a document's names are their positions here: they must be the problem's ids."""
+        if not hasattr(self.lib, "blance_plan_batch_docs"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_docs (build the current sources)")
+        if node_names is None and state_names is None:
+            names, node_names, state_names = names.part_names, names.node_names, names.state_names
+        nm, keep = wire_names_struct(names, node_names, state_names)
+        h = C.c_void_p()
+        self._check(self.lib.blance_batch_dict_create(C.byref(nm), len(names), len(node_names), len(state_names), C.byref(h)))
+        del keep
+        return BatchDict(self.lib, h, names, node_names, state_names)
+
+    def plan_batch_docs(self, fps, docs, dicts, assign_too=True, keep_prev_only=False, names=None, stats=False,
+                        favor_min_nodes=None, poison=None):
+        """blance_plan_batch_docs(): plan_batch_wire where problem i with docs[i] is not None is planned from that
+        PartitionMap document (bytes), decoded on the device against dicts[i] (Planner.batch_dict): prevMap, and with
+        assign_too the partitions to assign, are the document's; node_removed / node_added / nodes_to_add_nil are fps[i]'s.
+        assign_too / keep_prev_only: one bool or one per problem; names / stats / favor_min_nodes as in plan_batch_wire
+        (names None: no documents out).  Returns ([FlatResult or None], [moves or None], [stats or None], [bytes or None],
+        [outcome dict or None], info dict): an outcome has status, refusal, refusal_at, why, why_at, n_node_refs,
+        n_parts_seen; where its status is not 0 the problem was not planned, every other entry of that index is None and the
+        caller takes the host route.  poison: a byte every output buffer is filled with beforehand; the entries of a refused
+        index are then the untouched buffers (for tests)."""
+        import numpy as np
+        if not hasattr(self.lib, "blance_plan_batch_docs"):
+            raise BlanceError(abi.ERR_UNSUPPORTED, "this library has no blance_plan_batch_docs (build the current sources)")
+        fps = list(fps)
+        n = len(fps)
+        docs, dicts = list(docs), list(dicts)
+        names = [None] * n if names is None else list(names)
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+        a_too, keep_only, want = per(assign_too), per(keep_prev_only), per(stats)
+        if not (len(docs) == len(dicts) == len(names) == len(a_too) == len(keep_only) == len(want) == n):
+            raise ValueError("docs, dicts, names, assign_too, keep_prev_only, stats: one per problem")
+        structs = [fp.as_struct() for fp in fps]
+        dreq = (abi.BatchDoc * max(n, 1))()
+        dc_ptrs = (C.POINTER(abi.BatchDoc) * max(n, 1))()
+        keep = []
+        rcaps, mcaps, wcaps = {}, {}, {}
+        for i in range(n):
+            if docs[i] is None:
+                continue
+            buf = C.create_string_buffer(bytes(docs[i]), len(docs[i]) + 1)
+            keep.append(buf)
+            d = dreq[i]
+            d.dict = dicts[i]._h if dicts[i] is not None else None
+            d.json, d.len = C.cast(buf, C.c_void_p).value, len(docs[i])
+            d.assign_too, d.keep_prev_only = int(bool(a_too[i])), int(bool(keep_only[i]))
+            d.status = d.refusal = d.why = -77                       # (the call writes all seven outputs)
+            dc_ptrs[i] = C.pointer(d)
+            rc, mc, wc = C.c_int64(), C.c_int64(), C.c_size_t()
+            self._check(self.lib.blance_batch_doc_bounds(C.byref(structs[i]), C.byref(d), names[i]._h if names[i] is not None else None,
+                                                         C.byref(rc), C.byref(mc), C.byref(wc)))
+            rcaps[i], mcaps[i], wcaps[i] = rc.value, mc.value, wc.value
+        results = [abi.FlatResult(_ResultShape(fp, rcaps[i]) if i in rcaps else fp) for i, fp in enumerate(fps)]
+        mv_ptrs, mv_state = self._moves_requests(fps, results, favor_min_nodes, None, caps=mcaps)
+        st_ptrs, st_state = self._stats_requests(fps, want)
+        ask = [i for i in range(n) if names[i] is not None]
+        cap = np.array([wcaps[i] if i in wcaps else self.lib.blance_batch_wire_capacity(C.byref(structs[i]), names[i]._h)
+                        for i in ask], dtype=np.int64)
+        base = np.zeros(len(ask) + 1, np.int64)
+        base[1:] = np.cumsum(cap)
+        docs_block = np.empty(max(int(base[-1]), 1), dtype=np.uint8)
+        wreq = np.zeros(max(len(ask), 1), dtype=abi.BATCH_WIRE_DTYPE)
+        wreq["names"][:len(ask)] = [names[i]._h.value for i in ask]
+        wreq["buf"][:len(ask)] = docs_block.ctypes.data + base[:-1]
+        wreq["cap"][:len(ask)] = cap
+        wr_ptrs = np.zeros(max(n, 1), dtype=np.uint64)
+        wr_ptrs[ask] = wreq.ctypes.data + wreq.itemsize * np.arange(len(ask), dtype=np.uint64)
+        if poison is not None:
+            for r in results:
+                for a in (r.out_off, r.out_nodes, r.out_kind, r.warn_part, r.warn_state):
+                    a.view(np.uint8)[:] = poison
+            mv_state[5].view(np.uint8)[:] = poison
+            st_state[5].view(np.uint8)[:] = poison
+            docs_block[:] = poison
+            wreq["need"][:] = poison
+        pbs = (C.POINTER(abi.Problem) * max(n, 1))(*[C.pointer(s) for s in structs])
+        rss = (C.POINTER(abi.Result) * max(n, 1))(*[C.pointer(r.struct) for r in results])
+        info = abi.BatchInfo()
+        self._adopted = False
+        self._wire_adopted = None
+        self._check(self.lib.blance_plan_batch_docs(self._h, n, pbs, rss,
+                                                    mv_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchMoves))),
+                                                    st_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.PlanStats))),
+                                                    wr_ptrs.ctypes.data_as(C.POINTER(C.POINTER(abi.BatchWire))),
+                                                    dc_ptrs, C.byref(info)))
+        outcomes = [None if docs[i] is None else {f: int(getattr(dreq[i], f)) for f in abi.BATCH_DOC_OUT} for i in range(n)]
+        refused = [o is not None and o["status"] != 0 for o in outcomes]
+        out_docs = [None] * n
+        need, starts = wreq["need"].tolist(), base.tolist()
+        for j, i in enumerate(ask):
+            out_docs[i] = docs_block[starts[j]:starts[j + 1]] if refused[i] else docs_block[starts[j]:starts[j] + need[j]].tobytes()
+        moves = self._moves_unpack_some(mv_state, refused)
+        stats_out = self._stats_unpack(st_state)
+        if poison is not None:                                    # the refused indexes: the raw, untouched buffers
+            ask_mv, mbase, mblock = mv_state[1], mv_state[4], mv_state[5]
+            for j, i in enumerate(ask_mv):
+                if refused[i]:
+                    moves[i] = mblock[int(mbase[j]):int(mbase[j + 1])]
+        else:
+            for i in range(n):
+                if refused[i]:
+                    results[i] = stats_out[i] = out_docs[i] = None
+        return (results, moves, stats_out, out_docs, outcomes, {name: getattr(info, name) for name, _ in abi.BatchInfo._fields_})
+
+    @staticmethod
+    def _moves_unpack_some(state, skip):
+        """_moves_unpack for the problems i with not skip[i] (the others' blocks were not written); None for the rest."""
+        n, ask, P, cap, base, block, _, _ = state
+        moves = [None] * n
+        for j, i in enumerate(ask):
+            if skip[i]:
+                continue
+            e = int(base[j]) + int(P[j]) + 1
+            t, c = int(block[e - 1]), max(int(cap[j]), 1)
+            moves[i] = (block[e - int(P[j]) - 1:e], block[e:e + t], block[e + c:e + c + t], block[e + 2 * c:e + 2 * c + t])
+        return moves
 
     def plan_stats(self, n_states):
         """Per-state load statistics of the map the last plan produced (blance_plan_stats_get):

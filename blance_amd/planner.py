@@ -209,6 +209,56 @@ def PlanNextMapExBatchWire(calls, planner=None):
     return out
 
 
+def PlanNextMapExBatchDocs(calls, planner=None):
+    """Many rebalances planned from the stored PartitionMap documents by ONE blance_plan_batch_docs: the documents are decoded
+    on the device, straight into the batch's input.  A call is a dict with the arguments of PlanNextMapEx but prevMap, and
+    `document`: the bytes of json.Marshal(PartitionMap); prevMap and partitionsToAssign are both the document's map, and
+    partitionsToAssign is only read for the partition names (a map or a list of names; the document must hold every one).
+    An index whose document the device does not plan -- outside its subset, a missing partition, a duplicate -- goes the
+    host route (wire.decode, lists_of_wire_map, problem.wire_adopted_problem, a plan of its own), so every call ends in a
+    plan or in the host decoder's error (wire.WireError, problem.Unsupported).  Returns [(nextMap, warnings, route)] in call
+    order, route "device" or "host"."""
+    import numpy as np
+    from . import wire
+    pl = planner or default_planner()
+    fps, docs = [], []
+    for c in calls:
+        c = dict(c)
+        doc = c.pop("document")
+        names = list(c.pop("partitionsToAssign"))
+        gone, come = c.pop("nodesToRemove", None) or [], c.pop("nodesToAdd", None)
+        fp = _build_call({}, {n: Partition(n, {}) for n in names}, c.pop("nodesAll"), [], None, c.pop("model"), **c)
+        ids = {x: i for i, x in enumerate(fp.node_names)}
+        flags = lambda lst: np.bincount([ids[x] for x in lst if x in ids], minlength=fp.n_nodes_ext).astype(bool).astype(np.uint8)   # noqa: E731
+        fp.set("node_removed", flags(gone))
+        fp.set("node_added", flags(come or []))
+        fp.scalars["nodes_to_add_nil"] = int(come is None)
+        fps.append(fp)
+        docs.append(bytes(doc))
+    dicts = [pl.batch_dict(fp) for fp in fps]
+    try:
+        results, _, _, _, outcomes, _ = pl.plan_batch_docs(fps, docs, dicts)
+        out = []
+        for fp, doc, d, res, oc in zip(fps, docs, dicts, results, outcomes):
+            route = "device"
+            if oc["status"] != 0:
+                route = "host"
+                wm = wire.decode(doc)
+                try:
+                    lists = lists_of_wire_map(wm, d)
+                finally:
+                    wm.close()
+                new = problem.wire_adopted_problem(fp, lists, fp.node_removed[:fp.n_nodes_ext], fp.node_added[:fp.n_nodes_ext],
+                                                   bool(fp.nodes_to_add_nil), True, False, row_stride=0xffff)
+                res = pl.plan(new)
+            nextMap, warnings = _finish_call(fp, res, {}, {})
+            out.append((nextMap, warnings, route))
+        return out
+    finally:
+        for d in dicts:
+            d.close()
+
+
 def _beg_other(fp, prevMap):
     """prevMap's nodes under state keys outside the model, CSR over fp's partitions in its node id space (None if none)."""
     import numpy as np

@@ -132,6 +132,73 @@ int blance_plan_batch_wire(blance_ctx* ctx, int32_t n, const blance_problem* con
                            blance_batch_wire* const* wrs /* may be NULL; wrs[i] may be NULL: no document for problem i */,
                            blance_batch_info* info /* may be NULL */);
 
+/* ---- the same batch, planned from PartitionMap documents decoded on the device ----
+ * What a caller holds of an index is its stored document, not interned arrays.  A blance_batch_dict is what
+ * blance_wire_dict_create builds for the device -- per kind of name (partitions, nodes, states) an open-addressing table at
+ * load <= 1/2 over the raw names, the raw bytes and their int32 offsets -- as one block of int32 words in host memory: tied
+ * to no context and immutable, like a blance_batch_names; calls, contexts and threads may share one.  Refusals are exactly
+ * those of blance_wire_dict_create (BLANCE_ERR_BAD_ARG / BLANCE_ERR_UNSUPPORTED, same conditions). */
+typedef struct blance_batch_dict blance_batch_dict;
+int  blance_batch_dict_create(const blance_wire_names* names, int32_t n_parts, int32_t n_nodes_ext, int32_t n_states,
+                              blance_batch_dict** out);
+void blance_batch_dict_destroy(blance_batch_dict* d);      /* NULL is fine */
+
+/* For dcs[i] != NULL, pbs[i] is a valid skeleton and the problem planned is P'_i: the problem blance_wire_adopt defines
+ * (blance_hip.h) for the document decoded against dict, with node_removed / node_added / nodes_to_add_nil read from pbs[i]
+ * and assign_too / keep_prev_only as given.  res[i], mvs[i], sts[i] and wrs[i] receive what blance_plan_batch_wire would
+ * write for P'_i; the moves start from the document's map.
+ *
+ * The outcome is per document, not per call: what the document decides lands in dcs[i] and the call returns BLANCE_OK.
+ * status BLANCE_ERR_UNSUPPORTED: not planned -- refusal / refusal_at exactly what blance_wire_decode_device reports for
+ * these bytes (BLANCE_WIRE_REFUSED_DOCUMENT_TOO_LONG at 0 for len >= 2^31), or why / why_at exactly what blance_wire_adopt
+ * reports (BLANCE_WIRE_ADOPT_*, the smallest offender); res[i], mvs[i], sts[i] and wrs[i] (buffer included) are then not
+ * written and the caller takes the host route for that index.  info->n_batched + info->n_fallback
+ * counts the planned problems only.
+ *
+ * Argument errors refuse the whole call before anything runs (BLANCE_ERR_BAD_ARG, the problem's index in
+ * blance_last_error(), nothing written): dict NULL, json NULL with len > 0, dict sizes that differ from the problem's,
+ * non-zero reserved, mvs[i]->beg_other_off together with a document (P' has no prevMap keys outside the model), a document
+ * on a problem with max_iterations <= 0.  The capacity checks of a document problem use blance_batch_doc_bounds.
+ *
+ * Batched document problems are decoded by k_batch_decode, one workgroup per document, straight into the packed input
+ * slices (row stride 8): against the same call without documents a fully batched call adds ONE launch, whatever n, and one
+ * host round trip (the documents' summary words).  A document problem goes the single path inside the same call, from
+ * the original bytes (blance_upload(pbs[i]), a temporary context dictionary, blance_wire_adopt, blance_plan_resident and
+ * the readers), when pbs[i] is outside the batched envelope by its own sizes, when the document has a list longer than 8,
+ * when the document is longer than 2^28 bytes or would take the documents decoded in this call past 2^31 bytes (in call
+ * order), or when k_plan_batch marks the problem not done; refusals and why codes of that path pass into dcs[i] unchanged
+ * (a list longer than pbs[i]'s own row stride is BLANCE_WIRE_ADOPT_LIST_TOO_LONG there).
+ * dcs[i] == NULL: problem i exactly as by blance_plan_batch_wire; dcs == NULL is exactly blance_plan_batch_wire. */
+typedef struct blance_batch_doc {
+    /* in */
+    const blance_batch_dict* dict;     /* sizes must equal the problem's; its ids are the problem's ids (caller's contract) */
+    const char* json; size_t len;
+    int32_t assign_too, keep_prev_only;
+    int32_t reserved[2];               /* zero */
+    /* out */
+    int32_t status;                    /* BLANCE_OK: planned; BLANCE_ERR_UNSUPPORTED: not planned, see refusal / why */
+    int32_t refusal; int64_t refusal_at;          /* exactly what blance_wire_decode_device reports for this document */
+    int32_t why;     int64_t why_at;              /* BLANCE_WIRE_ADOPT_*, exactly what blance_wire_adopt reports */
+    int64_t n_node_refs, n_parts_seen;
+} blance_batch_doc;
+
+/* Upper bounds known before the plan.  A list of r node references takes at least 3 r + 1 bytes, so a document of len
+ * bytes holds at most len / 3 references:
+ *   result_cap = n_parts * sum_m max(k_m, 0) + len / 3 with assign_too, else blance_result_capacity(pb);
+ *   moves_cap  = len / 3 + result_cap;
+ *   wire_cap   = blance_batch_wire_capacity's formula with result_cap in place of blance_result_capacity(pb) (0 when
+ *                names is NULL).
+ * Any of the three pointers may be NULL.  BLANCE_ERR_BAD_ARG when pb or dc is NULL. */
+int blance_batch_doc_bounds(const blance_problem* pb, const blance_batch_doc* dc, const blance_batch_names* names /* may be NULL */,
+                            int64_t* result_cap, int64_t* moves_cap, size_t* wire_cap);
+
+int blance_plan_batch_docs(blance_ctx* ctx, int32_t n, const blance_problem* const* pbs, blance_result* const* res,
+                           blance_batch_moves* const* mvs /* may be NULL; mvs[i] may be NULL */,
+                           blance_plan_stats* const* sts /* may be NULL; sts[i] may be NULL */,
+                           blance_batch_wire* const* wrs /* may be NULL; wrs[i] may be NULL */,
+                           blance_batch_doc* const* dcs /* may be NULL; dcs[i] may be NULL: no document for problem i */,
+                           blance_batch_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
