@@ -243,7 +243,18 @@ struct FlatParams {
 constexpr int kBatchMaxNX = 256;       // node names of a batched problem (one thread per node, 64 or 256 threads)
 constexpr int kBatchMaxP = 16384;      // partitions
 constexpr int kBatchMaxL = 8;          // longest state list (constraints included)
-constexpr int kBatchHdr = 8;           // output header words: iterations, converged, warnings, list entries, error, done
+constexpr int kBatchHdr = 8;           // output header words, kBo* below
+// the header of a problem's output slice: sweeps made, converged, warnings, list entries, the kernel's error word, 1 once
+// k_plan_batch is done with the problem, findBestNodes calls (low 31 bits)
+enum { kBoIterations = 0, kBoConverged, kBoWarnings, kBoEntries, kBoError, kBoDone, kBoSteps };
+
+#ifdef __HIPCC__
+#define BLANCE_HOST_DEVICE __host__ __device__
+#else
+#define BLANCE_HOST_DEVICE
+#endif
+// k_plan_batch planned the problem exactly: what the kernels behind it and the host unpack.  Anything else goes the single path
+BLANCE_HOST_DEVICE inline bool batch_planned(const int32_t* hdr) { return hdr[kBoDone] == 1 && hdr[kBoError] == 0; }
 
 // One problem of a batch.  Its arrays are int32 words at fixed offsets inside three slices: input (packed by the host),
 // scratch (the kernel's working state) and output (what the host unpacks into the caller's blance_result).

@@ -14,7 +14,7 @@ __global__ __launch_bounds__(kBatchMovesThreads) void k_batch_moves(BatchMovesPa
     const int32_t* in = bp.in + D.in_base;
     int32_t* sc = bp.sc + D.sc_base;
     int32_t* out = bp.out + D.out_base;
-    if (out[5] != 1 || out[4] != 0) return;       // not planned exactly here: the host takes the single path (uniform exit)
+    if (!batch_planned(out)) return;              // not planned exactly here: the host takes the single path (uniform exit)
     const int tid = threadIdx.x, M = D.M, P = D.P, L = D.L, S = V.stride;
     const int32_t* phdr = in + D.i_phdr;          // prevMap lists [P*M][L], lengths in the low half of the header
     const int32_t* plist = in + D.i_plist;

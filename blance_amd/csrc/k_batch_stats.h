@@ -20,11 +20,11 @@ __global__ __launch_bounds__(kBatchStatsThreads) void k_batch_stats(BatchStatsPa
     const BatchDesc& D = bp.desc[V.desc];
     const int32_t* in = bp.in + D.in_base;
     int32_t* out = bp.out + D.out_base;
-    if (out[5] != 1 || out[4] != 0) return;       // not planned exactly here: the host takes the single path (uniform exit)
+    if (!batch_planned(out)) return;              // not planned exactly here: the host takes the single path (uniform exit)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = D.N, NX = D.NX, M = D.M, P = D.P;
     long long* res = (long long*)(out + V.o_stats);                 // [1 + 7 M]
-    if (out[0] == 0) {                            // MaxIterationsPerPlan <= 0: no map, every number 0
+    if (out[kBoIterations] == 0) {                // MaxIterationsPerPlan <= 0: no map, every number 0
         for (int i = tid; i < 1 + kBatchStatsArrays * M; i += T) res[i] = 0;
         return;
     }

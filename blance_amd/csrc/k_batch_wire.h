@@ -109,7 +109,9 @@ __global__ __launch_bounds__(kBatchWireThreads) void k_batch_wire_size(BatchWire
     const int32_t* in = bp.in + D.in_base;
     int32_t* out = bp.out + D.out_base;
     const int tid = threadIdx.x;
-    if (out[5] != 1 || out[4] != 0 || out[0] == 0) {         // not planned exactly here, or no map: no document (uniform exit)
+    // not planned exactly here, or no map: no document (uniform exit).  !batch_planned(out), spelled out: through the inlined
+    // predicate the compiler shapes this kernel's entry branches differently, and a refactor keeps the code object as it was
+    if (out[kBoDone] != 1 || out[kBoError] != 0 || out[kBoIterations] == 0) {
         if (tid == 0) { bp.wire_total[blockIdx.x] = 0; out[V.o_total] = 0; }
         return;
     }
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(kBatchWireThreads) void k_batch_wire_write(BatchWir
     const BatchDesc& D = bp.desc[V.desc];
     const int32_t* in = bp.in + D.in_base;
     const int32_t* out = bp.out + D.out_base;
-    if (out[5] != 1 || out[4] != 0 || out[0] == 0) return;   // as k_batch_wire_size (uniform exit)
+    if (!batch_planned(out) || out[kBoIterations] == 0) return;   // as k_batch_wire_size (uniform exit)
     const BatchWireView q = batch_wire_view(D, V, in, out);
     const int32_t* len = bp.sc + D.sc_base + V.s_len;        // [P + 1] the offsets of the ranks
     BLANCE_DYN_LDS(lds);

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(T) void k_plan_batch(BatchParams bp) {
     int32_t* sc = bp.sc + D.sc_base;
     int32_t* out = bp.out + D.out_base;
     if (D.skip) {                                  // blance_plan_batch_docs: its document was refused or goes the single path
-        if (tid == 0) { out[4] = 0; out[5] = 0; }  // (not done: the kernels behind this one leave it alone; uniform exit)
+        if (tid == 0) { out[kBoError] = 0; out[kBoDone] = 0; }  // (not done: the kernels behind this one leave it alone; uniform exit)
         return;
     }
     const int32_t* st = in + D.i_state;
@@ -383,13 +383,13 @@ __global__ __launch_bounds__(T) void k_plan_batch(BatchParams bp) {
     }
     if (tid == 0) {
         out[D.o_off + PM] = total;
-        out[0] = iterations;
-        out[1] = converged;
-        out[2] = n_warn;
-        out[3] = total;
-        out[4] = err;
-        out[5] = 1;
-        out[6] = (int)(steps & 0x7fffffff);
+        out[kBoIterations] = iterations;
+        out[kBoConverged] = converged;
+        out[kBoWarnings] = n_warn;
+        out[kBoEntries] = total;
+        out[kBoError] = err;
+        out[kBoDone] = 1;
+        out[kBoSteps] = (int)(steps & 0x7fffffff);
     }
 }
 
