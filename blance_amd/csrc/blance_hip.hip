@@ -31,6 +31,7 @@
 #include "host/json_escape.hpp"
 #include "host/problem_facts.hpp"
 #include "host/batch_layout.hpp"
+#include "host/wire_names.hpp"
 #ifdef BLANCE_SIMT_EMU          /* the emulator build is one translation unit */
 #include "tu_seq.hip"
 #include "tu_tree.hip"
@@ -256,6 +257,19 @@ struct blance_wire_dict {
     DevBuf slots[3], bytes[3], off[3];
 };
 
+// blance_calc_moves: inputs, per-partition slices, offsets, compacted outputs.  blance_plan_moves_get reads both maps where the
+// plan left them and keeps beg_other's CSR in the two buffers of the begin map (other_off / other_nodes); n_moves then has
+// its counters in front, c_* the moves at their final places.
+struct MovesBufs {
+    DevBuf beg_off, beg_nodes, end_off, end_nodes, op_node, op_state, op_kind, n_moves, c_node, c_state, c_kind;
+    DevBuf& other_off() { return beg_off; }
+    DevBuf& other_nodes() { return beg_nodes; }
+};
+// blance_plan_wire_names' eight tables (WireTables has the same names), k_wire_size's lengths, the document
+struct WireOutBufs { DevBuf order, part_esc, part_off, node_esc, node_off, state_esc, state_off, state_id, len, doc; };
+// the decoder: the document's copy, the record split's scratch, the claims, the decoded CSR (part_kind, kind, off, nodes)
+struct WireInBufs { DevBuf doc, tb, qbits, quotes, depth, count, rec, claim, part_kind, kind, off, nodes, refusal; };
+
 struct Mover;
 enum PassKind { kPassKernel = 0, kPassFlatBulk = 1, kPassBlank = 2, kPassStayTop = 3 };   // what ran a state pass (statistics)
 
@@ -323,18 +337,18 @@ struct blance_ctx : CtxHandles {
     struct RbItem { void* dst; size_t off, bytes; };
     std::vector<RbItem> rb_items;
     DevBuf vres, vseen;             // blance_upload: the device's part of the validation (k_validate_parts)
-    DevBuf mv[11];                  // blance_calc_moves: inputs, per-partition slices, offsets, compacted outputs (kept between calls)
+    MovesBufs mv;                   // blance_calc_moves, blance_plan_moves_get (kept between calls)
     // blance_plan_wire_names / blance_plan_wire_get: the names of the problem the context holds in their
     // escaped forms and document order, the byte offsets of the ranks, the document
     bool wire_names = false;        // `wire` holds the names of the problem uploaded last
     int wire_stage = kWireStageDefault;   // bytes of k_wire_write's LDS stage (test knob BLANCE_WIRE_STAGE lowers it)
-    DevBuf wire[10];
+    WireOutBufs wire;
     // blance_wire_dict_create / blance_wire_decode_device: the dictionaries made on this context, the
     // document's copy and the scratch of the decoder (kept between calls)
     int wd_tile = kWdTileDefault;   // bytes of a tile of the record split (test knob BLANCE_WIRE_IN_TILE lowers it)
     int wd_stage = kWdStageDefault; // bytes of k_wd_parse's LDS stage (test knob BLANCE_WIRE_IN_STAGE)
     std::vector<blance_wire_dict*> wd_dicts;
-    DevBuf wd[13];
+    WireInBufs wd;
     int64_t comm_calls = 0, comm_bytes = 0;
     size_t comm_events_used = 0;             // (comm_events: CtxHandles)
     double comm_ms = 0.0;                    // device time between those pairs, all plans so far
@@ -3293,8 +3307,9 @@ static int calc_moves_locked(blance_ctx* c, const blance_moves_problem* pb, blan
     if (cap > res->capacity) return fail(BLANCE_ERR_CAPACITY, "moves capacity too small");
     if (cap > (int64_t)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "more than 2^31 list entries");
     HIPTRY(hipSetDevice(c->device));
-    DevBuf &boff = c->mv[0], &bnod = c->mv[1], &eoff = c->mv[2], &enod = c->mv[3], &onode = c->mv[4], &ostate = c->mv[5],
-           &okind = c->mv[6], &nmov = c->mv[7], &cnode = c->mv[8], &cstate = c->mv[9], &ckind = c->mv[10];
+    MovesBufs& mb = c->mv;
+    DevBuf &boff = mb.beg_off, &bnod = mb.beg_nodes, &eoff = mb.end_off, &enod = mb.end_nodes, &onode = mb.op_node, &ostate = mb.op_state,
+           &okind = mb.op_kind, &nmov = mb.n_moves, &cnode = mb.c_node, &cstate = mb.c_state, &ckind = mb.c_kind;
     auto up = [&](DevBuf& b, const int32_t* src, size_t n) -> int {
         if (b.reserve(sizeof(int32_t) * (n + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
         if (n) HIPTRY(hipMemcpyAsync(b.p, src, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
@@ -3394,6 +3409,29 @@ static bool adopt_load_overflows(const blance_ctx* c, const PartsSummary& ps, bo
     return adopt_load_bound_exceeded(ps.aprev, keep ? c->kept_load_abs : 0, ps.sumw, ksum);
 }
 
+// neither adopts on a context with a communicator; who: the entry point, for the text
+static int comm_refuse(const blance_ctx* c, const char* who) {
+    if (comm_active(c) || c->rccl_comm || c->comm.allreduce_sum_i32 || c->comm.allgather_i32)
+        return fail(BLANCE_ERR_UNSUPPORTED, "%s on a context with a communicator", who);
+    return BLANCE_OK;
+}
+
+// Where a summary block keeps what validate_tail_b and upload_facts want of P' (k_adopt_len: kAdoptRes*, k_wire_adopt_sum:
+// kWaRes*): int32 words, and 64-bit words counted from word 4 of the block.  fresh < 0: the block has no such word, no
+// partition of P' is outside its prevMap
+struct SummaryWords { int longest, fresh, kinds, cap64, prev64, total64; };
+constexpr SummaryWords kAdoptSummary{kAdoptResLongest, -1, kAdoptResKinds, kAdoptRes64Cap, kAdoptRes64Prev, kAdoptRes64Total};
+constexpr SummaryWords kWaSummary{kWaResLongest, kWaResFresh, kWaResKinds, kWaRes64Cap, kWaRes64Prev, kWaRes64Total};
+static UploadSummary adopt_summary(const blance_ctx* c, const int32_t* vr, const SummaryWords& w) {
+    long long r64[5];
+    memcpy(r64, vr + 4, sizeof r64);
+    UploadSummary sum;
+    sum.ps = PartsSummary{vr[w.longest], w.fresh < 0 ? 0 : vr[w.fresh], r64[w.cap64], c->sum_abs_weight, r64[w.prev64]};
+    sum.assign_kinds = (uint32_t)vr[w.kinds];
+    sum.na = r64[w.total64];
+    return sum;
+}
+
 // The second half of both: from here on the problem is rewritten, a failure leaves the context without one, as a failed
 // upload does.  q: adopt_shell's problem with n_prev and n_loads set; na / np: the entries a_nodes / p_nodes must hold (-1:
 // the buffer stays as it is); write_lists launches the kernel that writes the lists and the partitions' flags.
@@ -3459,8 +3497,7 @@ static int adopt_locked(blance_ctx* c, const blance_adopt* ad) {
     if (c->stats.iterations == 0) return fail(BLANCE_ERR_BAD_ARG, "the plan made no sweep (max_iterations <= 0): there is no map to adopt");
     if (!ad->node_removed || !ad->node_added) return fail(BLANCE_ERR_BAD_ARG, "null array pointer");
     for (int32_t r : ad->reserved) if (r) return fail(BLANCE_ERR_BAD_ARG, "blance_adopt::reserved must be zero");
-    if (comm_active(c) || c->rccl_comm || c->comm.allreduce_sum_i32 || c->comm.allgather_i32)
-        return fail(BLANCE_ERR_UNSUPPORTED, "blance_plan_adopt on a context with a communicator");
+    if (int st = comm_refuse(c, "blance_plan_adopt")) return st;
     HIPTRY(hipSetDevice(c->device));
     const blance_problem& h = c->h;
     const int M = h.n_states, P = h.n_parts;
@@ -3497,13 +3534,7 @@ static int adopt_locked(blance_ctx* c, const blance_adopt* ad) {
         HIPTRY(read_back(c, vr, ap.res, sizeof vr));
         HIPTRY(stream_sync(c));
         HIPTRY(hipGetLastError());
-        long long r64[5];
-        memcpy(r64, vr + 4, sizeof r64);
-        sum.ps.L = vr[kAdoptResLongest];
-        sum.ps.cap = r64[kAdoptRes64Cap];
-        sum.ps.aprev = r64[kAdoptRes64Prev];
-        sum.assign_kinds = (uint32_t)vr[kAdoptResKinds];
-        sum.na = r64[kAdoptRes64Total];
+        sum = adopt_summary(c, vr, kAdoptSummary);
         if (sum.na > (long long)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "more than 2^31 list entries");
     }
     if (adopt_load_overflows(c, sum.ps, keep)) return fail(BLANCE_ERR_UNSUPPORTED, "partition weights overflow the int32 load tables");
@@ -3529,15 +3560,21 @@ extern "C" int blance_plan_adopt(blance_ctx* c, const blance_adopt* ad) {
     });
 }
 
+// a statistics request: the six mandatory arrays, their capacity (blance_plan_stats_get and every problem of a batch)
+static int stats_arrays_check(const blance_plan_stats* st, int n_states) {
+    if (st->n_states < n_states || !st->load_min || !st->load_max || !st->load_sum || !st->load_sumsq || !st->nodes_used ||
+        !st->unmet_slots)
+        return fail(BLANCE_ERR_BAD_ARG, "stats arrays missing or shorter than n_states");
+    return BLANCE_OK;
+}
+
 // the statistics of the map the context holds (blance_plan_stats_get; a batch's single-path problems); *launches grows by
 // the kernels launched
 static int plan_stats_locked(blance_ctx* c, blance_plan_stats* st, int64_t* launches = nullptr) {
     if (!c->planned) return fail(BLANCE_ERR_BAD_ARG, "nothing planned yet");
     const blance_problem& h = c->h;
     const int N = h.n_nodes, NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts;
-    if (st->n_states < M || !st->load_min || !st->load_max || !st->load_sum || !st->load_sumsq || !st->nodes_used ||
-        !st->unmet_slots)
-        return fail(BLANCE_ERR_BAD_ARG, "stats arrays missing or shorter than n_states");
+    if (int e = stats_arrays_check(st, M)) return e;
     HIPTRY(hipSetDevice(c->device));
     hipStream_t sm = c->stream;
     DevBuf load, out, cons, unmet, roff;
@@ -3593,6 +3630,26 @@ extern "C" int blance_plan_stats_get(blance_ctx* c, blance_plan_stats* st) {
     });
 }
 
+// the CSR of the prevMap keys outside the model, where a moves request has one (blance_plan_moves_get and every problem of
+// a batch): P + 1 offsets from 0, not falling, every node an id of the problem's
+static int beg_other_check(const int32_t* off, const int32_t* nodes, int P, int NX) {
+    if (!off) return BLANCE_OK;
+    if (off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets must start at 0");
+    for (int p = 0; p < P; p++)
+        if (off[p + 1] < off[p]) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets not monotone");
+    for (int32_t j = 0; j < off[P]; j++)
+        if (nodes[j] < 0 || nodes[j] >= NX) return fail(BLANCE_ERR_BAD_ARG, "beg_other node id outside [0, n_nodes_ext)");
+    return BLANCE_OK;
+}
+
+// prev_off[P*M] + beg_other_off[P] + blance_result_capacity(pb) (blance_plan_moves_capacity, blance_batch_moves_capacity)
+static int64_t moves_capacity(const blance_problem* pb, const int32_t* beg_other_off) {
+    if (!pb || !pb->prev_off || pb->n_parts < 0 || pb->n_states < 0) return 0;
+    int64_t cap = pb->prev_off[(size_t)pb->n_parts * pb->n_states] + blance_result_capacity(pb);
+    if (beg_other_off) cap += beg_other_off[pb->n_parts];
+    return cap;
+}
+
 // the partition moves of the map the context holds (blance_plan_moves_get): both maps are read where the
 // plan left them, k_plan_moves counts, the counts are scanned, k_plan_moves writes every move at its final place
 static int plan_moves_locked(blance_ctx* c, blance_plan_moves* mv) {
@@ -3607,17 +3664,8 @@ static int plan_moves_locked(blance_ctx* c, blance_plan_moves* mv) {
         return fail(BLANCE_ERR_BAD_ARG, "beg_other_off and beg_other_nodes: both or neither");
     const blance_problem& h = c->h;
     const int P = h.n_parts, M = h.n_states;
-    int64_t n_other = 0;
-    if (mv->beg_other_off) {
-        const int32_t* off = mv->beg_other_off;
-        if (off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets must start at 0");
-        for (int p = 0; p < P; p++)
-            if (off[p + 1] < off[p]) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets not monotone");
-        n_other = off[P];
-        for (int64_t j = 0; j < n_other; j++)
-            if (mv->beg_other_nodes[j] < 0 || mv->beg_other_nodes[j] >= h.n_nodes_ext)
-                return fail(BLANCE_ERR_BAD_ARG, "beg_other node id outside [0, n_nodes_ext)");
-    }
+    if (int e = beg_other_check(mv->beg_other_off, mv->beg_other_nodes, P, h.n_nodes_ext)) return e;
+    const int64_t n_other = mv->beg_other_off ? mv->beg_other_off[P] : 0;
     HIPTRY(hipSetDevice(c->device));
     hipStream_t sm = c->stream;
     unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
@@ -3625,7 +3673,8 @@ static int plan_moves_locked(blance_ctx* c, blance_plan_moves* mv) {
     if (P > 0) {
         constexpr size_t kHead = 1024;             // the six counter words, a cache line each, in front of n_moves [P + 1]
         static_assert(6 * kPlanMovesCounterStride * sizeof(unsigned long long) <= kHead, "counters outgrew their block");
-        DevBuf &ooff = c->mv[0], &onod = c->mv[1], &nmov = c->mv[7], &cnode = c->mv[8], &cstate = c->mv[9], &ckind = c->mv[10];
+        DevBuf &ooff = c->mv.other_off(), &onod = c->mv.other_nodes(), &nmov = c->mv.n_moves, &cnode = c->mv.c_node,
+               &cstate = c->mv.c_state, &ckind = c->mv.c_kind;
         if (nmov.reserve(kHead + sizeof(int32_t) * ((size_t)P + 2)) || ooff.reserve(sizeof(int32_t) * ((size_t)P + 2)) ||
             onod.reserve(sizeof(int32_t) * ((size_t)n_other + 1)))
             return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
@@ -3698,10 +3747,7 @@ static int plan_moves_locked(blance_ctx* c, blance_plan_moves* mv) {
 }
 
 extern "C" int64_t blance_plan_moves_capacity(const blance_problem* pb, const blance_plan_moves* mv) {
-    if (!pb || !pb->prev_off || pb->n_parts < 0 || pb->n_states < 0) return 0;
-    int64_t cap = pb->prev_off[(size_t)pb->n_parts * pb->n_states] + blance_result_capacity(pb);
-    if (mv && mv->beg_other_off) cap += mv->beg_other_off[pb->n_parts];
-    return cap;
+    return moves_capacity(pb, mv ? mv->beg_other_off : nullptr);
 }
 
 extern "C" int blance_plan_moves_get(blance_ctx* c, blance_plan_moves* mv) {
@@ -3712,84 +3758,30 @@ extern "C" int blance_plan_moves_get(blance_ctx* c, blance_plan_moves* mv) {
 }
 
 // ---- the planned map as PartitionMap JSON bytes (blance_plan_wire_names / blance_plan_wire_get)
-namespace {
-struct WireBlob { const char* bytes; const int64_t* off; int64_t n; };
-inline int wire_cmp(const WireBlob& b, int64_t x, int64_t y) {       // bytewise, as the host encoder orders map keys
-    const size_t xn = (size_t)(b.off[x + 1] - b.off[x]), yn = (size_t)(b.off[y + 1] - b.off[y]);
-    const size_t m = xn < yn ? xn : yn;
-    const int c = m ? memcmp(b.bytes + b.off[x], b.bytes + b.off[y], m) : 0;
-    if (c) return c;
-    return xn < yn ? -1 : (xn > yn ? 1 : 0);
-}
-// the ids of a blob's strings in byte order of the strings; false: two strings are equal
-bool wire_sort(const WireBlob& b, std::vector<int32_t>& order) {
-    const int64_t n = b.n;
-    order.resize((size_t)n);
-    for (int64_t i = 0; i < n; i++) order[(size_t)i] = (int32_t)i;
-    bool sorted = true;                                  // already in key order, strictly?  (then there is no duplicate either)
-    for (int64_t i = 1; i < n && sorted; i++) sorted = wire_cmp(b, i - 1, i) < 0;
-    if (sorted) return true;
-    // by the first eight bytes as one big-endian word (a shorter string padded with zeros), the whole strings on a tie
-    struct Key { uint64_t pre; int32_t id; };
-    std::vector<Key> keys((size_t)n);
-    for (int64_t i = 0; i < n; i++) {
-        const size_t len = (size_t)(b.off[i + 1] - b.off[i]);
-        uint64_t pre = 0;
-        for (size_t k = 0; k < 8; k++) pre = (pre << 8) | (k < len ? (unsigned char)b.bytes[b.off[i] + (int64_t)k] : 0u);
-        keys[(size_t)i] = Key{pre, (int32_t)i};
-    }
-    std::sort(keys.begin(), keys.end(), [&](const Key& x, const Key& y) {
-        if (x.pre != y.pre) return x.pre < y.pre;
-        return wire_cmp(b, x.id, y.id) < 0;
-    });
-    for (int64_t i = 0; i < n; i++) order[(size_t)i] = keys[(size_t)i].id;
-    for (int64_t i = 1; i < n; i++)
-        if (wire_cmp(b, order[(size_t)i - 1], order[(size_t)i]) == 0) return false;
-    return true;
-}
-// the escaped forms of a blob's strings in the order `order` gives (null: as they lie), `tail` behind each, with n + 1 offsets;
-// false: 2^31 bytes or more
-bool wire_escape(const WireBlob& b, const int32_t* order, const char* tail, std::string& out, std::vector<int32_t>& off) {
-    off.assign((size_t)b.n + 1, 0);
-    for (int64_t i = 0; i < b.n; i++) {
-        const int64_t id = order ? order[(size_t)i] : i;
-        blance_json::put_string(out, b.bytes + b.off[id], (size_t)(b.off[id + 1] - b.off[id]));
-        out += tail;
-        if (out.size() > (size_t)INT32_MAX) return false;
-        off[(size_t)i + 1] = (int32_t)out.size();
-    }
-    return true;
-}
-}  // namespace
 
-// What the document needs of the names alone, prepared on the host: the partitions' order, every string escaped.
-struct WirePrepared {
-    std::vector<int32_t> order, sorder, poff, noff, soff;
-    std::string pesc, nesc, sesc;
-};
-
-// pure host: the checks of the names and their prepared tables (blance_plan_wire_names and blance_batch_names_create)
-static int wire_prepare(const blance_wire_names* nm, int64_t n_parts, int64_t n_nodes_ext, int64_t n_states, WirePrepared& w) {
-    const WireBlob part{nm->part_bytes, nm->part_off, n_parts}, node{nm->node_bytes, nm->node_off, n_nodes_ext},
-        state{nm->state_bytes, nm->state_off, n_states};
-    for (const WireBlob* b : {&part, &node, &state}) {
-        if (!b->off) return fail(BLANCE_ERR_BAD_ARG, "null offsets");
-        if (b->off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "name offsets must start at 0");
-        for (int64_t i = 0; i < b->n; i++)
-            if (b->off[i + 1] < b->off[i]) return fail(BLANCE_ERR_BAD_ARG, "name offsets not monotone");
-        if (b->off[b->n] > 0 && !b->bytes) return fail(BLANCE_ERR_BAD_ARG, "null name bytes");
-    }
-    if (!wire_sort(state, w.sorder)) return fail(BLANCE_ERR_BAD_ARG, "two states with one name");
-    if (!wire_sort(part, w.order))
+// What a caller is told of a failure of host/wire_names.hpp, where all the tables of the four entry points are made.  The
+// encoder's two (blance_plan_wire_names, blance_batch_names_create) and the dictionaries' two (blance_wire_dict_create,
+// blance_batch_dict_create) word a negative count and the 2^31 bytes differently; kDupNode comes from the dictionaries alone.
+enum class WireSide { kEncoder, kDict };
+static int wire_fail(WireErr e, WireSide side) {
+    const bool enc = side == WireSide::kEncoder;
+    switch (e) {
+    case WireErr::kNone: return BLANCE_OK;
+    case WireErr::kNegativeSize: return fail(BLANCE_ERR_BAD_ARG, enc ? "negative size" : "negative count");
+    case WireErr::kTooManyLists: return fail(BLANCE_ERR_BAD_ARG, "n_parts * n_states of 2^31 - 1 or more");
+    case WireErr::kNullOffsets: return fail(BLANCE_ERR_BAD_ARG, "null offsets");
+    case WireErr::kFirstOffset: return fail(BLANCE_ERR_BAD_ARG, "name offsets must start at 0");
+    case WireErr::kNotMonotone: return fail(BLANCE_ERR_BAD_ARG, "name offsets not monotone");
+    case WireErr::kNullBytes: return fail(BLANCE_ERR_BAD_ARG, "null name bytes");
+    case WireErr::kDupPartition:
         return fail(BLANCE_ERR_UNSUPPORTED, "two partitions with one name (the reference's map would keep one of them)");
-    if (!wire_escape(part, w.order.data(), "", w.pesc, w.poff) || !wire_escape(node, nullptr, "", w.nesc, w.noff) ||
-        !wire_escape(state, w.sorder.data(), ":", w.sesc, w.soff))
-        return fail(BLANCE_ERR_UNSUPPORTED, "the escaped names take 2^31 bytes or more");
-    return BLANCE_OK;
+    case WireErr::kDupNode: return fail(BLANCE_ERR_BAD_ARG, "two nodes with one name");
+    case WireErr::kDupState: return fail(BLANCE_ERR_BAD_ARG, "two states with one name");
+    case WireErr::kTooLong:
+        return fail(BLANCE_ERR_UNSUPPORTED, enc ? "the escaped names take 2^31 bytes or more" : "names of 2^31 bytes or more");
+    }
+    return fail(BLANCE_ERR_BAD_ARG, "unknown failure of the names");
 }
-
-// the eight prepared tables in the order of c->wire[0..7]: order, partitions' bytes and offsets, nodes', states', state_id
-struct WireTables { const void* p[8]; size_t bytes[8]; };
 
 static int wire_tables_upload_locked(blance_ctx* c, const WireTables& t) {
     HIPTRY(hipSetDevice(c->device));
@@ -3797,9 +3789,13 @@ static int wire_tables_upload_locked(blance_ctx* c, const WireTables& t) {
     Mover up(c, true);
     c->stage.used = 0;                                   // (the stream is idle between calls)
     int e = 0;
-    for (int i = 0; i < 8; i++) {
-        if (c->wire[i].reserve(t.bytes[i] + 16)) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-        if ((e = up.copy(c->wire[i].p, t.p[i], t.bytes[i]))) return e;
+    WireOutBufs& w = c->wire;
+    const struct { DevBuf& buf; const WireTable& tab; } pairs[8] = {
+        {w.order, t.order}, {w.part_esc, t.part_esc}, {w.part_off, t.part_off}, {w.node_esc, t.node_esc},
+        {w.node_off, t.node_off}, {w.state_esc, t.state_esc}, {w.state_off, t.state_off}, {w.state_id, t.state_id}};
+    for (const auto& x : pairs) {
+        if (x.buf.reserve(x.tab.bytes + 16)) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        if ((e = up.copy(x.buf.p, x.tab.p, x.tab.bytes))) return e;
     }
     if ((e = up.flush())) return e;
     HIPTRY(stream_sync(c));                              // nothing of this frame is read after the call
@@ -3812,14 +3808,8 @@ static int wire_names_locked(blance_ctx* c, const blance_wire_names* nm) {
     if (!c->uploaded) return fail(BLANCE_ERR_BAD_ARG, "no problem on the context (blance_upload or blance_plan first)");
     const blance_problem& h = c->h;
     WirePrepared w;
-    const int st = wire_prepare(nm, h.n_parts, h.n_nodes_ext, h.n_states, w);
-    if (st) return st;
-    const WireTables t{{w.order.data(), w.pesc.data(), w.poff.data(), w.nesc.data(), w.noff.data(), w.sesc.data(), w.soff.data(),
-                        w.sorder.data()},
-                       {sizeof(int32_t) * w.order.size(), w.pesc.size(), sizeof(int32_t) * w.poff.size(), w.nesc.size(),
-                        sizeof(int32_t) * w.noff.size(), w.sesc.size(), sizeof(int32_t) * w.soff.size(),
-                        sizeof(int32_t) * w.sorder.size()}};
-    return wire_tables_upload_locked(c, t);
+    if (int st = wire_fail(wire_prepare(nm, h.n_parts, h.n_nodes_ext, h.n_states, w), WireSide::kEncoder)) return st;
+    return wire_tables_upload_locked(c, wire_tables_of(w));
 }
 
 extern "C" int blance_plan_wire_names(blance_ctx* c, const blance_wire_names* nm) {
@@ -3849,16 +3839,17 @@ static int plan_wire_locked(blance_ctx* c, char* buf, size_t cap, size_t* need, 
     HIPTRY(hipSetDevice(c->device));
     hipStream_t sm = c->stream;
     constexpr size_t kHead = 256;                        // the 64-bit total on a cache line of its own, in front of len [P + 1]
-    DevBuf &wlen = c->wire[8], &wdoc = c->wire[9];
+    WireOutBufs& w = c->wire;
+    DevBuf &wlen = w.len, &wdoc = w.doc;
     if (wlen.reserve(kHead + sizeof(int32_t) * ((size_t)P + 2))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
     const DevProblem d = result_problem(c);
     PlanWireParams q;
     memset(&q, 0, sizeof q);
     q.P = P; q.M = h.n_states; q.L = d.L; q.NX = h.n_nodes_ext;
-    q.order = c->wire[0].as<int32_t>();
-    q.part_esc = c->wire[1].as<char>(); q.part_off = c->wire[2].as<int32_t>();
-    q.node_esc = c->wire[3].as<char>(); q.node_off = c->wire[4].as<int32_t>();
-    q.state_esc = c->wire[5].as<char>(); q.state_off = c->wire[6].as<int32_t>(); q.state_id = c->wire[7].as<int32_t>();
+    q.order = w.order.as<int32_t>();
+    q.part_esc = w.part_esc.as<char>(); q.part_off = w.part_off.as<int32_t>();
+    q.node_esc = w.node_esc.as<char>(); q.node_off = w.node_off.as<int32_t>();
+    q.state_esc = w.state_esc.as<char>(); q.state_off = w.state_off.as<int32_t>(); q.state_id = w.state_id.as<int32_t>();
     q.lists = d.live; q.list_len = d.live_len; q.list_kind = d.live_kind;
     q.total = wlen.as<unsigned long long>();
     q.len = (int32_t*)((char*)wlen.p + kHead);
@@ -3907,69 +3898,6 @@ extern "C" int blance_plan_wire_get(blance_ctx* c, char* buf, size_t cap, size_t
 }
 
 // ---- a PartitionMap document decoded on the device (blance_wire_dict_create / blance_wire_decode_device)
-namespace {
-// the open-addressing table of a blob's names (k_wire_decode.h: WdTable) at load <= 1/2 and the offsets as int32;
-// 0, or 1: two names are equal, 2: 2^31 bytes or more
-int wd_build_table(const WireBlob& b, std::vector<int32_t>& slots, uint32_t& mask, std::vector<int32_t>& off32) {
-    if (b.off[b.n] > (int64_t)INT32_MAX) return 2;
-    size_t cap = 2;
-    while (cap < 2 * (size_t)b.n) cap <<= 1;
-    mask = (uint32_t)(cap - 1);
-    slots.assign(2 * cap, -1);
-    off32.resize((size_t)b.n + 1);
-    for (int64_t i = 0; i <= b.n; i++) off32[(size_t)i] = (int32_t)b.off[i];
-    for (int64_t i = 0; i < b.n; i++) {
-        const unsigned char* s = (const unsigned char*)b.bytes + b.off[i];
-        const int n = (int)(b.off[i + 1] - b.off[i]);
-        uint32_t h = wd_hash_init();
-        for (int k = 0; k < n; k++) h = wd_hash_step(h, s[k]);
-        h = wd_hash_done(h, n);
-        uint32_t at = h & mask;
-        for (;;) {
-            const int32_t id = slots[2 * (size_t)at];
-            if (id < 0) break;
-            if ((uint32_t)slots[2 * (size_t)at + 1] == h && wire_cmp(b, id, i) == 0) return 1;
-            at = (at + 1) & mask;
-        }
-        slots[2 * (size_t)at] = (int32_t)i;
-        slots[2 * (size_t)at + 1] = (int32_t)h;
-    }
-    return 0;
-}
-}  // namespace
-
-// what a dictionary is made of on the host (blance_wire_dict_create and blance_batch_dict_create share it): per kind of name
-// wd_build_table's table and int32 offsets, and where the raw names lie (the caller's blobs, or a batch dictionary's block)
-struct WdHostTables {
-    int32_t n[3] = {0, 0, 0};
-    uint32_t mask[3] = {0, 0, 0};
-    std::vector<int32_t> slots[3], off32[3];
-    const void* bytes[3] = {nullptr, nullptr, nullptr};
-};
-
-// pure host: the checks of blance_wire_dict_create and the three tables
-static int wd_host_tables(const blance_wire_names* nm, int32_t P, int32_t NX, int32_t M, WdHostTables& t) {
-    if (P < 0 || NX < 0 || M < 0) return fail(BLANCE_ERR_BAD_ARG, "negative count");
-    if ((int64_t)P * M >= (int64_t)INT32_MAX) return fail(BLANCE_ERR_BAD_ARG, "n_parts * n_states of 2^31 - 1 or more");
-    const WireBlob blobs[3] = {{nm->part_bytes, nm->part_off, P}, {nm->node_bytes, nm->node_off, NX}, {nm->state_bytes, nm->state_off, M}};
-    for (const WireBlob& b : blobs) {
-        if (!b.off) return fail(BLANCE_ERR_BAD_ARG, "null offsets");
-        if (b.off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "name offsets must start at 0");
-        for (int64_t i = 0; i < b.n; i++)
-            if (b.off[i + 1] < b.off[i]) return fail(BLANCE_ERR_BAD_ARG, "name offsets not monotone");
-        if (b.off[b.n] > 0 && !b.bytes) return fail(BLANCE_ERR_BAD_ARG, "null name bytes");
-    }
-    for (int k = 0; k < 3; k++) {
-        t.n[k] = (int32_t)blobs[k].n;
-        t.bytes[k] = blobs[k].bytes;
-        const int e = wd_build_table(blobs[k], t.slots[k], t.mask[k], t.off32[k]);
-        if (e == 2) return fail(BLANCE_ERR_UNSUPPORTED, "names of 2^31 bytes or more");
-        if (e == 1 && k == 0) return fail(BLANCE_ERR_UNSUPPORTED, "two partitions with one name (the reference's map would keep one of them)");
-        if (e == 1) return fail(BLANCE_ERR_BAD_ARG, k == 1 ? "two nodes with one name" : "two states with one name");
-    }
-    return BLANCE_OK;
-}
-
 // the tables as a dictionary of the context
 static int wire_dict_upload_locked(blance_ctx* c, const WdHostTables& t, blance_wire_dict** out) {
     std::unique_ptr<blance_wire_dict> d(new blance_wire_dict());
@@ -3998,7 +3926,7 @@ static int wire_dict_upload_locked(blance_ctx* c, const WdHostTables& t, blance_
 
 static int wire_dict_locked(blance_ctx* c, const blance_wire_names* nm, int32_t P, int32_t NX, int32_t M, blance_wire_dict** out) {
     WdHostTables t;
-    const int e = wd_host_tables(nm, P, NX, M, t);
+    const int e = wire_fail(wd_host_tables(nm, P, NX, M, t), WireSide::kDict);
     return e ? e : wire_dict_upload_locked(c, t, out);
 }
 
@@ -4024,17 +3952,21 @@ extern "C" void blance_wire_dict_destroy(blance_ctx* c, blance_wire_dict* d) {
     });
 }
 
-// The decoder's device part: the record split, both parse passes, the decoded CSR left in c->wd[] (kWdPartKind, kWdOff,
-// kWdKind, kWdNodes) -- blance_wire_decode_device downloads it from there, blance_wire_adopt makes it the problem's lists.
-// The counters, the refusal and the first pass's device_ms go to `out`; its arrays are not touched.  count_only: pass 1
-// alone; check_capacity: out->capacity below the entries ends the call before pass 2.  On BLANCE_OK behind pass 2 the
-// stream is idle and c->ev0 .. c->ev1 span the kernels.
-enum { kWdDoc, kWdTb, kWdQbits, kWdQuotes, kWdDepth, kWdCount, kWdRec, kWdClaim, kWdPartKind, kWdKind, kWdOff, kWdNodes, kWdRefusal };
-static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out,
-                                   bool count_only, bool check_capacity) {
+// what a decode says of its document before it has looked
+static void wire_lists_reset(blance_wire_lists* out) {
     out->n_node_refs = out->n_parts_seen = 0;
     out->refusal = 0; out->refusal_at = -1;
     out->device_ms = out->total_ms = 0.0;
+}
+
+// The decoder's device part: the record split, both parse passes, the decoded CSR left in c->wd (part_kind, off, kind,
+// nodes) -- blance_wire_decode_device downloads it from there, blance_wire_adopt makes it the problem's lists.
+// The counters, the refusal and the first pass's device_ms go to `out`; its arrays are not touched.  count_only: pass 1
+// alone; check_capacity: out->capacity below the entries ends the call before pass 2.  On BLANCE_OK behind pass 2 the
+// stream is idle and c->ev0 .. c->ev1 span the kernels.
+static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out,
+                                   bool count_only, bool check_capacity) {
+    wire_lists_reset(out);
     if (len > (size_t)INT32_MAX) {                       // before anything is launched
         out->refusal = kWdDocumentTooLong; out->refusal_at = 0;
         return fail(BLANCE_ERR_UNSUPPORTED, "refused: a document of 2^31 bytes or more");
@@ -4050,19 +3982,17 @@ static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, con
     q.n_tiles = cdiv((int64_t)len, q.tile);
     q.P = P; q.NX = NX; q.M = M; q.stage = c->wd_stage;
     const size_t nt = (size_t)q.n_tiles;
-    enum { kDoc = kWdDoc, kTb = kWdTb, kQbits = kWdQbits, kQuotes = kWdQuotes, kDepth = kWdDepth, kCount = kWdCount, kRec = kWdRec,
-           kClaim = kWdClaim, kPartKind = kWdPartKind, kKind = kWdKind, kOff = kWdOff, kNodes = kWdNodes, kRefusal = kWdRefusal };
-    DevBuf* w = c->wd;
-    if (w[kDoc].reserve(len + 2 * kWdPad) || w[kTb].reserve(4 * (nt + 1)) || w[kQbits].reserve(nt * (size_t)q.tile / 8 + 16) ||
-        w[kQuotes].reserve(4 * (nt + 2)) || w[kDepth].reserve(4 * (nt + 2)) || w[kCount].reserve(4 * (nt + 2)) ||
-        w[kClaim].reserve(4 * ((size_t)P + 1)) || w[kPartKind].reserve((size_t)P + 1) || w[kKind].reserve((size_t)PM + 1) ||
-        w[kOff].reserve(4 * ((size_t)PM + 2)) || w[kRefusal].reserve(256))
+    WireInBufs& w = c->wd;
+    if (w.doc.reserve(len + 2 * kWdPad) || w.tb.reserve(4 * (nt + 1)) || w.qbits.reserve(nt * (size_t)q.tile / 8 + 16) ||
+        w.quotes.reserve(4 * (nt + 2)) || w.depth.reserve(4 * (nt + 2)) || w.count.reserve(4 * (nt + 2)) ||
+        w.claim.reserve(4 * ((size_t)P + 1)) || w.part_kind.reserve((size_t)P + 1) || w.kind.reserve((size_t)PM + 1) ||
+        w.off.reserve(4 * ((size_t)PM + 2)) || w.refusal.reserve(256))
         return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-    q.doc = w[kDoc].as<unsigned char>();
-    q.tb = w[kTb].as<int32_t>(); q.qbits = w[kQbits].as<uint32_t>();
-    q.quotes = w[kQuotes].as<int32_t>(); q.depth = w[kDepth].as<int32_t>(); q.count = w[kCount].as<int32_t>();
-    q.claim = w[kClaim].as<int32_t>(); q.part_kind = w[kPartKind].as<uint8_t>(); q.kind = w[kKind].as<uint8_t>();
-    q.off = w[kOff].as<int32_t>(); q.refusal = w[kRefusal].as<unsigned long long>();
+    q.doc = w.doc.as<unsigned char>();
+    q.tb = w.tb.as<int32_t>(); q.qbits = w.qbits.as<uint32_t>();
+    q.quotes = w.quotes.as<int32_t>(); q.depth = w.depth.as<int32_t>(); q.count = w.count.as<int32_t>();
+    q.claim = w.claim.as<int32_t>(); q.part_kind = w.part_kind.as<uint8_t>(); q.kind = w.kind.as<uint8_t>();
+    q.off = w.off.as<int32_t>(); q.refusal = w.refusal.as<unsigned long long>();
     const blance_wire_dict& dd = *d;
     WdTable* tabs[3] = {&q.part, &q.node, &q.state};
     for (int k = 0; k < 3; k++)
@@ -4071,14 +4001,14 @@ static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, con
     {
         Mover up(c, true);
         c->stage.used = 0;                               // (the stream is idle between calls)
-        if ((e = up.copy(w[kDoc].p, json, len))) return e;
+        if ((e = up.copy(w.doc.p, json, len))) return e;
         if ((e = up.flush())) return e;
     }
-    HIPTRY(hipMemsetAsync(w[kClaim].p, 0, 4 * ((size_t)P + 1), sm));
-    HIPTRY(hipMemsetAsync(w[kPartKind].p, 0, (size_t)P + 1, sm));
-    HIPTRY(hipMemsetAsync(w[kKind].p, 0, (size_t)PM + 1, sm));
-    HIPTRY(hipMemsetAsync(w[kOff].p, 0, 4 * ((size_t)PM + 2), sm));
-    HIPTRY(hipMemsetAsync(w[kRefusal].p, 0xFF, 8, sm));
+    HIPTRY(hipMemsetAsync(w.claim.p, 0, 4 * ((size_t)P + 1), sm));
+    HIPTRY(hipMemsetAsync(w.part_kind.p, 0, (size_t)P + 1, sm));
+    HIPTRY(hipMemsetAsync(w.kind.p, 0, (size_t)PM + 1, sm));
+    HIPTRY(hipMemsetAsync(w.off.p, 0, 4 * ((size_t)PM + 2), sm));
+    HIPTRY(hipMemsetAsync(w.refusal.p, 0xFF, 8, sm));
     HIPTRY(hipEventRecord(c->ev0, sm));
     // stage 1: the record starts (a hint: k_wire_decode.h)
     int32_t R = 0;
@@ -4095,8 +4025,8 @@ static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, con
         HIPTRY(stream_sync(c));
         HIPTRY(hipGetLastError());
         if (R < 0 || (size_t)R > len) return fail(BLANCE_ERR_DEVICE, "k_wd_walk: a record count outside the document");
-        if (w[kRec].reserve(4 * ((size_t)R + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-        q.rec = w[kRec].as<int32_t>();
+        if (w.rec.reserve(4 * ((size_t)R + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+        q.rec = w.rec.as<int32_t>();
         if (R > 0) BLANCE_LAUNCH_NOSYNC(k_wd_walk<2>, wgs, 256, 0, sm, q);
     }
     q.R = R;
@@ -4126,8 +4056,8 @@ static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, con
     if (count_only) return BLANCE_OK;
     if (check_capacity && out->capacity < (int64_t)total) return fail(BLANCE_ERR_CAPACITY, "the caller's nodes array is too small (see n_node_refs)");
     // pass 2: the node ids
-    if (w[kNodes].reserve(4 * ((size_t)total + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
-    q.nodes = w[kNodes].as<int32_t>();
+    if (w.nodes.reserve(4 * ((size_t)total + 1))) return fail(BLANCE_ERR_DEVICE, "hipMalloc failed");
+    q.nodes = w.nodes.as<int32_t>();
     if (total > 0) BLANCE_LAUNCH(k_wd_parse<true>, wgs2, kWdRun, (size_t)q.stage, sm, q);
     HIPTRY(hipEventRecord(c->ev1, sm));
     unsigned long long again = 0;
@@ -4139,9 +4069,7 @@ static int wire_decode_device_part(blance_ctx* c, const blance_wire_dict* d, con
 }
 
 static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const char* json, size_t len, blance_wire_lists* out) {
-    out->n_node_refs = out->n_parts_seen = 0;
-    out->refusal = 0; out->refusal_at = -1;
-    out->device_ms = out->total_ms = 0.0;
+    wire_lists_reset(out);
     if (std::find(c->wd_dicts.begin(), c->wd_dicts.end(), d) == c->wd_dicts.end())
         return fail(BLANCE_ERR_BAD_ARG, "the dictionary is not one of this context's");
     if (out->capacity < 0 || (!out->nodes && out->capacity > 0)) return fail(BLANCE_ERR_BAD_ARG, "nodes NULL with a capacity, or a negative capacity");
@@ -4155,10 +4083,10 @@ static int wire_decode_locked(blance_ctx* c, const blance_wire_dict* d, const ch
     {   // the download
         Mover down(c, false);
         c->stage.used = 0;
-        if ((e = down.copy(out->part_kind, c->wd[kWdPartKind].p, (size_t)P))) return e;
-        if ((e = down.copy(out->off, c->wd[kWdOff].p, 4 * ((size_t)PM + 1)))) return e;
-        if ((e = down.copy(out->kind, c->wd[kWdKind].p, (size_t)PM))) return e;
-        if ((e = down.copy(out->nodes, c->wd[kWdNodes].p, 4 * (size_t)total))) return e;
+        if ((e = down.copy(out->part_kind, c->wd.part_kind.p, (size_t)P))) return e;
+        if ((e = down.copy(out->off, c->wd.off.p, 4 * ((size_t)PM + 1)))) return e;
+        if ((e = down.copy(out->kind, c->wd.kind.p, (size_t)PM))) return e;
+        if ((e = down.copy(out->nodes, c->wd.nodes.p, 4 * (size_t)total))) return e;
         if ((e = down.finish())) return e;
     }
     HIPTRY(stream_sync(c));
@@ -4196,8 +4124,7 @@ static int wire_adopt_locked(blance_ctx* c, struct blance_wire_adopt* wa) {
     const int NX = h.n_nodes_ext, M = h.n_states, P = h.n_parts;
     if (d->n[0] != P || d->n[1] != NX || d->n[2] != M)
         return fail(BLANCE_ERR_BAD_ARG, "the dictionary's sizes are not those of the problem the context holds");
-    if (comm_active(c) || c->rccl_comm || c->comm.allreduce_sum_i32 || c->comm.allgather_i32)
-        return fail(BLANCE_ERR_UNSUPPORTED, "blance_wire_adopt on a context with a communicator");
+    if (int st = comm_refuse(c, "blance_wire_adopt")) return st;
     HIPTRY(hipSetDevice(c->device));
     const int64_t PM = (int64_t)P * M;
     const bool keep = wa->keep_prev_only != 0, assign_too = wa->assign_too != 0;
@@ -4218,8 +4145,8 @@ static int wire_adopt_locked(blance_ctx* c, struct blance_wire_adopt* wa) {
     memset(&ap, 0, sizeof ap);
     ap.P = P; ap.M = M; ap.L = c->L; ap.weights_nil = h.partition_weights_nil; ap.assign_too = assign_too ? 1 : 0;
     for (int m = 0; m < M; m++) ap.k[m] = c->state_constraints[m];
-    ap.part_kind = c->wd[kWdPartKind].as<uint8_t>(); ap.off = c->wd[kWdOff].as<int32_t>();
-    ap.kind = c->wd[kWdKind].as<uint8_t>(); ap.nodes = c->wd[kWdNodes].as<int32_t>();
+    ap.part_kind = c->wd.part_kind.as<uint8_t>(); ap.off = c->wd.off.as<int32_t>();
+    ap.kind = c->wd.kind.as<uint8_t>(); ap.nodes = c->wd.nodes.as<int32_t>();
     ap.cur_a_off = c->a_off.as<int32_t>(); ap.cur_a_kind = c->a_kind.as<uint8_t>();
     ap.part_weight = c->part_weight.as<int32_t>(); ap.part_has_weight = c->part_has_weight.as<uint8_t>();
     RESERVE(wire_adopt_res, sizeof(int32_t) * kWireAdoptResWords);
@@ -4243,12 +4170,7 @@ static int wire_adopt_locked(blance_ctx* c, struct blance_wire_adopt* wa) {
         HIPTRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
         wa->device_ms = ms;
     }
-    long long r64[5];
-    memcpy(r64, vr + 4, sizeof r64);
-    UploadSummary sum;
-    sum.ps = PartsSummary{vr[kWaResLongest], vr[kWaResFresh], r64[kWaRes64Cap], c->sum_abs_weight, r64[kWaRes64Prev]};
-    sum.assign_kinds = (uint32_t)vr[kWaResKinds];
-    sum.na = r64[kWaRes64Total];
+    const UploadSummary sum = adopt_summary(c, vr, kWaSummary);
 
     // the refusals: all of them before the problem is touched
     auto refuse = [&](int why, int64_t at, const char* text) {
@@ -4365,25 +4287,9 @@ int batch_moves_check(BatchProblem& b) {
     if (!mv->beg_other_off != !mv->beg_other_nodes)
         return fail(BLANCE_ERR_BAD_ARG, "beg_other_off and beg_other_nodes: both or neither");
     if (pb->max_iterations <= 0) return fail(BLANCE_ERR_BAD_ARG, "moves asked for a problem with max_iterations <= 0 (no map)");
-    if (mv->beg_other_off) {
-        const int32_t* off = mv->beg_other_off;
-        if (off[0] != 0) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets must start at 0");
-        for (int p = 0; p < pb->n_parts; p++)
-            if (off[p + 1] < off[p]) return fail(BLANCE_ERR_BAD_ARG, "beg_other offsets not monotone");
-        for (int32_t j = 0; j < off[pb->n_parts]; j++)
-            if (mv->beg_other_nodes[j] < 0 || mv->beg_other_nodes[j] >= pb->n_nodes_ext)
-                return fail(BLANCE_ERR_BAD_ARG, "beg_other node id outside [0, n_nodes_ext)");
-    }
+    if (int e = beg_other_check(mv->beg_other_off, mv->beg_other_nodes, pb->n_parts, pb->n_nodes_ext)) return e;
     if (!b.dc) b.moves_cap = blance_batch_moves_capacity(pb, mv);
     if (o.capacity < b.moves_cap) return fail(BLANCE_ERR_CAPACITY, "moves capacity too small");
-    return BLANCE_OK;
-}
-
-// the statistics request of one problem: the six mandatory arrays, their capacity (blance_plan_stats_get's own check)
-int batch_stats_check(const blance_problem* pb, const blance_plan_stats* st) {
-    if (st->n_states < pb->n_states || !st->load_min || !st->load_max || !st->load_sum || !st->load_sumsq || !st->nodes_used ||
-        !st->unmet_slots)
-        return fail(BLANCE_ERR_BAD_ARG, "stats arrays missing or shorter than n_states");
     return BLANCE_OK;
 }
 
@@ -4439,54 +4345,22 @@ static int batch_moves_single(blance_ctx* c, const blance_problem* pb, const bla
 }
 
 extern "C" int64_t blance_batch_moves_capacity(const blance_problem* pb, const blance_batch_moves* mv) {
-    if (!pb || !pb->prev_off || pb->n_parts < 0 || pb->n_states < 0) return 0;
-    int64_t cap = pb->prev_off[(size_t)pb->n_parts * pb->n_states] + blance_result_capacity(pb);
-    if (mv && mv->beg_other_off) cap += mv->beg_other_off[pb->n_parts];
-    return cap;
+    return moves_capacity(pb, mv ? mv->beg_other_off : nullptr);
 }
 
 // ---- the prepared names of one index (blance_batch_names): wire_prepare's tables as one block of int32
-// words, the block a batch copies behind a problem's packed input slice (k_batch_wire.h reads it through its header)
-struct blance_batch_names {
+// words (host/wire_names.hpp: NamesBlock), the block a batch copies behind a problem's packed input slice
+struct blance_batch_names : NamesBlock {
     int32_t n_parts = 0, n_nodes_ext = 0, n_states = 0;
-    std::vector<int32_t> block;                          // kBatchNamesHdr word offsets, then the tables
-    size_t part_esc_bytes = 0, state_esc_bytes = 0;      // the sums of blance_batch_wire_capacity
-    int32_t node_esc_max = 0;                            // the longest escaped node name
-    WireTables tables;                                   // the same tables as c->wire[0..7] wants them (the single path)
 };
 
 extern "C" int blance_batch_names_create(const blance_wire_names* names, int32_t n_parts, int32_t n_nodes_ext, int32_t n_states,
                                          blance_batch_names** out) {
     return guarded([&]() -> int {
         if (!names || !out) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-        if (n_parts < 0 || n_nodes_ext < 0 || n_states < 0) return fail(BLANCE_ERR_BAD_ARG, "negative size");
-        WirePrepared w;
-        const int st = wire_prepare(names, n_parts, n_nodes_ext, n_states, w);
-        if (st) return st;
         std::unique_ptr<blance_batch_names> nm(new blance_batch_names);
+        if (int st = wire_fail(names_block_build(names, n_parts, n_nodes_ext, n_states, *nm), WireSide::kEncoder)) return st;
         nm->n_parts = n_parts; nm->n_nodes_ext = n_nodes_ext; nm->n_states = n_states;
-        nm->part_esc_bytes = w.pesc.size();
-        nm->state_esc_bytes = w.sesc.size();
-        for (int32_t x = 0; x < n_nodes_ext; x++) nm->node_esc_max = std::max(nm->node_esc_max, w.noff[(size_t)x + 1] - w.noff[(size_t)x]);
-        // kNamesOrder .. kNamesStateEsc, each table at a multiple of 4 words
-        const void* src[8] = {w.order.data(), w.poff.data(), w.noff.data(), w.soff.data(), w.sorder.data(),
-                              w.pesc.data(), w.nesc.data(), w.sesc.data()};
-        const size_t bytes[8] = {sizeof(int32_t) * w.order.size(), sizeof(int32_t) * w.poff.size(), sizeof(int32_t) * w.noff.size(),
-                                 sizeof(int32_t) * w.soff.size(), sizeof(int32_t) * w.sorder.size(),
-                                 w.pesc.size(), w.nesc.size(), w.sesc.size()};
-        size_t words = kBatchNamesHdr, at[8];
-        for (int i = 0; i < 8; i++) { at[i] = words; words += (((bytes[i] + 3) / 4) + 3) & ~(size_t)3; }
-        if (words > (size_t)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "the escaped names take 2^31 bytes or more");
-        nm->block.assign(words, 0);
-        for (int i = 0; i < 8; i++) {
-            nm->block[(size_t)i] = (int32_t)at[i];
-            if (bytes[i]) memcpy(nm->block.data() + at[i], src[i], bytes[i]);
-        }
-        const int32_t* b = nm->block.data();
-        // (c->wire[0..7]: order, partitions' bytes, their offsets, nodes' bytes, offsets, states' bytes, offsets, state_id)
-        const int to_wire[8] = {kNamesOrder, kNamesPartEsc, kNamesPartOff, kNamesNodeEsc, kNamesNodeOff, kNamesStateEsc,
-                                kNamesStateOff, kNamesStateId};
-        for (int i = 0; i < 8; i++) { nm->tables.p[i] = b + at[to_wire[i]]; nm->tables.bytes[i] = bytes[to_wire[i]]; }
         *out = nm.release();
         return BLANCE_OK;
     });
@@ -4494,24 +4368,16 @@ extern "C" int blance_batch_names_create(const blance_wire_names* names, int32_t
 
 extern "C" void blance_batch_names_destroy(blance_batch_names* nm) { delete nm; }
 
-// blance_batch_wire_capacity's formula (blance_batch.h) for a plan of at most result_cap list entries
-static size_t batch_wire_cap_of(const blance_problem* pb, const blance_batch_names* nm, int64_t result_cap) {
-    const size_t P = (size_t)pb->n_parts, M = (size_t)pb->n_states;
-    return 2 + 29 * P + 2 * nm->part_esc_bytes + P * (nm->state_esc_bytes + 5 * M) + (size_t)result_cap * ((size_t)nm->node_esc_max + 1);
-}
-
 extern "C" size_t blance_batch_wire_capacity(const blance_problem* pb, const blance_batch_names* nm) {
     if (!pb || !nm || pb->n_parts < 0 || pb->n_states < 0) return 0;
-    return batch_wire_cap_of(pb, nm, blance_result_capacity(pb));
+    return batch_wire_cap_of(pb, *nm, blance_result_capacity(pb));
 }
 
 // ---- the dictionary of one index for blance_plan_batch_docs (blance_batch_dict): wd_host_tables' tables
-// as one block of int32 words, the block a batch copies behind a problem's packed input slice (k_batch_decode.h reads it
-// through its header); `tables` is the same as blance_wire_dict_create wants it (the single path), its names in the block
-struct blance_batch_dict {
+// as one block of int32 words (host/wire_names.hpp: DictBlock), the block a batch copies behind a problem's packed input
+// slice; `tables` is the same as blance_wire_dict_create wants it (the single path), its names in the block
+struct blance_batch_dict : DictBlock {
     int32_t n_parts = 0, n_nodes_ext = 0, n_states = 0;
-    std::vector<int32_t> block;                          // kBatchDictHdr words, then per kind slots, offsets, raw bytes
-    WdHostTables tables;
 };
 
 extern "C" int blance_batch_dict_create(const blance_wire_names* names, int32_t n_parts, int32_t n_nodes_ext, int32_t n_states,
@@ -4520,28 +4386,8 @@ extern "C" int blance_batch_dict_create(const blance_wire_names* names, int32_t 
         if (!names || !out) return fail(BLANCE_ERR_BAD_ARG, "null argument");
         *out = nullptr;
         std::unique_ptr<blance_batch_dict> d(new blance_batch_dict);
-        WdHostTables& t = d->tables;
-        const int st = wd_host_tables(names, n_parts, n_nodes_ext, n_states, t);
-        if (st) return st;
+        if (int st = wire_fail(dict_block_build(names, n_parts, n_nodes_ext, n_states, *d), WireSide::kDict)) return st;
         d->n_parts = n_parts; d->n_nodes_ext = n_nodes_ext; d->n_states = n_states;
-        size_t words = kBatchDictHdr, at[3][3];
-        for (int k = 0; k < 3; k++) {
-            const size_t nb = (size_t)t.off32[k][(size_t)t.n[k]];
-            const size_t w[3] = {t.slots[k].size(), t.off32[k].size(), (nb + 3) / 4};
-            for (int j = 0; j < 3; j++) { at[k][j] = words; words += (w[j] + 3) & ~(size_t)3; }
-        }
-        if (words > (size_t)INT32_MAX) return fail(BLANCE_ERR_UNSUPPORTED, "names of 2^31 bytes or more");
-        d->block.assign(words, 0);
-        int32_t* b = d->block.data();
-        for (int k = 0; k < 3; k++) {
-            const size_t nb = (size_t)t.off32[k][(size_t)t.n[k]];
-            b[4 * k] = (int32_t)at[k][0]; b[4 * k + 1] = (int32_t)t.mask[k]; b[4 * k + 2] = (int32_t)at[k][2]; b[4 * k + 3] = (int32_t)at[k][1];
-            b[12 + k] = t.n[k];
-            memcpy(b + at[k][0], t.slots[k].data(), sizeof(int32_t) * t.slots[k].size());
-            memcpy(b + at[k][1], t.off32[k].data(), sizeof(int32_t) * t.off32[k].size());
-            if (nb) memcpy(b + at[k][2], t.bytes[k], nb);
-            t.bytes[k] = b + at[k][2];                   // (the caller's blobs are gone after this call)
-        }
         *out = d.release();
         return BLANCE_OK;
     });
@@ -4552,16 +4398,10 @@ extern "C" void blance_batch_dict_destroy(blance_batch_dict* d) { delete d; }
 extern "C" int blance_batch_doc_bounds(const blance_problem* pb, const blance_batch_doc* dc, const blance_batch_names* nm,
                                        int64_t* result_cap, int64_t* moves_cap, size_t* wire_cap) {
     if (!pb || !dc || !pb->state_constraints || pb->n_parts < 0 || pb->n_states < 0) return fail(BLANCE_ERR_BAD_ARG, "null argument");
-    const int64_t refs = (int64_t)(dc->len / 3);
-    int64_t rc = blance_result_capacity(pb);
-    if (dc->assign_too) {
-        int64_t ksum = 0;
-        for (int m = 0; m < pb->n_states; m++) ksum += pb->state_constraints[m] > 0 ? pb->state_constraints[m] : 0;
-        rc = (int64_t)pb->n_parts * ksum + refs;
-    }
-    if (result_cap) *result_cap = rc;
-    if (moves_cap) *moves_cap = refs + rc;
-    if (wire_cap) *wire_cap = nm ? batch_wire_cap_of(pb, nm, rc) : 0;
+    const DocBounds b = batch_doc_bounds(pb, dc->len, dc->assign_too != 0, nm, blance_result_capacity(pb));
+    if (result_cap) *result_cap = b.result_cap;
+    if (moves_cap) *moves_cap = b.moves_cap;
+    if (wire_cap) *wire_cap = b.wire_cap;
     return BLANCE_OK;
 }
 
@@ -4574,7 +4414,7 @@ int batch_wire_check(BatchProblem& b) {
     if (wr->names->n_parts != pb->n_parts || wr->names->n_nodes_ext != pb->n_nodes_ext || wr->names->n_states != pb->n_states)
         return fail(BLANCE_ERR_BAD_ARG, "the names were made for other sizes than the problem's");
     if (pb->max_iterations <= 0) return fail(BLANCE_ERR_BAD_ARG, "a document asked for a problem with max_iterations <= 0 (no map)");
-    b.wire_cap = batch_wire_cap_of(pb, wr->names, b.result_cap);
+    b.wire_cap = batch_wire_cap_of(pb, *wr->names, b.result_cap);
     if (wr->cap < b.wire_cap) return fail(BLANCE_ERR_CAPACITY, "document capacity too small");
     return BLANCE_OK;
 }
@@ -4706,7 +4546,7 @@ struct BatchCall {
             if (!st && !b.dc) b.result_cap = blance_result_capacity(b.pb);
             if (!st) st = batch_result_check(b);
             if (!st && b.mv) st = batch_moves_check(b);
-            if (!st && b.ps) st = batch_stats_check(b.pb, b.ps);
+            if (!st && b.ps) st = stats_arrays_check(b.ps, b.pb->n_states);
             if (!st && b.wr) st = batch_wire_check(b);
             if (st) return fail_problem(st, i);
         }

@@ -341,6 +341,11 @@ struct BatchWireDesc {
 // int32 offsets (word offset) --, then the three counts; then the tables, each at a multiple of 4 words.
 constexpr int kBatchDecodeThreads = 256;
 constexpr int kBatchDictHdr = 16;
+// the hash of a name in a dictionary's tables (WdTable, k_wire_decode.h): FNV-1a over the unescaped bytes, the length folded
+// in.  One definition for the host that builds the tables (host/wire_names.hpp) and both translation units that parse.
+BLANCE_HOST_DEVICE inline uint32_t wd_hash_init() { return 2166136261u; }
+BLANCE_HOST_DEVICE inline uint32_t wd_hash_step(uint32_t h, unsigned b) { return (h ^ b) * 16777619u; }     // FNV-1a
+BLANCE_HOST_DEVICE inline uint32_t wd_hash_done(uint32_t h, int n) { h ^= (uint32_t)n; h ^= h >> 15; return h; }
 constexpr int kBatchDecodeLdsHead = 4096;                   // scan and reduction words in front of the parse stage
 // summary words of one document (k_batch_decode's place-and-sum), int32 unless said otherwise
 enum { kBdRefusal = 0 /* 64 bit: all ones, or offset << 8 | reason */, kBdRecords = 2, kBdRefs = 3, kBdLongest = 4, kBdFresh = 5,

@@ -80,9 +80,7 @@ struct WireDecodeParams {
     unsigned long long* refusal;                             // all ones: min over the refusals of offset << 8 | reason
 };
 
-__host__ __device__ inline uint32_t wd_hash_init() { return 2166136261u; }
-__host__ __device__ inline uint32_t wd_hash_step(uint32_t h, unsigned b) { return (h ^ b) * 16777619u; }     // FNV-1a
-__host__ __device__ inline uint32_t wd_hash_done(uint32_t h, int n) { h ^= (uint32_t)n; h ^= h >> 15; return h; }
+// (wd_hash_init / wd_hash_step / wd_hash_done: blance_kernels.h, shared with the host that builds the tables)
 
 #ifdef BLANCE_SIMT_EMU
 inline unsigned long long wd_atomic_min(unsigned long long* p, unsigned long long v) {
